@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- H.264 bytes/s of the arithmetic re-encode hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 2|3|4|5] [--kind cabac|range]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 2|3|4|5] [--kind cabac|range] [--full] [--dump-outputs DIR]
 
 A step is one pass of the hot path over one batch of synthetic slices that is already
 resident in HBM (wave-interleaved tiles, generated on the device from seeded streams,
@@ -12,9 +12,13 @@ clip, 1 slice per frame -- on every rank (weak scaling: rank r owns slices
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline      dominant kernel (the encode kernel): algorithmic bytes per launch / average
                 launch duration (HIP events on the launching stream) against HBM peak
+and, with --full only (measurements of their own, after the timed steps):
   cpu_baseline  the same coding done on the host CPU cores over a bounded sample of the same
                 workload: oracle/_ref (the reference's own arithmetic_code.h) when it has been
                 built, else the oracle restatement; GPU output is byte-compared with it.
+  e2e, e2e_cabac8  PCIe-inclusive rate of the batch API (host records in, host bytes out).
+A plain run sets up, warms up, times the steps and prints the line.  --dump-outputs DIR also writes what
+the last timed step computed (rank 0's batch) to DIR/*.npy: see dump_outputs().
 """
 import argparse
 import json
@@ -249,6 +253,51 @@ def e2e_block(avr, workload, kind, n_slices, first_slice, device, rounds=12, obj
             "h2d_ms_alone": tm["h2d_ms"], "note": "PCIe-inclusive; never the bench line's value"}
 
 
+def dump_outputs(w, out_dir, final_states, budget=60_000_000):
+    """What the last timed step handed its caller, as .npy files under out_dir, at most `budget` bytes in all:
+      out_len.npy, status.npy   every slice's coded length and status (float64, float32)
+      digest.npy                every slice's coded bytes folded into one number: sum of (byte + 1) * w(position), w odd and
+                                below 2^24, modulo 2^52 (float64, exact)
+      sample_slices.npy         a fixed, seeded sample of slice numbers (float64) ...
+      sample_bytes.npy          ... their coded bytes one after another (float32, 0..255)
+      sample_final_states.npy   ... their final context states, one row per slice (float32; K1 only)
+    The inputs are the seeded synthetic workload, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    dev = w.out.device
+    torch.cuda.synchronize(dev)
+    n = w.n_slices
+    start = w.out_off[:-1]
+    lens = torch.minimum(w.out_len.to(torch.int64), w.out_off[1:] - start)     # (a slice in error may report more than fits)
+    seg = torch.repeat_interleave(torch.arange(n, device=dev), lens)
+    pos = torch.arange(seg.numel(), device=dev) - (torch.cumsum(lens, 0) - lens)[seg]
+    val = w.out[start[seg] + pos].to(torch.int64) + 1
+    weight = ((pos * 0x9E3779B1) & 0xFFFFFF) | 1
+    digest = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, seg, val * weight) & ((1 << 52) - 1)
+    lens_h = lens.cpu().numpy()
+    arrays = {"out_len": lens_h.astype(np.float64), "status": w.status.cpu().numpy().astype(np.float32),
+              "digest": digest.cpu().numpy().astype(np.float64)}
+    left = budget - sum(a.nbytes + 128 for a in arrays.values()) - 3 * 128
+    ns = w.n_states if final_states else 0
+    pick = []
+    for i in np.random.default_rng(0).permutation(n):
+        cost = 4 * (int(lens_h[i]) + ns) + 8
+        if cost > left:
+            break
+        pick.append(int(i))
+        left -= cost
+    off_h = start.cpu().numpy()
+    arrays["sample_slices"] = np.array(pick, dtype=np.float64)
+    arrays["sample_bytes"] = (torch.cat([w.out[int(off_h[i]):int(off_h[i]) + int(lens_h[i])] for i in pick]).cpu().numpy()
+                              if pick else np.zeros(0, np.uint8)).astype(np.float32)
+    if final_states:
+        fs = w.final_states.view(n, w.n_states)[torch.tensor(pick, dtype=torch.int64, device=dev)]
+        arrays["sample_final_states"] = fs.cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N ...` with no launcher around it: N ranks of this same command line under torch.distributed.run
     (one process per GPU, rendezvous on 127.0.0.1 at a port that is free now).  Returns the child's exit code; rank 0's JSON
@@ -294,8 +343,13 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank codes its own copy of the workload's slice count (default); strong: ONE batch of the "
                          "workload's slice count is split over the ranks (contiguous ranges of near-equal bin totals)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive block (host records in, host bytes out)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the CPU baseline (byte-compared with the GPU output) and the "
+                         "PCIe-inclusive blocks (e2e, e2e_cabac8); a plain run measures only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (rank 0's batch) to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the PCIe-inclusive block (host records in, host bytes out)")
     ap.add_argument("--test-hook", action="append", default=[], metavar="NAME=VALUE",
                     help="MEASUREMENT ONLY: run on the -DAVR_TEST_HOOKS build of the library with this hook set (csrc/avr_internal.h); "
                          "the line says so in config.test_hooks.  The product library has no such switches")
@@ -464,12 +518,14 @@ def main():
                                                  "note": "0 guessed = the step asked the device and waited (no warm-up step before it)"}),
             "prepass_ms_in_step": prepass_ms,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(w, args.dump_outputs, final_states=kind == avr.KIND_CABAC and args.records != "resolved")
+        if args.full and world == 1 and not args.no_cpu_baseline:
             def gpu_bytes_of(m):
                 return w.results()[0][:m]
             line["cpu_baseline"] = cpu_baseline(avr, args.workload, kind, n_slices, first, gpu_bytes_of)
             line["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
-        if world == 1 and not args.no_e2e and args.records == "bins":
+        if args.full and world == 1 and not args.no_e2e and args.records == "bins":
             line["e2e"] = e2e_block(avr, args.workload, kind, n_slices, first, local_rank)
             if kind == avr.KIND_CABAC:                           # the same batches as one-byte records (AVR_KIND_CABAC8): half the bytes over PCIe
                 line["e2e_cabac8"] = e2e_block(avr, args.workload, kind, n_slices, first, local_rank, records8=True)

@@ -44,8 +44,8 @@ def oracle():
 def ref():
     import oracle_lib
     lib = oracle_lib.load_ref()
-    if lib is None:
-        pytest.skip("oracle/_ref not built and /root/reference absent")
+    if lib is None:             # oracle/_ref cannot be built here: its recorded answers (tests/golden/make_ref_answers.py)
+        lib = oracle_lib.load_ref_answers()
     return lib
 
 

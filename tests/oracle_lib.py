@@ -187,6 +187,91 @@ class Ref:
         return out[:n].tobytes(), st.tobytes(), status.value
 
 
+class RefAnswers:
+    """oracle/_ref's answers to a fixed set of calls, looked up by the call's arguments: what the tests use where the reference
+    is not there to build oracle/_ref from.  Same methods as Ref.  tests/golden/make_ref_answers.py records them by running the
+    tests against the built library through recorder(); a call that was not recorded raises."""
+    # method -> the types Ref converts its arguments to, and the fields of its answer (one field, or a tuple of them)
+    METHODS = {"half_encode": ((np.uint8,), (bytes,)),
+               "half_decode": ((bytes, int), (np.ndarray,)),
+               "range_encode": ((np.uint16,), (bytes, int)),
+               "range_decode": ((bytes, np.uint16), (np.ndarray,)),
+               "cabac_encode": ((np.uint16, np.uint8), (bytes, bytes, int))}
+
+    def __init__(self):
+        self.table = {}                                      # key -> (method, answer)
+
+    @classmethod
+    def key(cls, name, args):
+        import hashlib
+        h = hashlib.sha256(name.encode())
+        for a, t in zip(args, cls.METHODS[name][0]):
+            b = (bytes(a) if t is bytes else int(a).to_bytes(8, "little", signed=True) if t is int
+                 else np.ascontiguousarray(a, dtype=t).tobytes())
+            h.update(len(b).to_bytes(8, "little"))
+            h.update(b)
+        return h.digest()
+
+    def __getattr__(self, name):
+        if name not in self.METHODS:
+            raise AttributeError(name)
+
+        def answer(*args):
+            k = self.key(name, args)
+            if k not in self.table:
+                raise KeyError(f"ref.{name}: no recorded answer for these arguments (the tests ask oracle/_ref something new: "
+                               "rerun tests/golden/make_ref_answers.py where the reference is)")
+            return self.table[k][1]
+        return answer
+
+    def recorder(self, ref):
+        """A stand-in for `ref` (a Ref) that passes every call on and keeps the answer in this table."""
+        table = self.table
+
+        class Recorder:
+            def __getattr__(self, name):
+                def call(*args):
+                    out = getattr(ref, name)(*args)
+                    table[RefAnswers.key(name, args)] = (name, out)
+                    return out
+                return call
+        return Recorder()
+
+    def save(self, path):
+        names = sorted(self.METHODS)
+        keys, methods, fields, blob, at = [], [], [], [], 0
+        for k, (name, out) in self.table.items():
+            row = [(0, 0)] * 3                               # per field: (offset, length) into blob, or (value, -1) for an int
+            for j, v in enumerate(out if isinstance(out, tuple) else (out,)):
+                if isinstance(v, int):
+                    row[j] = (v, -1)
+                else:
+                    b = v.tobytes() if isinstance(v, np.ndarray) else bytes(v)
+                    row[j] = (at, len(b))
+                    blob.append(b)
+                    at += len(b)
+            keys.append(np.frombuffer(k, np.uint8))
+            methods.append(names.index(name))
+            fields.append(row)
+        np.savez_compressed(path, keys=np.array(keys, np.uint8).reshape(-1, 32), methods=np.array(methods, np.int64),
+                            fields=np.array(fields, np.int64).reshape(-1, 3, 2), blob=np.frombuffer(b"".join(blob), np.uint8))
+
+    @classmethod
+    def load(cls, path):
+        names = sorted(cls.METHODS)
+        g = np.load(path, allow_pickle=False)
+        blob = g["blob"]
+        self = cls()
+        for k, m, row in zip(g["keys"], g["methods"], g["fields"]):
+            name = names[int(m)]
+            vals = [int(a) if t is int else blob[a:a + n].tobytes() if t is bytes else blob[a:a + n].copy()
+                    for t, (a, n) in zip(cls.METHODS[name][1], row)]
+            self.table[k.tobytes()] = (name, vals[0] if len(vals) == 1 else tuple(vals))
+        return self
+
+
+REF_ANSWERS = os.path.join(ROOT, "tests", "golden", "ref_answers.npz")
+
 _oracle = None
 _ref = False
 
@@ -204,6 +289,11 @@ def load_ref():
         path = build_ref()
         _ref = Ref(path) if path else None
     return _ref
+
+
+def load_ref_answers():
+    """What the tests ask oracle/_ref, answered from tests/golden/ref_answers.npz (for where oracle/_ref cannot be built)."""
+    return RefAnswers.load(REF_ANSWERS)
 
 
 # ---------------------------------------------------------------- seeded stream makers shared by tests

@@ -1,10 +1,9 @@
 """f4: the bin-stream source without FFmpeg (avrecode-ms_amd/csrc/host/avr_h264.h) and the `recode` command line on top of it.
 
-The real-stream fixtures are the two CABAC H.264 MP4s that ship with the image (imageio's resources):
+The real-stream fixtures are two CABAC H.264 MP4s from imageio's standard images, kept in tests/golden/:
     realshort.mp4   High profile 4:2:0, 8x8 transform, I / P slices, 36 slices of 300 macroblocks
     cockatoo.mp4    High 4:4:4 Predictive (x264 build 142), weighted prediction, 3-4 references, I / P / B slices,
                     280 slices of 3600 macroblocks
-They are not copied into the repository; a test that needs them is skipped where they are absent.
 
 What parsing them to the end pins: the slice-data syntax and every context derivation of the parser, and -- because a wrong
 (m, n) of a context a stream uses derails the arithmetic decoder within a few bins -- the initialisation values typed
@@ -18,7 +17,7 @@ import subprocess
 
 import pytest
 
-IMAGES = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images"
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CLIPS = {"realshort.mp4": (36, 300), "cockatoo.mp4": (280, 3600)}
 
 
@@ -28,10 +27,7 @@ def recode(avr):
 
 
 def clip(name):
-    path = os.path.join(IMAGES, name)
-    if not os.path.exists(path):
-        pytest.skip(f"{path} is not in this image")
-    return path
+    return os.path.join(GOLD, name)
 
 
 @pytest.mark.parametrize("name", sorted(CLIPS))

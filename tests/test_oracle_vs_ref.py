@@ -1,8 +1,9 @@
 """Pin the oracle (oracle/avr_oracle.c) against the reference's own range coder.
 
-oracle/_ref is /root/reference/arithmetic_code.h compiled unmodified (oracle/ref_harness.cpp);
-these tests run wherever that library exists (it is built here, and travels prebuilt to the
-GPU box).  They follow the reference's only active unit test, test/arithmetic_code.cpp:93-111
+oracle/_ref is the reference's arithmetic_code.h compiled unmodified (oracle/ref_harness.cpp).
+Where it cannot be built (no reference checkout), the `ref` fixture answers the same calls
+from tests/golden/ref_answers.npz, recorded from it by tests/golden/make_ref_answers.py.
+They follow the reference's only active unit test, test/arithmetic_code.cpp:93-111
 (random bits, p = 1/2, encode -> decode -> compare), and extend it to the two instantiations
 recode.cpp and cabac_code.h use.
 """

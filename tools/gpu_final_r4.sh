@@ -9,7 +9,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 bench() { # name args...
   local name=$1; shift
-  timeout -k 10 500 python3 $R/bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }
+  timeout -k 10 500 python3 $R/bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_$name.json'));c=d.get('cpu_baseline') or {};e=d.get('e2e') or {};e8=d.get('e2e_cabac8') or {};print('$name', round(d['ms_per_step'],3),'ms', round(d['value']/1e9,3),'GB/s frac', round(d['roofline']['frac'],4), '| cpu', c.get('kind'), round(c.get('value',0)/1e6,1), 'MB/s x', round(d.get('gpu_over_cpu',0),1), c.get('parity_vs_gpu'), '| e2e', round(e.get('value',0)/1e9,2), 'cabac8', round(e8.get('value',0)/1e9,2))"
 }
 if [ "$PART" = a ]; then
