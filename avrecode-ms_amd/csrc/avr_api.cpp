@@ -199,6 +199,7 @@ int avr_test_hook_set(const char *name, uint32_t value) {
     else if (!strcmp(name, "k2p_seg_len")) h.k2p_seg_len = value;
     else if (!strcmp(name, "local_waves")) h.local_waves = value;
     else if (!strcmp(name, "k2p_wave")) h.k2p_wave = value;
+    else if (!strcmp(name, "k1p_keep_retry")) h.k1p_keep_retry = value;
     else if (!strcmp(name, "k1_waves")) h.k1_waves = value;
     else if (!strcmp(name, "k1_fwd")) h.k1_fwd = value;
     else if (!strcmp(name, "k1_words8")) h.k1_words8 = value;

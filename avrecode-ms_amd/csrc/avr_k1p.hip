@@ -1657,7 +1657,7 @@ hipError_t launch_k1p_code(hipStream_t s, const uint8_t *codes, const uint32_t *
     const Plan p{nullptr, nullptr, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
                  pl->dig_off, 0, 0, nullptr, nullptr};
     hipError_t e = launch_code(s, p, n_slices, pl, static_cast<uint8_t *>(workspace), codes, 0xffffffffu, out, out_off, out_len, status);
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
     return launch_cabac_encode_codes(s, codes, pl->res_off, n_bins, nullptr, n_slices, out, out_off, out_len, status,
                                      AVR_SLICE_RETRY_SERIAL);
 }

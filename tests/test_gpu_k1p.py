@@ -165,14 +165,28 @@ def test_chunked_full_size_config2_sampled(avr, oracle):
     assert w.results()[0] == again == got
 
 
-def test_chunked_full_size_config2_every_slice(avr, oracle):
+@pytest.mark.parametrize("steps", ["one-call", "bench"])
+def test_chunked_full_size_config2_every_slice(avr, oracle, steps):
     """The headline path (BASELINE.json configs[1] through encode_chunked(), i.e. K1p) with EVERY one of its 512 slices against the
     oracle -- cabac_code.h:33-67 on arithmetic_code.h, threaded over the host's cores -- through a checksum of checksums, and the
-    final context states of every slice beside the bytes (the twin of test_range_chunked_full_size's check of the compress direction)."""
+    final context states of every slice beside the bytes (the twin of test_range_chunked_full_size's check of the compress direction).
+    steps "bench": the path bench.py times -- set_parts(0) (two parts on streams of their own at this size), one step,
+    synchronise, settle(), then two more steps sized by the hint, without clearing the outputs in between."""
     import hashlib
+    import torch
     n_slices = 512
     w = avr.DeviceWorkload.synth(2, n_slices, avr.KIND_CABAC, 0, 1000)
-    w.encode_chunked()
+    if steps == "bench":
+        assert w.set_parts(0) == 2
+        w.encode_chunked()
+        torch.cuda.synchronize()
+        w.settle()
+        w.encode_chunked()
+        w.encode_chunked()
+        torch.cuda.synchronize()
+        assert not w.settle()["redone"]
+    else:
+        w.encode_chunked()
     got, status = w.results()
     assert not any(status)
     cfg, nbh, off, recs, states = host_synth(avr, 2, n_slices, avr.KIND_CABAC, 1000)
@@ -185,6 +199,12 @@ def test_chunked_full_size_config2_every_slice(avr, oracle):
     dig = lambda chunks: hashlib.sha256(b"".join(hashlib.sha256(c).digest() for c in chunks)).hexdigest()
     assert [len(x) for x in got] == [len(x) for x in want]
     assert dig(got) == dig(want)
+    from concurrent.futures import ThreadPoolExecutor                 # the oracle's final states, a slice per call (ctypes lets go of the GIL)
+    ns = cfg.n_states
+    with ThreadPoolExecutor(16) as ex:
+        want_fs = list(ex.map(lambda i: oracle.cabac_encode(parts[i], states[i * ns:(i + 1) * ns])[1], range(n_slices)))
+    fs = w.final_states.cpu().numpy().reshape(n_slices, ns)
+    assert dig([fs[i].tobytes() for i in range(n_slices)]) == dig(want_fs)
 
 
 def test_batch_api_takes_the_chunked_path_for_long_slices(avr, oracle, hooks):

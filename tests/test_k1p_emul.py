@@ -149,3 +149,27 @@ def test_fp64_division_of_the_recoded_coder_is_exact(emul):
     the CPU against the integer divide: 200 000 dividends below 2^63 (edges, exact multiples, all-ones low words) times
     every divisor 1..255."""
     assert emul.div_emul_check(7, 200000) == 0
+
+
+@pytest.mark.parametrize("end", ["carry", "none", "cut"])
+def test_long_carry_chains(emul, oracle, end):
+    """Chains of 30 .. 20 000 16-bit digits (tests/carry_streams.py) -- past one of phase D's 33-digit segments, one of its
+    8 448-digit tiles, two tiles -- that one carry turns from 0xff to 0x00 ("carry"), that stay 0xff ("none") or that
+    finish() decides ("cut"): exact bytes and final states, and none of them declined."""
+    import carry_streams
+    for k, n_chain in enumerate((30, 70, 2200, 9000, 20000)):
+        recs, st = carry_streams.carry_chain_cabac(np.random.default_rng(700 + k), 3 + 40 * k, n_chain, end)
+        want = oracle.cabac_encode(recs, st)
+        data, final, info = k1p(emul, recs, st)
+        assert info[3] == 0 and (data, final) == want[:2], f"chain {n_chain} {end} info={info}"
+        assert carry_streams.longest_run(data, 0 if end == "carry" else data[2 * (3 + 40 * k) + 8])[1] >= 2 * (n_chain - 3)
+
+
+def test_long_carry_chain_without_lps_is_declined(emul, oracle):
+    """A chain with no coded LPS for more than 16 chunks: declined (the kernels hand it to the serial kernel), not mis-coded."""
+    import carry_streams
+    recs, st = carry_streams.carry_chain_cabac(np.random.default_rng(77), 5, 3000, "carry", n_ctx=4, p_bypass=1.0,
+                                               init_states=[124, 125, 124, 125])
+    assert carry_streams.longest_run(oracle.cabac_encode(recs, st)[0], 0)[1] >= 2 * (3000 - 3)
+    _, _, info = k1p(emul, recs, st)
+    assert info[3] == 1

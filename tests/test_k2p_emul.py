@@ -102,3 +102,29 @@ def test_zero_probability_bin_is_reported(emul, oracle):
     recs = np.array([0 | (3 << 1) | (4 << 8)] * 100 + [1 | (0 << 1) | (9 << 8)] + [0 | (3 << 1) | (4 << 8)] * 50, np.uint16)
     assert oracle.range_encode(recs)[1] == 1
     assert emul_encode(emul, recs, 16)[0] is None
+
+
+@pytest.mark.parametrize("end", ["carry", "none", "cut"])
+@pytest.mark.parametrize("chunk", [64, 1024])
+def test_long_carry_chains(emul, oracle, end, chunk):
+    """Runs of 0xff that one carry turns into 0x00 ("carry"), that stay ("none") or that finish() decides ("cut")
+    (tests/carry_streams.py), shorter than, as long as and longer than the finishing pass's 64-position segments and
+    4 096-position tiles."""
+    import carry_streams
+    for k, run in enumerate((40, 64, 100, 4096, 4500, 9000)):
+        recs = chain_with_run(carry_streams, 800 + k, 5 + 31 * k, run, end)
+        want, status = oracle.range_encode(recs)
+        got, info = emul_encode(emul, recs, chunk)
+        assert status == 0 and got == want, f"run {run} {end} chunk={chunk} info={info}"
+
+
+def chain_with_run(carry_streams, seed, n_lead, run, end):
+    """A K2 chain whose carry run (the 0x00 run of its "carry" form) is exactly `run` bytes long."""
+    n_chain = run + 8
+    for _ in range(4):
+        c = carry_streams.carry_chain_range(np.random.default_rng(seed), n_lead, n_chain, "carry")
+        got = carry_streams.longest_run(oracle_lib.load_oracle().range_encode(c)[0], 0)[1]
+        if got == run:
+            return c if end == "carry" else carry_streams.carry_chain_range(np.random.default_rng(seed), n_lead, n_chain, end)
+        n_chain += run - got
+    raise AssertionError(f"no chain with a run of {run}")
