@@ -158,12 +158,15 @@ SIGNATURES = {
     "avr_multi_add_slice_cabac": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     "avr_multi_add_slice_range": (c_int, [c_void_p, c_void_p, c_size_t]),
     "avr_multi_add_slice_codes": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "avr_multi_add_slice_cabac8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     "avr_multi_run": (c_int, [c_void_p]),
     "avr_multi_get": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int)]),
     "avr_multi_placement": (c_int, [c_void_p, c_size_t]),
     "avr_multi_load": (c_int, [c_void_p, c_void_p]),
     "avr_pack_tiles_device": (c_int, [c_int, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p, c_void_p, c_void_p]),
+    "avr_pack_tiles8_device": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p, c_void_p, c_void_p]),
     "avr_cabac_encode_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avr_range_encode_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
@@ -172,6 +175,10 @@ SIGNATURES = {
     "avr_cabac_encode_chunked_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                                 c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p]),
+    "avr_cabac8_chunked_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
+    "avr_cabac8_encode_chunked_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                 c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]),
     "avr_cabac_encode_chunked_device_hinted": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                                        c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                                        c_void_p, c_uint32, c_void_p]),
@@ -465,6 +472,13 @@ class MultiBatch:
         c = np.ascontiguousarray(codes, dtype=np.uint8)
         return _check(self._L.avr_multi_add_slice_codes(self._h, c.ctypes.data, c.size))
 
+    def add_slice_cabac8(self, recs8, init_states) -> int:
+        """K1 from one-byte records (as Batch.add_slice_cabac8; n_states <= MAX_STATES8)."""
+        import numpy as np
+        r = np.ascontiguousarray(recs8, dtype=np.uint8)
+        s = np.ascontiguousarray(init_states, dtype=np.uint8)
+        return _check(self._L.avr_multi_add_slice_cabac8(self._h, r.ctypes.data, r.size, s.ctypes.data, s.size))
+
     def run(self):
         _check(self._L.avr_multi_run(self._h))
 
@@ -485,6 +499,7 @@ class MultiBatch:
 
 from .device import DeviceWorkload, encode_tiles, plan_tiles, synth_config  # noqa: E402  (torch-backed helpers)
 
-__all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_RANGE", "SEL_BYPASS", "SEL_TERMINATE",
+__all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE",
+           "SEL_BYPASS", "SEL_TERMINATE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
            "make_cabac_records", "make_range_records", "plan_tiles", "synth_config", "tail_patch"]

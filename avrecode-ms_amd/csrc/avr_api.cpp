@@ -128,7 +128,7 @@ struct avr_batch {
 
     // device side
     DevBuf<uint16_t> d_recs;
-    DevBuf<uint8_t> d_recs8;                // one-byte records as they came over PCIe (widened into d_recs on the device)
+    DevBuf<uint8_t> d_recs8;                // one-byte records as they came over PCIe (what the kernels read: no two-byte copy)
     DevBuf<uint4> d_tiles;
     DevBuf<uint64_t> d_rec_off, d_tile_off, d_out_off, d_dense_off;
     DevBuf<uint32_t> d_n_bins, d_order, d_out_len;
@@ -316,9 +316,9 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
         b->rec_off.push_back(off + padded);
         *where = dst;
     } else if (recs8) {
-        // one byte per record in the same pinned buffer, slice i at BYTE rec_off[i] (its records will be at record rec_off[i] on the
-        // device); what lies between a slice's last record and the next multiple of 8 is made a no-op by the widening kernel
-        const uint64_t padded = (uint64_t(n) + 7) & ~uint64_t(7);
+        // one byte per record in the same pinned buffer, slice i at BYTE rec_off[i], a multiple of 16 (the one-byte kernels read
+        // 16-byte groups); what lies between a slice's last record and the next multiple of 16 is told apart by its index there
+        const uint64_t padded = (uint64_t(n) + 15) & ~uint64_t(15);
         uint8_t *dst = reinterpret_cast<uint8_t *>(b->h_recs.p) + off;
         memset(dst + n, 0, padded - n);
         b->rec_off.push_back(off + padded);
@@ -466,7 +466,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     b->last_path = chunked;
 
     int rc;
-    if ((rc = b->d_recs.reserve(total_recs)) || (b->recs8 && (rc = b->d_recs8.reserve(total_recs + 16))) || (!chunked && (rc = b->d_tiles.reserve(total_chunks))) ||
+    if ((b->recs8 ? (rc = b->d_recs8.reserve(total_recs + 16)) : (rc = b->d_recs.reserve(total_recs))) || (!chunked && (rc = b->d_tiles.reserve(total_chunks))) ||
         (rc = b->d_rec_off.reserve(n + 1)) || (rc = b->d_tile_off.reserve(n_tiles + 1)) ||
         (rc = b->d_out_off.reserve(n + 1)) || (rc = b->d_dense_off.reserve(n + 1)) ||
         (rc = b->d_n_bins.reserve(n)) || (rc = b->d_order.reserve(n)) || (rc = b->d_out_len.reserve(n)) ||
@@ -484,6 +484,10 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     const avr::DenseHint hint{use_hint ? std::min<uint32_t>(b->dense_hint, uint32_t(ns)) : 0u, b->h_ndense.p, b->h_ndense.p + 1};
     b->hint_used = hint.rows;
     b->h_ndense.p[0] = b->h_ndense.p[1] = 0;
+    if (b->recs8 && chunked) {                                   // the one-byte K1p call needs no guess: its contexts are the slices' n_states
+        b->hint_used = 0;
+        b->h_ndense.p[0] = uint32_t(ns);
+    }
     AVR_HIP(hipEventRecord(b->ev[0], s));
     if (b->recs8) AVR_HIP(hipMemcpyAsync(b->d_recs8.p, b->h_recs.p, total_recs, hipMemcpyHostToDevice, s));        // one byte a record
     else AVR_HIP(hipMemcpyAsync(b->d_recs.p, b->h_recs.p, total_recs * sizeof(uint16_t), hipMemcpyHostToDevice, s));
@@ -497,8 +501,6 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if (cabac && ns) AVR_HIP(hipMemcpyAsync(b->d_states.p, b->h_states.p, n * ns, hipMemcpyHostToDevice, s));
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
-    if (b->recs8)                                                // ... widened into the records the kernels read: from here on an AVR_KIND_CABAC batch
-        AVR_HIP(avr::launch_expand_records8(s, b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), total_recs, b->d_recs.p));
     // Both K1 paths renumber the batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
     // their census pass, the one-lane-per-slice kernel through launch_cabac_encode): records and states go in as they are.
     if (chunked && !cabac) {
@@ -549,11 +551,19 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         AVR_STAGE(b->d_blk_slice.p, blk_slice.data(), blk_slice.size());
         AVR_HIP(hipEventRecord(b->ev[2], s));
         uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
-        AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(ns), &plan, wsp,
-                                b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p, &hint));
+        if (b->recs8)                                            // one-byte records: no census, no guess to check, nothing waits
+            AVR_HIP(avr::launch_k1p8(s, b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(ns), &plan, wsp,
+                                     b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p));
+        else
+            AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(ns), &plan, wsp,
+                                    b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p, &hint));
     } else {
-        AVR_HIP(avr::launch_pack_tiles(s, b->kind, uint32_t(ns), b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
-                                       b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
+        if (b->recs8)                                            // one-byte records widened, validated and transposed in one pass
+            AVR_HIP(avr::launch_pack_tiles8(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
+                                            b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
+        else
+            AVR_HIP(avr::launch_pack_tiles(s, b->kind, uint32_t(ns), b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
+                                           b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
         AVR_HIP(hipEventRecord(b->ev[2], s));
         if (cabac)
             AVR_HIP(avr::launch_cabac_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_states.p,
@@ -728,7 +738,7 @@ static int multi_add(avr_multi *m, int kind, const void *data, size_t n, size_t 
     if (n > 0xfffffff0u) return fail(AVR_ERR_INVALID, "slice too long");
     if (m->n_bins.size() >= m->max_slices) return fail(AVR_ERR_CAPACITY, "batch holds max_slices=%zu slices", m->max_slices);
     if (m->total_bins + n > m->max_bins) return fail(AVR_ERR_CAPACITY, "batch holds max_bins=%zu records", m->max_bins);
-    if (kind == AVR_KIND_CABAC) {
+    if (kind == AVR_KIND_CABAC || kind == AVR_KIND_CABAC8) {
         if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
         if (!init_states && n_states) return fail(AVR_ERR_INVALID, "null init_states");
         if (!m->n_bins.empty() && n_states != m->n_states) return fail(AVR_ERR_INVALID, "all slices of a batch use the same n_states");
@@ -749,6 +759,11 @@ int avr_multi_add_slice_cabac(avr_multi *m, const uint16_t *recs, size_t n, cons
 }
 int avr_multi_add_slice_range(avr_multi *m, const uint16_t *recs, size_t n) { return multi_add(m, AVR_KIND_RANGE, recs, n, 2, nullptr, 0); }
 int avr_multi_add_slice_codes(avr_multi *m, const uint8_t *codes, size_t n) { return multi_add(m, AVR_KIND_CABAC_CODES, codes, n, 1, nullptr, 0); }
+int avr_multi_add_slice_cabac8(avr_multi *m, const uint8_t *recs8, size_t n, const uint8_t *init_states, size_t n_states) {
+    if (n_states > AVR_MAX_STATES8)                              // (first: what needs no batch is checked without one)
+        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    return multi_add(m, AVR_KIND_CABAC8, recs8, n, 1, init_states, n_states);
+}
 
 int avr_multi_run(avr_multi *m) {
     if (!m) return fail(AVR_ERR_INVALID, "null batch");
@@ -783,6 +798,7 @@ int avr_multi_run(avr_multi *m) {
             int r;
             if (m->kind == AVR_KIND_CABAC)
                 r = avr_batch_add_slice_cabac(b, reinterpret_cast<const uint16_t *>(p), m->n_bins[i], m->states.data() + size_t(i) * m->n_states, m->n_states);
+            else if (m->kind == AVR_KIND_CABAC8) r = avr_batch_add_slice_cabac8(b, p, m->n_bins[i], m->states.data() + size_t(i) * m->n_states, m->n_states);
             else if (m->kind == AVR_KIND_RANGE) r = avr_batch_add_slice_range(b, reinterpret_cast<const uint16_t *>(p), m->n_bins[i]);
             else r = avr_batch_add_slice_codes(b, p, m->n_bins[i]);
             if (r < 0) { rc[d] = r; err[d] = avr_last_error(); }
@@ -839,6 +855,28 @@ int avr_pack_tiles_device(int device, void *stream, int kind, size_t n_states, c
     return AVR_OK;
 }
 
+// one-byte records: what the host can check of the layout -- the base 16-byte aligned, the offsets' array 8-byte aligned (the offsets
+// themselves live on the device, where the kernels flag a slice whose offset is not a multiple of 16)
+static int check_recs8(const uint8_t *recs8, const uint64_t *rec_off, size_t n_states) {
+    if (n_states > AVR_MAX_STATES8)
+        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    if (reinterpret_cast<uintptr_t>(recs8) & 15) return fail(AVR_ERR_INVALID, "recs8 is not 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(rec_off) & 7) return fail(AVR_ERR_INVALID, "rec_off is not 8-byte aligned");
+    return AVR_OK;
+}
+
+int avr_pack_tiles8_device(int device, void *stream, size_t n_states, const uint8_t *recs8, const uint64_t *rec_off,
+                           const uint32_t *n_bins, const uint32_t *order, size_t n_slices, const uint64_t *tile_off, void *tiles,
+                           int32_t *status) {
+    if (int rc = check_common(rec_off, n_bins, tile_off, n_slices)) return rc;
+    if (int rc = check_recs8(recs8, rec_off, n_states)) return rc;
+    if (n_slices && (!recs8 || !tiles || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_pack_tiles8(static_cast<hipStream_t>(stream), uint32_t(n_states), recs8, rec_off, n_bins, order,
+                                    uint32_t(n_slices), tile_off, tiles, status));
+    return AVR_OK;
+}
+
 int avr_cabac_encode_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                   uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states) {
@@ -879,6 +917,28 @@ int avr_cabac_encode_chunked_device(int device, void *stream, const uint16_t *re
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), init_states,
                             uint32_t(n_states), plan, workspace, out, out_off, out_len, status, final_states));
+    return AVR_OK;
+}
+
+size_t avr_cabac8_chunked_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan) {
+    if (!plan || n_states > AVR_MAX_STATES8) return 0;
+    return avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan);
+}
+
+int avr_cabac8_encode_chunked_device(int device, void *stream, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                                     size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
+                                     void *workspace, size_t workspace_bytes, uint8_t *out, const uint64_t *out_off,
+                                     uint32_t *out_len, int32_t *status, uint8_t *final_states) {
+    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
+    if (int rc = check_recs8(recs8, rec_off, n_states)) return rc;
+    if (n_slices && (!recs8 || !out || !out_len || (n_states && !init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->dig_off || !workspace || !status)))
+        return fail(AVR_ERR_INVALID, "null plan pointer");
+    if (workspace_bytes < avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan))
+        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac8_chunked_workspace_bytes()", workspace_bytes);
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_k1p8(static_cast<hipStream_t>(stream), recs8, rec_off, n_bins, uint32_t(n_slices), init_states,
+                             uint32_t(n_states), plan, workspace, out, out_off, out_len, status, final_states));
     return AVR_OK;
 }
 

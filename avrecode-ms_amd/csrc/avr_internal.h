@@ -102,9 +102,9 @@ hipError_t launch_synth_tiles(hipStream_t s, int workload, uint32_t scale, uint6
                               const uint64_t *tile_off, void *tiles, uint8_t *init_states,
                               uint32_t n_states);
 
-// one-byte K1 records (AVR_KIND_CABAC8) -> the two-byte records of the kernels; `total` = records of the batch (a multiple of 8)
-hipError_t launch_expand_records8(hipStream_t s, const uint8_t *in, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                                  uint32_t n_states, uint64_t total, uint16_t *out);
+// one-byte K1 records (AVR_KIND_CABAC8, slice i at byte rec_off[i], a multiple of 16) -> the two-byte tiles of launch_pack_tiles
+hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                              const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);
 hipError_t launch_context_census(hipStream_t s, const uint16_t *recs, uint64_t n, uint32_t *bitmap);
 hipError_t launch_context_remap(hipStream_t s, uint16_t *recs, uint64_t n, const uint16_t *table);
 hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_src, uint8_t *dst, uint32_t n_dst,
@@ -121,6 +121,11 @@ hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t 
                             uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
                             void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
                             uint8_t *final_states);
+// the same from one-byte records (rec_off in bytes, multiples of 16; n_states <= AVR_MAX_STATES8): no census, no wait; workspace as above
+hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                       uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
+                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
+                       uint8_t *final_states);
 size_t k1p_resolve_workspace_bytes(size_t n_slices, uint32_t n_states, const avr_chunk_plan *pl);
 hipError_t launch_k1p_resolve(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                               uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "avr_coder.h"
 #include "avr_internal.h"
@@ -48,7 +49,8 @@ struct Plan {                       // device pointers of the caller's plan (avr
     uint32_t n_states;              // sort keys: the contexts the batch uses, numbered densely 0 .. n_states-1 (k_k1p_densemap)
     uint32_t ns_full;               // contexts per slice as the caller numbers them (init_states / final_states rows)
     const uint16_t *table;          // [1024] caller's context number -> dense id (kNotUsed: occurs nowhere in the batch)
-    const uint16_t *index;          // [n_states] dense id -> caller's context number
+    const uint16_t *index;          // [n_states] dense id -> caller's context number (null: the identity, one-byte records)
+    const uint8_t *recs8;           // one-byte records (AVR_KIND_CABAC8) in place of recs: rec_off in bytes, multiples of 16
 };
 constexpr uint32_t kNotUsed = 0xffffu;
 
@@ -212,6 +214,27 @@ __device__ __forceinline__ void for_record_groups(const uint16_t *r, uint32_t i0
     for (; i < i1; i += 8) f(*reinterpret_cast<const U4 *>(r + i));
 }
 
+// The same walk over one-byte records (AVR_KIND_CABAC8): 16 records a group, 64 a line.  One-byte records have no no-op value --
+// every byte is a context, bypass or terminate bin -- so what lies past a slice's last bin in its last group is told apart by
+// index: f(first index of the group, group, masked) with masked = std::true_type for the groups after the last whole line (the
+// only ones that can reach past i1), std::false_type for the others.  A slice's bytes are readable up to the next multiple of 16.
+template <class F>
+__device__ __forceinline__ void for_record_groups8(const uint8_t *r, uint32_t i0, uint32_t i1, F &&f) {
+    uint32_t i = i0;
+    if (i + 64 <= i1) {
+        const uint32_t last = i0 + ((i1 - i0) / 64u - 1u) * 64u;                 // where the chunk's last whole line starts
+        const U4 *q = reinterpret_cast<const U4 *>(r + i);
+        U4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3];
+        for (; i + 64 <= i1; i += 64) {
+            const U4 *qn = reinterpret_cast<const U4 *>(r + (i + 64 <= last ? i + 64 : last));
+            const U4 n0 = qn[0], n1 = qn[1], n2 = qn[2], n3 = qn[3];
+            f(i, v0, std::false_type{}); f(i + 16, v1, std::false_type{}); f(i + 32, v2, std::false_type{}); f(i + 48, v3, std::false_type{});
+            v0 = n0; v1 = n1; v2 = n2; v3 = n3;
+        }
+    }
+    for (; i < i1; i += 16) f(i, *reinterpret_cast<const U4 *>(r + i), std::true_type{});
+}
+
 // One lane per chunk: counting sort of the chunk's context bins by (dense) context, in LDS, serially.
 //   pass 1  count the bins of every context                    cnt[k][lane]++           (16-bit, lane-private)
 //   scan    exclusive prefix over the contexts                 cnt[k][lane] = first position of context k
@@ -240,19 +263,25 @@ __device__ __forceinline__ void for_record_groups(const uint16_t *r, uint32_t i0
 //   AVR_SLICE_RETRY_CENSUS  (internal) if row nk + 2 is not empty, counting such slices in *n_retry.
 // SelT: uint16_t while the offsets fit (up to 500 contexts) -- with 86 contexts eight waves' rows and a table of 4 KiB are the
 // CU's 160 KiB to the byte -- uint32_t beyond.
-template <class SelT>
+// R8: one-byte records (p.recs8, AVR_KIND_CABAC8).  The selector is the dense id already (nk = n_states <= 126), 126 is bypass and 127
+// terminate; a selector in [nk, 126) goes to row nk + 3 (a bad record), and a byte past the slice's last bin -- the caller's padding,
+// any value -- to row nk + 1 by its index.  Nothing lands in row nk + 2: no census, no second pass.  A slice whose rec_off is not a
+// multiple of 16 is a bad record as well (its groups are read from the multiple of 16 below it, never from an unaligned address).
+template <class SelT, bool R8>
 __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks, int32_t *status, uint32_t *lbits,
                                                    uint16_t *lend, uint32_t *n_retry) {
     extern __shared__ uint32_t local_lds[];                      // per wave: bits[33][64], then cnt[(nk + 5) / 2][64] (two 16-bit counters each)
-    __shared__ SelT sel_tab[2048];
+    constexpr uint32_t kSelTab = R8 ? 128 : 2048;
+    __shared__ SelT sel_tab[kSelTab];
     const uint32_t nk = p.n_states, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t cnt_rows = (nk + 5) / 2;                      // contexts 0 .. nk-1 and the rows nk .. nk+3
     const uint32_t wave_dwords = (33 + cnt_rows) * 64;
     uint32_t *bits = local_lds + wv * wave_dwords;
     uint32_t *cnt = bits + 33 * 64;
-    for (uint32_t sel = threadIdx.x; sel < 2048; sel += blockDim.x) {
+    for (uint32_t sel = threadIdx.x; sel < kSelTab; sel += blockDim.x) {
         uint32_t k;
-        if (sel < 1024u) {
+        if (R8) k = sel < nk ? sel : sel == AVR_SEL8_TERMINATE ? nk : sel == AVR_SEL8_BYPASS ? nk + 1 : nk + 3;
+        else if (sel < 1024u) {
             const uint32_t d = p.table[sel];
             k = d < nk ? d : sel < p.ns_full ? nk + 2 : nk + 3;
         } else k = sel == AVR_SEL_TERMINATE ? nk : (sel == AVR_SEL_BYPASS || sel == (AVR_NOP_CABAC >> 1)) ? nk + 1 : nk + 3;
@@ -264,6 +293,8 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
     uint32_t i0 = 0, i1 = 0, n = 0, s = 0;
     bool mine = false;                                           // the lane has a chunk of a live slice
     const uint16_t *r = p.recs;
+    const uint8_t *r8 = p.recs8;
+    uint32_t misaligned = 0;
     if (gc < total_chunks) {
         s = p.chunk_slice[gc];
         if (status[s] == AVR_SLICE_OK) {
@@ -272,7 +303,13 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
             i0 = (gc - p.chunk_base[s]) * kChunk;
             i1 = i0 + kChunk < n ? i0 + kChunk : n;
             if (i0 > i1) i0 = i1;
-            r = p.recs + p.rec_off[s];
+            if (R8) {
+                const uint64_t off = p.rec_off[s];
+                misaligned = uint32_t(off & 15u);
+                r8 = p.recs8 + (off & ~uint64_t(15));
+            } else {
+                r = p.recs + p.rec_off[s];
+            }
         }
     }
     uint32_t *my_cnt = cnt + lane;                               // counters of contexts 2j, 2j+1 at my_cnt[64 j]
@@ -282,7 +319,28 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
     // cache line of records per trip with the next one in flight (see for_codes_all).
     auto for_groups = [&](auto &&f) { for_record_groups(r, i0, i1, f); };
     uint32_t high = 0;                                           // OR of all records: bits 12..15 must stay clear
-    for_groups([&](const U4 &v) {                                // pass 1
+    const uint32_t k_pad = nk + 1;                               // R8: the row of a byte past the slice's last bin
+    const uint32_t e_pad = (k_pad >> 1) * 256u | (k_pad & 1u) * 16u;
+    // R8: the sixteen records of a group, their table entries (padding by index when masked) and bins
+    auto group8 = [&](uint32_t base, const U4 &v, auto masked, uint32_t e[16], uint32_t bin[16]) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++) {
+            const uint32_t b = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+            e[j] = sel_tab[b >> 1];
+            if (decltype(masked)::value) e[j] = base + j < i1 ? e[j] : e_pad;
+            bin[j] = b & 1u;
+        }
+    };
+    if (R8) for_record_groups8(r8, i0, i1, [&](uint32_t base, const U4 &v, auto masked) {      // pass 1
+        uint32_t e[16], bin[16];
+        group8(base, v, masked, e, bin);
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++)
+            __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(cnt_b + (e[j] & ~255u)), 1u << (e[j] & 31u), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+    });
+    else for_groups([&](const U4 &v) {                           // pass 1
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         high |= (w[0] | w[1]) | (w[2] | w[3]);
         uint32_t e[8];
@@ -294,7 +352,7 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
     });
     auto count_of = [&](uint32_t k) { return (my_cnt[64 * (k >> 1)] >> (16 * (k & 1u))) & 0xffffu; };
-    const uint32_t n_term = count_of(nk), n_missed = count_of(nk + 2), n_invalid = count_of(nk + 3) | (high & 0xf000f000u);
+    const uint32_t n_term = count_of(nk), n_missed = count_of(nk + 2), n_invalid = count_of(nk + 3) | (high & 0xf000f000u) | misaligned;
     uint32_t term_at = 0;                                        // where the terminate row starts
     {
         uint32_t run = 0;                                        // exclusive prefix over the contexts and the terminate row; the rest starts at 1024
@@ -307,7 +365,22 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
             run += (2 * j <= nk ? c0 : 0u) + (2 * j + 1 <= nk ? c1 : 0u);
         }
     }
-    for_groups([&](const U4 &v) {                                // pass 2
+    if (R8) for_record_groups8(r8, i0, i1, [&](uint32_t base, const U4 &v, auto masked) {      // pass 2
+        uint32_t e[16], bin[16], pos[16];
+        group8(base, v, masked, e, bin);
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++)
+            pos[j] = __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(cnt_b + (e[j] & ~255u)), 1u << (e[j] & 31u), __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++) {
+            const uint32_t at = (pos[j] >> (e[j] & 31u)) & 2047u;
+            const uint32_t row = at >> 5 < 32u ? at >> 5 : 32u;
+            __hip_atomic_fetch_or(reinterpret_cast<uint32_t *>(bits_b + row * 256u), bin[j] << (at & 31u), __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    });
+    else for_groups([&](const U4 &v) {                           // pass 2
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         uint32_t e[8], pos[8];
 #pragma unroll
@@ -333,8 +406,9 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
             ones += __popc(my_bits[64 * (pos >> 5)] & mask);
             pos += take;
         }
-        constexpr uint32_t kTerm1 = (AVR_SEL_TERMINATE << 1) | 1;
-        const bool bad_term = ones > 1u || (ones == 1u && !(i1 == n && r[n - 1] == kTerm1));   // one 1: it is the last bin iff the last bin is one
+        constexpr uint32_t kTerm1 = (AVR_SEL_TERMINATE << 1) | 1, kTerm1_8 = (AVR_SEL8_TERMINATE << 1) | 1;
+        auto last_is_term1 = [&]() { return i1 == n && (R8 ? r8[misaligned + n - 1] == kTerm1_8 : r[n - 1] == kTerm1); };   // (n >= 1 here)
+        const bool bad_term = ones > 1u || (ones == 1u && !last_is_term1());   // one 1: it is the last bin iff the last bin is one
         if (n_invalid || bad_term) status[s] = AVR_SLICE_BAD_RECORD;
         else if (n_missed && atomicCAS(&status[s], AVR_SLICE_OK, AVR_SLICE_RETRY_CENSUS) == AVR_SLICE_OK) atomicAdd(n_retry, 1u);
     }
@@ -392,7 +466,7 @@ __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint3
     const uint32_t nk = p.n_states, pair = wave * 64 + lane;
     const uint32_t s = groups ? wave / groups : pair / nk, k = groups ? (wave - s * groups) + lane * groups : pair - s * nk;
     if ((groups && lane >= chain_lanes) || s >= n_slices || status[s] != AVR_SLICE_OK || k >= nk) return;
-    const uint32_t col = p.index[k], row4 = ((nk + 3) >> 2) << 2;
+    const uint32_t col = p.index ? p.index[k] : k, row4 = ((nk + 3) >> 2) << 2;
     if (col >= p.ns_full) return;                                // a row beyond the batch's contexts (launch sized by a guess)
     uint32_t st = init_states[size_t(s) * p.ns_full + col] & 127u;
     const uint32_t c0 = p.chunk_base[s], nc = (p.n_bins[s] + kChunk - 1) / kChunk;
@@ -553,7 +627,7 @@ __device__ __forceinline__ bool chain_lane(const Plan &p, uint32_t n_slices, uin
     const uint32_t seg = wave % n_segs, pair = (wave / n_segs) * 64 + lane;          // pair = slice * nk + context
     const uint32_t s = pair / nk, k = pair - s * nk;
     if (s >= n_slices || status[s] != AVR_SLICE_OK) return false;
-    const uint32_t col = p.index[k];
+    const uint32_t col = p.index ? p.index[k] : k;
     if (col >= p.ns_full) return false;
     const uint32_t nc = (p.n_bins[s] + kChunk - 1) / kChunk, seg_len = (nc + n_segs - 1) / n_segs;
     const uint32_t c_begin = seg * seg_len < nc ? seg * seg_len : nc, c_end = c_begin + seg_len < nc ? c_begin + seg_len : nc;
@@ -823,21 +897,29 @@ struct B1Walk {
     }
 };
 
-template <bool TILE_CODES>
+// R8: one-byte records (p.recs8; see k_k1p_local): selector = dense id, 126 bypass, 127 terminate, and a byte past the slice's
+// last bin goes to the padding pseudo state by its index -- no code of its own, kCodePad as a two-byte no-op record gets.
+template <bool TILE_CODES, bool R8>
 __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunks, const uint32_t *est, uint8_t *res,
                                                     const int32_t *status, Stretch *stretch, uint32_t max_stretch) {
     extern __shared__ uint32_t replay_lds[];                     // per wave: state dwords [(nk+8)/4][64]
     __shared__ uint4 info[2 * kReplayStates];
     __shared__ uint2 codes2[256];
-    __shared__ uint32_t sel_off[2048];
+    constexpr uint32_t kSelOff = R8 ? 128 : 2048;
+    __shared__ uint32_t sel_off[kSelOff];
     const uint32_t lane = threadIdx.x & 63, nk = p.n_states;
     for (uint32_t c = threadIdx.x; c < 256; c += blockDim.x) codes2[c] = device_codes2(c);
     uint8_t *stb = reinterpret_cast<uint8_t *>(replay_lds) + (threadIdx.x >> 6) * (((nk + 8) >> 2) << 8) + lane * 4;
-    for (uint32_t sel = threadIdx.x; sel < 2048; sel += blockDim.x) {
-        // contexts get their dense id; 1024 (bypass), 1025 (terminate), 1026 (no-op) -> nk+1, nk+2, nk+3; the rest nk / nk+4
-        const uint32_t over = (sel < 1023u ? 1023u : sel > 1027u ? 1027u : sel) - 1023u;
-        const uint32_t dense = sel < 1024u ? uint32_t(p.table[sel]) : kNotUsed;
-        const uint32_t kk = (dense < nk ? dense : nk) + over;
+    for (uint32_t sel = threadIdx.x; sel < kSelOff; sel += blockDim.x) {
+        uint32_t kk;
+        if (R8) {                                                // 126 (bypass), 127 (terminate) -> nk+1, nk+2; [nk, 126) -> nk+4
+            kk = sel < nk ? sel : sel == AVR_SEL8_BYPASS ? nk + 1 : sel == AVR_SEL8_TERMINATE ? nk + 2 : nk + 4;
+        } else {
+            // contexts get their dense id; 1024 (bypass), 1025 (terminate), 1026 (no-op) -> nk+1, nk+2, nk+3; the rest nk / nk+4
+            const uint32_t over = (sel < 1023u ? 1023u : sel > 1027u ? 1027u : sel) - 1023u;
+            const uint32_t dense = sel < 1024u ? uint32_t(p.table[sel]) : kNotUsed;
+            kk = (dense < nk ? dense : nk) + over;
+        }
         sel_off[sel] = ((kk & ~3u) << 6) + (kk & 3u);
     }
     for (uint32_t i = threadIdx.x; i < 2 * kReplayStates; i += blockDim.x) {
@@ -901,6 +983,54 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
         c0 = __builtin_amdgcn_perm(e[1].y, e[0].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[3].y, e[2].y, 0x05010c0cu);
         c1 = __builtin_amdgcn_perm(e[5].y, e[4].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[7].y, e[6].y, 0x05010c0cu);
     };
+    if (R8) {
+        // 8 one-byte records (lo: the first four) -> 8 codes; masked: records at or past `lim` take the padding pseudo state
+        const uint32_t pad_off = (((nk + 3) & ~3u) << 6) + ((nk + 3) & 3u);
+        auto eight8 = [&](uint32_t lo, uint32_t hi, uint32_t base, uint32_t lim, auto masked, uint32_t &c0, uint32_t &c1, uint4 e[8]) {
+            uint32_t off[8], bin[8];
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) {
+                const uint32_t b = ((j < 4 ? lo : hi) >> (8 * (j & 3))) & 0xffu;
+                off[j] = sel_off[b >> 1];
+                if (decltype(masked)::value) off[j] = base + j < lim ? off[j] : pad_off;
+                bin[j] = b & 1u;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < 8; j++) {
+                uint8_t *sp = stb + off[j];
+                const uint32_t st = *sp;
+                e[j] = info[(st << 1) | bin[j]];
+                *sp = uint8_t(e[j].y);
+            }
+            c0 = __builtin_amdgcn_perm(e[1].y, e[0].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[3].y, e[2].y, 0x05010c0cu);
+            c1 = __builtin_amdgcn_perm(e[5].y, e[4].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[7].y, e[6].y, 0x05010c0cu);
+        };
+        // 16 records -> 16 codes, B1 over them, the codes out
+        auto sixteen8 = [&](uint32_t base, const U4 &v, auto masked) {
+            U4 a;
+            uint4 e[8];
+            eight8(v.x, v.y, base, i1, masked, a.x, a.y, e); b1.group(base, e);
+            eight8(v.z, v.w, base + 8, i1, masked, a.z, a.w, e); b1.group(base + 8, e);
+            put16(base, a);
+        };
+        // from the multiple of 16 at or below rec_off, as k_k1p_local reads it: never an unaligned 16-byte load, whatever the order of the
+        // kernels (a slice whose rec_off is not a multiple of 16 has been flagged by k_k1p_local and does not get here)
+        const uint8_t *r8 = p.recs8 + (p.rec_off[s] & ~uint64_t(15));
+        if (i0 < n) {
+            for_record_groups8(r8, i0, i1, sixteen8);
+            b1.chunk_done();
+            // past the chunk: on through the next chunk's bins until the stretch closes (codes not written: not this lane's)
+            for (uint32_t i = i0 + kChunk; b1.mode != 3 && i < n; i += 8) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(r8 + i);
+                uint32_t c0, c1;
+                uint4 e[8];
+                eight8(v.x, v.y, i, n, std::true_type{}, c0, c1, e);
+                b1.tail(i, e);
+            }
+        }
+        stretch[gc] = b1.finish();
+        return;
+    }
     // a slice's records are padded with no-ops to a multiple of 8, its codes to a multiple of 16
     uint32_t i = i0;
     if (i0 < n) {
@@ -1272,9 +1402,12 @@ __global__ __launch_bounds__(256) void k_k1p_d(Plan p, const SliceTotals *tot, c
 // 256-entry LDS table.  Two uses: the slices phase D hands back (want_status = AVR_SLICE_RETRY_SERIAL: the
 // carry pattern of k_k1p_d, or the test switch), and batches of many short slices, where one lane per
 // slice fills the chip and the per-chunk machinery of K1p would be all overhead.
-// Slice i's codes are at codes + res_off[i] (16-byte aligned, readable up to the next multiple of 16).
-__global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_in, const uint64_t *res_off, const uint32_t *n_bins,
-                                                           const uint32_t *order, uint32_t n_slices, uint8_t *out,
+// Slice i's codes are at codes + res_off[i] (16-byte aligned, readable up to the next multiple of 16); TILE: in the kernels' own
+// wave-interleaved buffer instead (TileCodes, slice i from global chunk chunk_base[i] on) -- the hand-over of the one-byte K1p call,
+// which has no two-byte records to hand over (launch_k1p8).
+template <bool TILE>
+__global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_in, const uint64_t *res_off, const uint32_t *chunk_base,
+                                                           const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices, uint8_t *out,
                                                            const uint64_t *out_off, uint32_t *out_len, int32_t *status,
                                                            int32_t want_status) {
     __shared__ CodeEntry codes[256];
@@ -1288,7 +1421,10 @@ __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_
         return;
     }
     const uint32_t n = n_bins[slice];
-    const uint8_t *res = codes_in + res_off[slice];
+    const uint8_t *res = TILE ? codes_in : codes_in + res_off[slice];
+    const TileCodes tiled{codes_in, TILE ? chunk_base[slice] : 0u};
+    auto load16 = [&](uint32_t i) { return TILE ? tiled.load16(i) : *reinterpret_cast<const U4 *>(res + i); };
+    auto byte = [&](uint32_t i) { return TILE ? tiled.byte(i) : uint32_t(res[i]); };
     const uint64_t o0 = out_off[slice];
     const uint32_t cap = uint32_t(out_off[slice + 1] - o0);
     CabacEncoder e;
@@ -1307,9 +1443,9 @@ __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_
     };
     uint32_t i = 0;
     if (n >= 16) {
-        U4 v = *reinterpret_cast<const U4 *>(res);
+        U4 v = load16(0);
         for (; i + 16 <= n; i += 16) {                           // the next group is in flight while this one is coded
-            const U4 nx = i + 32 <= n ? *reinterpret_cast<const U4 *>(res + i + 16) : v;
+            const U4 nx = i + 32 <= n ? load16(i + 16) : v;
             uint32_t w0 = v.x, w1 = v.y, w2 = v.z, w3 = v.w;
 #pragma unroll 1
             for (uint32_t k = 0; k < 4; k++) {
@@ -1320,7 +1456,7 @@ __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_
             v = nx;
         }
     }
-    for (; i < n; i++) bin(res[i]);
+    for (; i < n; i++) bin(byte(i));
     e.finish();                                                  // cabac_code.h:63-65 / ~encoder(), arithmetic_code.h:100
     e.w.flush();
     out_len[slice] = e.w.n;
@@ -1381,7 +1517,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
                                  const avr_chunk_plan *pl, uint8_t *w, uint8_t *res, int32_t *status, uint8_t *final_states,
                                  uint32_t max_stretch, const Stretch **stretch_out, const DenseHint *hint = nullptr,
                                  uint32_t stride = 1, bool second_pass = false, uint32_t *retry_count = nullptr,
-                                 bool tile_codes = false) {
+                                 bool tile_codes = false, bool r8 = false) {
     const uint32_t ns = p.ns_full;
     const ResolveLayout L = resolve_layout(n_slices, ns, pl);
     uint32_t *lbits = reinterpret_cast<uint32_t *>(w + L.lbits);
@@ -1400,17 +1536,25 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
     if (final_states && ns && !second_pass &&
         (e = hipMemcpyAsync(final_states, init_states, size_t(n_slices) * ns, hipMemcpyDeviceToDevice, s)) != hipSuccess)
         return e;                                                // contexts without bins keep their state
-    hipLaunchKernelGGL(k_k1p_census, dim3((pl->total_blocks + kCensusBlocks - 1) / kCensusBlocks), dim3(256), 0, s, p, pl->total_blocks, status, used, stride);
-    hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
-    if ((e = tn_table(s, &tn)) != hipSuccess) return e;
     uint32_t n_states = 0;
-    if (hint && hint->rows) {                                    // sized by the caller's guess, checked by the caller afterwards (DenseHint)
-        n_states = hint->rows < ns ? hint->rows : ns;
-        if (hint->host_count && (e = hipMemcpyAsync(hint->host_count, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if (r8) {
+        // one-byte records: the selectors are dense ids below ns already -- no census, no renumbering, nothing to read back
+        n_states = ns;
+        p.table = nullptr;
+        p.index = nullptr;
+        if ((e = tn_table(s, &tn)) != hipSuccess) return e;
     } else {
-        if ((e = hipMemcpyAsync(&n_states, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        if (hint && hint->host_count) *hint->host_count = n_states;
+        hipLaunchKernelGGL(k_k1p_census, dim3((pl->total_blocks + kCensusBlocks - 1) / kCensusBlocks), dim3(256), 0, s, p, pl->total_blocks, status, used, stride);
+        hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
+        if ((e = tn_table(s, &tn)) != hipSuccess) return e;
+        if (hint && hint->rows) {                                    // sized by the caller's guess, checked by the caller afterwards (DenseHint)
+            n_states = hint->rows < ns ? hint->rows : ns;
+            if (hint->host_count && (e = hipMemcpyAsync(hint->host_count, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        } else {
+            if ((e = hipMemcpyAsync(&n_states, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+            if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+            if (hint && hint->host_count) *hint->host_count = n_states;
+        }
     }
     p.n_states = n_states;
     {
@@ -1419,8 +1563,8 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         // what there is to win), as workgroups of w waves: the w with the most waves resident, the smaller workgroup on a tie
         const uint32_t per_wave = (33 + (n_states + 5) / 2) * 64 * 4;
         const bool narrow = n_states <= 500;                     // (rows up to (n_states + 3) / 2 = 251: offsets below 2^16)
-        const uint32_t kLdsPerCu = 160 * 1024, kStatic = narrow ? 2048 * 2 : 2048 * 4;
-        auto local = narrow ? k_k1p_local<uint16_t> : k_k1p_local<uint32_t>;
+        const uint32_t kLdsPerCu = 160 * 1024, kStatic = r8 ? 128 * 2 : narrow ? 2048 * 2 : 2048 * 4;
+        auto local = r8 ? k_k1p_local<uint16_t, true> : narrow ? k_k1p_local<uint16_t, false> : k_k1p_local<uint32_t, false>;
         uint32_t waves = 1, best = 0;
         for (uint32_t w = 1; w <= 8; w++) {
             const uint32_t need = w * per_wave + kStatic;
@@ -1493,7 +1637,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
     const uint32_t per_wave = ((n_states + 8) / 4) * 256;
     const uint32_t replay_waves = per_wave * 4 <= 48 * 1024 ? 4 : per_wave * 2 <= 48 * 1024 ? 2 : 1;
     const uint32_t replay_lds = replay_waves * per_wave;
-    auto replay = tile_codes ? k_k1p_replay<true> : k_k1p_replay<false>;
+    auto replay = r8 ? k_k1p_replay<true, true> : tile_codes ? k_k1p_replay<true, false> : k_k1p_replay<false, false>;   // (r8: tile codes only)
     if (replay_lds > 48 * 1024) {
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(replay), hipFuncAttributeMaxDynamicSharedMemorySize, int(replay_lds));
         if (e != hipSuccess) return e;
@@ -1538,8 +1682,8 @@ hipError_t launch_cabac_encode_codes(hipStream_t s, const uint8_t *codes, const 
                                      const uint32_t *order, uint32_t n_slices, uint8_t *out, const uint64_t *out_off,
                                      uint32_t *out_len, int32_t *status, int32_t want_status) {
     if (n_slices == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cabac_encode_codes, dim3((n_slices + 63) / 64), dim3(64), 0, s, codes, res_off, n_bins, order, n_slices,
-                       out, out_off, out_len, status, want_status);
+    hipLaunchKernelGGL(k_cabac_encode_codes<false>, dim3((n_slices + 63) / 64), dim3(64), 0, s, codes, res_off, nullptr, n_bins, order,
+                       n_slices, out, out_off, out_len, status, want_status);
     return hipGetLastError();
 }
 
@@ -1644,6 +1788,31 @@ hipError_t launch_k1p_resolve(hipStream_t s, const uint16_t *recs, const uint64_
     if (e != hipSuccess || !retry) return e;
     return k1p_second_pass(s, p, n_slices, init_states, n_states, pl, w, codes, nullptr, nullptr, nullptr, status, final_states, false);
 }
+// The one-byte form (AVR_KIND_CABAC8, avr_cabac8_encode_chunked_device): the same phases on p.recs8, without the census, the
+// renumbering, the second pass and the host round trip (the selectors are dense ids below n_states <= AVR_MAX_STATES8 already):
+// everything is enqueued, nothing waits.  The slices phase D hands over are coded by the serial coder from the resolved codes this
+// call made (k_cabac_encode_codes on the wave-interleaved buffer): same bytes as from the records, and no two-byte copy of them.
+hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                       uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
+                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
+                       uint8_t *final_states) {
+    if (n_slices == 0) return hipSuccess;
+    uint8_t *w = static_cast<uint8_t *>(workspace);
+    uint8_t *res = w;                                        w += up256(codes_bytes(pl));
+    const Plan p{nullptr, rec_off, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
+                 pl->dig_off, n_states, n_states, nullptr, nullptr, recs8};
+    const Stretch *st = nullptr;
+    hipError_t e = launch_resolve(s, p, n_slices, init_states, pl, w, res, status, final_states, kMaxStretch, &st, nullptr, 1, false,
+                                  nullptr, true, true);
+    if (e != hipSuccess) return e;
+    w += resolve_ws_bytes(n_slices, n_states, pl);
+    e = launch_code(s, p, n_slices, pl, w, res, kMaxStretch, out, out_off, out_len, status, st, true);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((n_slices + 63) / 64), dim3(64), 0, s, res, nullptr, pl->chunk_base, n_bins,
+                       nullptr, n_slices, out, out_off, out_len, status, int32_t(AVR_SLICE_RETRY_SERIAL));
+    return hipGetLastError();
+}
+
 // ... and phases B-D from resolved codes (no stretch is declined for its length here: a stretch without an
 // LPS is simply walked to its end by one lane); a slice phase D hands back is coded by k_cabac_encode_codes
 size_t k1p_code_workspace_bytes(size_t n_slices, const avr_chunk_plan *pl) {

@@ -716,6 +716,48 @@ __global__ __launch_bounds__(64) void k_pack_tiles(
     if (active && bad) status[slice] = AVR_SLICE_BAD_RECORD;
 }
 
+// The same from ONE-BYTE K1 records (AVR_KIND_CABAC8: bin | dense selector << 1, include/avrecode_ms_amd.h): widened, validated and
+// transposed in one pass, into the two-byte tiles above -- selector 126 -> 1024 (bypass), 127 -> 1025 (terminate), a selector below
+// n_states (<= AVR_MAX_STATES8) as it is, any other -> 1027 with AVR_SLICE_BAD_RECORD, records past n_bins -> no-ops (whatever the
+// caller's padding bytes hold).  Slice i's bytes are at recs8 + rec_off[i], a multiple of 16 (another value: AVR_SLICE_BAD_RECORD; the
+// slice is read from the multiple of 16 below it).  Eight bytes a lane a chunk in, sixteen out.
+__global__ __launch_bounds__(64) void k_pack_tiles8(
+    uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+    const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, uint4 *tiles, int32_t *status) {
+    const uint32_t lane = threadIdx.x, t = blockIdx.x;
+    const uint32_t g = t * 64 + lane;
+    const bool active = g < n_slices;
+    const uint32_t slice = active ? (order ? order[g] : g) : 0;
+    const uint32_t nb = active ? n_bins[slice] : 0;
+    const uint32_t my_chunks = (nb + 7) >> 3;
+    const uint32_t tile_chunks = uint32_t((tile_off[t + 1] - tile_off[t]) >> 6);
+    const uint64_t off = active ? rec_off[slice] : 0;
+    const uint2 *src = reinterpret_cast<const uint2 *>(recs8 + (off & ~uint64_t(15)));
+    uint4 *dst = tiles + tile_off[t] + lane;
+    constexpr uint32_t nop2 = AVR_NOP_CABAC | (AVR_NOP_CABAC << 16);
+    bool bad = (off & 15) != 0;
+    for (uint32_t c = 0; c < tile_chunks; c++) {
+        uint4 v = make_uint4(nop2, nop2, nop2, nop2);
+        if (c < my_chunks) {
+            const uint2 b8 = src[c];
+            const uint32_t valid = nb - c * 8;                   // records valid in this chunk (>= 1)
+            uint32_t o[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k++) {
+                const uint32_t b = ((k < 4 ? b8.x : b8.y) >> (8 * (k & 3))) & 0xffu, sel8 = b >> 1;
+                const uint32_t sel = sel8 == AVR_SEL8_BYPASS ? AVR_SEL_BYPASS : sel8 == AVR_SEL8_TERMINATE ? AVR_SEL_TERMINATE
+                                   : sel8 < n_states ? sel8 : 1027u;
+                bad |= k < valid && sel == 1027u;
+                const uint32_t r = k < valid ? (sel << 1) | (b & 1u) : uint32_t(AVR_NOP_CABAC);
+                if (k & 1) o[k >> 1] |= r << 16; else o[k >> 1] = r;
+            }
+            v = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+        dst[size_t(c) * 64] = v;
+    }
+    if (active && bad) status[slice] = AVR_SLICE_BAD_RECORD;
+}
+
 // ------------------------------------------------------------------ dense context ids
 
 // A slice's contexts are identified by their offset in libavcodec's cabac_state[1024]
@@ -868,32 +910,6 @@ __global__ __launch_bounds__(64) void k_synth_slices(
     rs.flush(chunks);
 }
 
-// One-byte K1 records (AVR_KIND_CABAC8: bin | dense selector << 1; include/avrecode_ms_amd.h) widened into the two-byte records every K1
-// kernel reads -- what the batch API does with a batch that came over PCIe in half the bytes.  One thread per 8 records: 8 bytes in,
-// 16 out, both coalesced; a slice's records past its n_bins (the staging buffer pads every slice to 8) become no-ops.  Slice i's bytes
-// are at byte rec_off[i] of `in`, its records at record rec_off[i] of `out`: the same offsets, a multiple of 8 each.
-__global__ __launch_bounds__(256) void k_expand_records8(const uint8_t *in, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                                                         uint32_t n_states, uint64_t total, uint16_t *out) {
-    const uint64_t g = (uint64_t(blockIdx.x) * 256 + threadIdx.x) * 8;           // first of this thread's eight records
-    if (g >= total) return;
-    uint32_t lo = 0, hi = n_slices;                              // the slice g lies in: the last i with rec_off[i] <= g
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (rec_off[mid] <= g) lo = mid; else hi = mid; }
-    const uint64_t first = g - rec_off[lo];
-    const uint32_t n = n_bins[lo];
-    const uint2 v = *reinterpret_cast<const uint2 *>(in + g);
-    const uint32_t w[2] = {v.x, v.y};
-    uint32_t o[4];
-#pragma unroll
-    for (uint32_t j = 0; j < 8; j++) {
-        const uint32_t b = (w[j >> 2] >> (8 * (j & 3))) & 0xffu, sel8 = b >> 1;
-        uint32_t sel = sel8 == AVR_SEL8_BYPASS ? AVR_SEL_BYPASS : sel8 == AVR_SEL8_TERMINATE ? AVR_SEL_TERMINATE : sel8 < n_states ? sel8 : 1027u;
-        uint32_t rec = (sel << 1) | (b & 1u);
-        if (first + j >= n) rec = AVR_NOP_CABAC;
-        if (j & 1) o[j >> 1] |= rec << 16; else o[j >> 1] = rec;
-    }
-    *reinterpret_cast<uint4 *>(out + g) = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 // ------------------------------------------------------------------ launchers
 
 // The renumbering's scratch (4.25 KiB: used[32] + n_dense | table[1024] | index[1024]): one per (device, stream), made on
@@ -1027,6 +1043,15 @@ hipError_t launch_pack_tiles(hipStream_t s, int kind, uint32_t n_states, const u
     return hipGetLastError();
 }
 
+hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                              const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status) {
+    if (n_slices == 0) return hipSuccess;
+    const dim3 grid((n_slices + 63) / 64), block(64);
+    hipLaunchKernelGGL(k_pack_tiles8, grid, block, 0, s, n_states, recs8, rec_off, n_bins, order, n_slices, tile_off,
+                       reinterpret_cast<uint4 *>(tiles), status);
+    return hipGetLastError();
+}
+
 hipError_t launch_context_census(hipStream_t s, const uint16_t *recs, uint64_t n, uint32_t *bitmap) {
     if (n == 0) return hipSuccess;
     const uint64_t want = (n / 8 + 255) / 256;
@@ -1083,14 +1108,6 @@ hipError_t launch_synth_tiles(hipStream_t s, int workload, uint32_t scale, uint6
     hipLaunchKernelGGL(k_synth_tiles, dim3((n_slices + 63) / 64), dim3(64), 0, s, workload, scale, seed,
                        first_slice, kind, n_slices, order, tile_off, reinterpret_cast<uint4 *>(tiles),
                        init_states, n_states);
-    return hipGetLastError();
-}
-
-hipError_t launch_expand_records8(hipStream_t s, const uint8_t *in, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                                  uint32_t n_states, uint64_t total, uint16_t *out) {
-    if (n_slices == 0 || total == 0) return hipSuccess;
-    const uint64_t threads = total / 8;
-    hipLaunchKernelGGL(k_expand_records8, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, s, in, rec_off, n_bins, n_slices, n_states, total, out);
     return hipGetLastError();
 }
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 
-from . import KIND_CABAC, KIND_RANGE, NOP_CABAC, NOP_RANGE, AvrError, SynthConfig, _check, lib
+from . import KIND_CABAC, KIND_CABAC8, KIND_RANGE, MAX_STATES8, NOP_CABAC, NOP_RANGE, AvrError, SynthConfig, _check, lib
 
 
 def synth_config(workload: int, scale_permille: int = 1000, first_slice: int = 0) -> SynthConfig:
@@ -57,7 +57,11 @@ def encode_tiles(kind, tiles, tile_off, n_bins, order, out, out_off, out_len, st
 
 
 class DeviceWorkload:
-    """A batch of slices resident in HBM in the wave-interleaved tile layout."""
+    """A batch of slices resident in HBM in the wave-interleaved tile layout.
+
+    KIND_CABAC8: K1 from one-byte records (bin | dense selector << 1).  Such a workload keeps the records slice-major, one byte
+    each (rec8_flat, rec8_off: byte offsets, multiples of 16), for encode_chunked(), and the two-byte tiles avr_pack_tiles8_device
+    makes of them for encode()."""
 
     def __init__(self, kind, device_index, n_bins, order, tile_off, tiles, init_states, n_states):
         import torch
@@ -73,7 +77,7 @@ class DeviceWorkload:
         self.out_len = torch.zeros(self.n_slices, dtype=torch.int32, device=dev)
         self.status = torch.zeros(self.n_slices, dtype=torch.int32, device=dev)
         self.final_states = (torch.empty(self.n_slices * max(n_states, 1), dtype=torch.uint8, device=dev)
-                             if kind == KIND_CABAC else None)
+                             if kind in (KIND_CABAC, KIND_CABAC8) else None)
         self.total_bins = int(n_bins.to(torch.int64).sum().item())
         # K1 sized by the context count of the previous run of this object (avr_cabac_encode_*_device_hinted): no host round trip
         # in the call; settle() looks at what the device reported once the caller has synchronised
@@ -104,10 +108,14 @@ class DeviceWorkload:
         return w
 
     @classmethod
-    def from_host(cls, kind, recs_list, init_states_list=None, device_index=0):
-        """Upload per-slice uint16 record arrays and pack them into tiles on the device."""
+    def from_host(cls, kind, recs_list, init_states_list=None, device_index=0, pad_bytes=None):
+        """Upload per-slice uint16 record arrays and pack them into tiles on the device.  KIND_CABAC8: uint8 records, slice-major
+        at multiples of 16 bytes; the bytes between a slice's last record and the next slice are taken from pad_bytes (a uint8
+        array, repeated over the whole buffer; default zeros) -- the kernels must not code them, whatever they hold."""
         import numpy as np
         import torch
+        if kind == KIND_CABAC8:
+            return cls._from_host8(recs_list, init_states_list, device_index, pad_bytes)
         L = lib()
         dev = torch.device("cuda", device_index)
         n = len(recs_list)
@@ -139,6 +147,76 @@ class DeviceWorkload:
         w.status.copy_(pack_status)
         return w
 
+    @classmethod
+    def _from_host8(cls, recs_list, init_states_list, device_index, pad_bytes):
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", device_index)
+        n = len(recs_list)
+        nb = np.array([len(r) for r in recs_list], dtype=np.int32)
+        rec_off = np.zeros(n + 1, dtype=np.int64)
+        rec_off[1:] = np.cumsum((nb.astype(np.int64) + 15) // 16 * 16)
+        size = int(rec_off[-1]) + 16
+        flat = np.zeros(size, np.uint8) if pad_bytes is None else np.resize(np.asarray(pad_bytes, dtype=np.uint8), size)
+        for i, r in enumerate(recs_list):
+            flat[rec_off[i]:rec_off[i] + len(r)] = np.asarray(r, dtype=np.uint8)
+        n_states = len(init_states_list[0]) if init_states_list else 0
+        with torch.cuda.device(dev):
+            init = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.uint8) for s in init_states_list])
+                                    if n_states else np.zeros(1, np.uint8)).to(dev)
+            w = cls._pack8(device_index, torch.from_numpy(flat).to(dev), torch.from_numpy(rec_off).to(dev),
+                           torch.from_numpy(nb).to(dev), init, n_states)
+            torch.cuda.synchronize(dev)
+        return w
+
+    @classmethod
+    def _pack8(cls, device_index, rec8_flat, rec8_off, n_bins, init_states, n_states):
+        """A KIND_CABAC8 workload from one-byte slice-major records on the device: tiles by avr_pack_tiles8_device."""
+        import torch
+        if n_states > MAX_STATES8:
+            raise AvrError(f"n_states {n_states} > {MAX_STATES8}: one-byte records name at most {MAX_STATES8} contexts")
+        dev = n_bins.device
+        n = n_bins.numel()
+        order, tile_off = plan_tiles(n_bins)
+        tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
+        pack_status = torch.zeros(n, dtype=torch.int32, device=dev)
+        _check(lib().avr_pack_tiles8_device(device_index, _stream_ptr(torch), n_states, rec8_flat.data_ptr(), rec8_off.data_ptr(),
+                                            n_bins.data_ptr(), order.data_ptr(), n, tile_off.data_ptr(), tiles.data_ptr(),
+                                            pack_status.data_ptr()))
+        w = cls(KIND_CABAC8, device_index, n_bins, order, tile_off, tiles, init_states, n_states)
+        w.rec8_flat, w.rec8_off = rec8_flat, rec8_off
+        w.status.copy_(pack_status)
+        return w
+
+    def to_cabac8(self):
+        """This K1 workload as one-byte records (a new KIND_CABAC8 workload on the same device): selector s < n_states stays s,
+        bypass becomes SEL8_BYPASS, terminate SEL8_TERMINATE.  Needs n_states <= MAX_STATES8 -- after densify() for a stream that
+        numbers its contexts sparsely.  The padding bytes are whatever the two-byte layout had there, narrowed (no-op records
+        become a context's byte): never coded."""
+        import torch
+        if self.kind != KIND_CABAC or self.n_states > MAX_STATES8:
+            raise AvrError(f"to_cabac8 needs a KIND_CABAC workload with n_states <= {MAX_STATES8} (densify() first)")
+        recs, rec_off = self._slice_major()
+        dev = self.n_bins.device
+        with torch.cuda.device(dev):
+            nb = self.n_bins.to(torch.int64)
+            pad16 = (nb + 15) // 16 * 16
+            off8 = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(pad16, 0)])
+            total = int(off8[-1])
+            slice_of = torch.repeat_interleave(torch.arange(self.n_slices, device=dev), pad16)
+            src = torch.arange(total, device=dev) - off8[:-1][slice_of] + rec_off[:-1][slice_of]   # (< rec_off[-1] + 8: in the copy)
+            del slice_of
+            r = recs[src].to(torch.int32) & 0xffff
+            del src
+            sel = r >> 1
+            sel8 = torch.where(sel == 1024, 126, torch.where(sel == 1025, 127, sel))
+            flat8 = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
+            flat8[:total] = (((sel8 << 1) | (r & 1)) & 0xff).to(torch.uint8)
+            del r, sel, sel8
+            w = DeviceWorkload._pack8(self.device_index, flat8, off8, self.n_bins, self.init_states, self.n_states)
+            torch.cuda.synchronize(dev)
+        return w
+
     def encode(self):
         """One pass of the hot path over the batch (enqueued on torch's current stream).  K1: sized by the context count the previous
         run of this object reported (none yet: the call asks the device and waits); exact whatever the guess.  settle() after a
@@ -152,7 +230,8 @@ class DeviceWorkload:
                 self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
                 self.final_states.data_ptr() if self.final_states is not None else None, self.rows_hint, self._counts.data_ptr()))
             return
-        encode_tiles(self.kind, self.tiles, self.tile_off, self.n_bins, self.order, self.out, self.out_off,
+        kind = KIND_CABAC if self.kind == KIND_CABAC8 else self.kind      # (KIND_CABAC8: two-byte tiles, made by avr_pack_tiles8_device)
+        encode_tiles(kind, self.tiles, self.tile_off, self.n_bins, self.order, self.out, self.out_off,
                      self.out_len, self.status, self.init_states, self.n_states, self.final_states, self.device_index)
 
     def _part_array(self, rows_hint):
@@ -277,6 +356,8 @@ class DeviceWorkload:
     def _slice_major(self):
         """Slice-major records on the device (what the intra-slice parallel path reads)."""
         import torch
+        if self.kind == KIND_CABAC8:
+            return self.rec8_flat, self.rec8_off
         if getattr(self, "rec_flat", None) is None:
             dev = self.n_bins.device
             nb = self.n_bins.to(torch.int64)
@@ -373,8 +454,9 @@ class DeviceWorkload:
                              t["blk_base"].data_ptr(), t["blk_slice"].data_ptr(), t["dig_off"].data_ptr(),
                              int(res_off[-1]), int(dig_off[-1]), int(chunk_base[-1]), int(blk_base[-1]))
             self._plan = dict(tensors=t, plan=plan)
-            if self.kind == KIND_CABAC:                     # (K2 sizes its own workspace, see encode_chunked)
-                ws_bytes = lib().avr_cabac_chunked_workspace_bytes(self.n_slices, self.n_states, ctypes.byref(plan))
+            if self.kind in (KIND_CABAC, KIND_CABAC8):      # (K2 sizes its own workspace, see encode_chunked)
+                ws_of = lib().avr_cabac8_chunked_workspace_bytes if self.kind == KIND_CABAC8 else lib().avr_cabac_chunked_workspace_bytes
+                ws_bytes = ws_of(self.n_slices, self.n_states, ctypes.byref(plan))
                 self._plan.update(ws_bytes=ws_bytes, ws=torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev))
         return self._plan
 
@@ -383,6 +465,13 @@ class DeviceWorkload:
         import torch
         recs, rec_off = self._slice_major()
         p = self._chunk_plan()
+        if self.kind == KIND_CABAC8:                         # one-byte records: nothing to guess, nothing waits
+            _check(lib().avr_cabac8_encode_chunked_device(
+                self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(),
+                self.n_slices, self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), (p["ws"].data_ptr() + 255) // 256 * 256,
+                p["ws_bytes"], self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
+                self.final_states.data_ptr()))
+            return
         if self.kind != KIND_CABAC:
             L = lib()
             out_total = int(self.out_off[-1].item()) if "out_total" not in p else p["out_total"]

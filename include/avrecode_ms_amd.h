@@ -138,9 +138,11 @@ int avr_batch_add_slice_range(avr_batch *b, const uint16_t *recs, size_t n);
 int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n);
 /* K1 from ONE-BYTE records (AVR_KIND_CABAC8, above): the same slice as avr_batch_add_slice_cabac would take, in half the bytes
  * over PCIe -- which is what bounds the batch API end to end (2 B per bin against 0.1 B of output).  init_states: n_states <=
- * AVR_MAX_STATES8 bytes, indexed by the dense selector.  On the device the records are widened into the two-byte form
- * (k_expand_records8) and take the path of avr_batch_add_slice_cabac from there: same kernels, same bytes, same statuses -- a
- * selector >= n_states that is neither bypass nor terminate comes back as AVR_SLICE_BAD_RECORD. */
+ * AVR_MAX_STATES8 bytes, indexed by the dense selector.  The device reads the one-byte records as they came, with no two-byte copy:
+ * a batch of many short slices through avr_pack_tiles8_device's packer (widened, validated and transposed in one pass) and the
+ * one-lane-per-slice kernel, a batch of few long ones through avr_cabac8_encode_chunked_device (no census, no host round trip).
+ * Same bytes, final states and statuses as avr_batch_add_slice_cabac -- a selector >= n_states that is neither bypass nor
+ * terminate comes back as AVR_SLICE_BAD_RECORD. */
 int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n,
                                const uint8_t *init_states, size_t n_states);
 /* Zero-copy form of the four calls above: room for a slice of n elements (uint16_t records for AVR_KIND_CABAC /
@@ -168,7 +170,8 @@ int avr_batch_get(avr_batch *b, size_t slice, const uint8_t **bytes, size_t *len
 int avr_batch_get_states(avr_batch *b, size_t slice, const uint8_t **states, size_t *n_states);
 /* How the last run went: [0] 1 = intra-slice parallel kernels, 0 = one lane per slice; [1] context rows the kernels
  * were sized by from the previous run's count (0: the run asked the device and waited); [2] contexts the batch uses
- * (as the sampled census saw them); [3] bit 0 = avr_batch_wait found the guess too small and ran the batch
+ * (as the sampled census saw them) -- except for a one-byte (AVR_KIND_CABAC8) batch on the intra-slice parallel kernels, which
+ * take no census: there it is the batch's declared n_states, every one of which has a row; [3] bit 0 = avr_batch_wait found the guess too small and ran the batch
  * again, bit 1 = it ran the second pass of the intra-slice parallel path (slices with a bin in a context the sampled
  * census missed).  CABAC-record batches; zeros otherwise. */
 int avr_batch_run_info(avr_batch *b, uint32_t info[4]);
@@ -188,6 +191,8 @@ void       avr_multi_destroy(avr_multi *m);
 int avr_multi_add_slice_cabac(avr_multi *m, const uint16_t *recs, size_t n, const uint8_t *init_states, size_t n_states);
 int avr_multi_add_slice_range(avr_multi *m, const uint16_t *recs, size_t n);
 int avr_multi_add_slice_codes(avr_multi *m, const uint8_t *codes, size_t n);
+/* one-byte records, as avr_batch_add_slice_cabac8 (n_states <= AVR_MAX_STATES8) */
+int avr_multi_add_slice_cabac8(avr_multi *m, const uint8_t *recs8, size_t n, const uint8_t *init_states, size_t n_states);
 int avr_multi_run(avr_multi *m);
 int avr_multi_get(avr_multi *m, size_t slice, const uint8_t **bytes, size_t *len, int *status);
 /* which entry of `devices` coded the slice, and the bins each entry was given (n_devices values): for tests and reports */
@@ -233,6 +238,18 @@ int avr_pack_tiles_device(int device, void *stream, int kind, size_t n_states,
  * with out_len 0; otherwise the kernel writes AVR_SLICE_*.  Records are trusted to be valid
  * (packer / generator output); a selector that is not a context of the slice, bypass or
  * terminate is treated as a no-op. */
+/* The packer for ONE-BYTE records (AVR_KIND_CABAC8): slice i's records are recs8[rec_off[i] .. rec_off[i] + n_bins[i]), rec_off in
+ * BYTES, each a multiple of 16, and readable up to the next multiple of 16 (what lies past n_bins is never coded, whatever it holds).
+ * Writes the two-byte tile layout above -- what avr_cabac_encode_tiles_device and its hinted form read -- with the same checks:
+ * a selector that is neither < n_states (<= AVR_MAX_STATES8) nor AVR_SEL8_BYPASS / AVR_SEL8_TERMINATE, or a rec_off value that
+ * is not a multiple of 16, sets status[slice] = AVR_SLICE_BAD_RECORD.  status must be zero-filled before.  Refused before anything
+ * touches a device (AVR_ERR_INVALID): n_states > AVR_MAX_STATES8, a null pointer with n_slices > 0, recs8 not 16-byte aligned,
+ * rec_off not 8-byte aligned. */
+int avr_pack_tiles8_device(int device, void *stream, size_t n_states,
+                           const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                           const uint32_t *order, size_t n_slices,
+                           const uint64_t *tile_off, void *tiles, int32_t *status);
+
 int avr_cabac_encode_tiles_device(int device, void *stream,
                                   const void *tiles, const uint64_t *tile_off,
                                   const uint32_t *n_bins, const uint32_t *order, size_t n_slices,
@@ -289,6 +306,24 @@ int avr_cabac_encode_chunked_device(int device, void *stream,
                                     const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
                                     uint8_t *out, const uint64_t *out_off,
                                     uint32_t *out_len, int32_t *status, uint8_t *final_states);
+
+/* K1p from ONE-BYTE records (AVR_KIND_CABAC8; layout as for avr_pack_tiles8_device: rec_off in bytes, multiples of 16, the bytes
+ * past n_bins in a slice's last 16 are padding of any value).  The same bytes, final states and statuses as
+ * avr_cabac_encode_chunked_device on the same slices as two-byte records, the same plan (blk_base / blk_slice are not read: there is
+ * no census), workspace avr_cabac8_chunked_workspace_bytes(...).  The selectors are dense ids below n_states <= AVR_MAX_STATES8
+ * already, so the call has nothing to count or renumber: it NEVER BLOCKS THE CALLING THREAD -- every kernel is enqueued on `stream`
+ * and the call returns, with no read-back of a context count, no guess to check afterwards and no second pass (what the two-byte
+ * call and its hinted form need).  Validation is as strict as the two-byte call's: a selector in [n_states, 126), a
+ * put_terminate(1) that is not the slice's last bin, or a rec_off value that is not a multiple of 16 sets AVR_SLICE_BAD_RECORD for
+ * that slice alone.  Refused before anything touches a device: as avr_pack_tiles8_device, and a workspace too small (AVR_ERR_CAPACITY). */
+size_t avr_cabac8_chunked_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan);
+int avr_cabac8_encode_chunked_device(int device, void *stream,
+                                     const uint8_t *recs8, const uint64_t *rec_off,
+                                     const uint32_t *n_bins, size_t n_slices,
+                                     const uint8_t *init_states, size_t n_states,
+                                     const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
+                                     uint8_t *out, const uint64_t *out_off,
+                                     uint32_t *out_len, int32_t *status, uint8_t *final_states);
 
 /* The K1 device calls SIZED BY THE CALLER'S GUESS of how many contexts the batch uses (r4) -- the count an earlier call reported,
  * which is how avr_batch runs from its second batch on -- so that the call enqueues everything and returns: the calls above read
