@@ -192,7 +192,9 @@ __global__ __launch_bounds__(256) void k_k1p_tn(uint8_t *tn) {
 }
 
 // A lane's walk over the 16-byte record groups [i0, i1) of its chunk (8 records a group; a slice's records are padded with no-ops to
-// a whole group): a cache line of 64 bytes a trip, the next trip's line in flight meanwhile.  The loads of the next line are
+// a whole group): a cache line of 64 bytes a trip, the next trip's line in flight meanwhile.  f(first index of the group, group,
+// masked), masked as in for_record_groups8 below: std::true_type for the groups after the last whole line, the only ones that can
+// reach past i1.  The loads of the next line are
 // UNCONDITIONAL -- past the chunk's last whole line the address is clamped to that line (a hit) instead of the load being skipped: hipcc
 // puts a load inside a branch behind an exec mask and waits for it (s_waitcnt vmcnt) before the branch's end, which turned "the next
 // line in flight" into "every trip waits out a memory latency" in rounds 1-3 (tools/ubench/read_patterns: 1.4 against 4.3 TB/s for
@@ -207,11 +209,11 @@ __device__ __forceinline__ void for_record_groups(const uint16_t *r, uint32_t i0
         for (; i + 32 <= i1; i += 32) {
             const U4 *qn = reinterpret_cast<const U4 *>(r + (i + 32 <= last ? i + 32 : last));
             const U4 n0 = qn[0], n1 = qn[1], n2 = qn[2], n3 = qn[3];
-            f(v0); f(v1); f(v2); f(v3);
+            f(i, v0, std::false_type{}); f(i + 8, v1, std::false_type{}); f(i + 16, v2, std::false_type{}); f(i + 24, v3, std::false_type{});
             v0 = n0; v1 = n1; v2 = n2; v3 = n3;
         }
     }
-    for (; i < i1; i += 8) f(*reinterpret_cast<const U4 *>(r + i));
+    for (; i < i1; i += 8) f(i, *reinterpret_cast<const U4 *>(r + i), std::true_type{});
 }
 
 // The same walk over one-byte records (AVR_KIND_CABAC8): 16 records a group, 64 a line.  One-byte records have no no-op value --
@@ -252,8 +254,9 @@ __device__ __forceinline__ void for_record_groups8(const uint8_t *r, uint32_t i0
 // Row j of `cnt` and row j of `bits` are 64 lanes wide: the data-dependent accesses never conflict across
 // lanes.  What a record's 11-bit selector means is one look-up: sel_tab[selector] = byte offset of the
 // counter row | 16 for the high half.  Rows past the contexts: nk = terminate bins (sorted like a context: their
-// values end up side by side behind the last context's), nk + 1 = bypass and padding, nk + 2 = a context of the
-// slice that has no dense id (the sampled census missed it), nk + 3 = no selector of the slice at all.  The last
+// values end up side by side behind the last context's), nk + 1 = bypass and padding (a record past the slice's last bin, by its
+// index), nk + 2 = a context of the slice that has no dense id (the sampled census missed it), nk + 3 = no selector of the slice at
+// all -- the no-op selector 1026 included, which only the padding may hold.  The last
 // three count from position 1024, i.e. land in a spare row of `bits`: no branch on the bin kind anywhere.
 //
 // This is also where every record of the path is examined (the census only samples).  A lane flags its slice
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
         else if (sel < 1024u) {
             const uint32_t d = p.table[sel];
             k = d < nk ? d : sel < p.ns_full ? nk + 2 : nk + 3;
-        } else k = sel == AVR_SEL_TERMINATE ? nk : (sel == AVR_SEL_BYPASS || sel == (AVR_NOP_CABAC >> 1)) ? nk + 1 : nk + 3;
+        } else k = sel == AVR_SEL_TERMINATE ? nk : sel == AVR_SEL_BYPASS ? nk + 1 : nk + 3;   // (the no-op selector too: a bad record)
         sel_tab[sel] = SelT((k >> 1) * 256u | (k & 1u) * 16u);
     }
     for (uint32_t i = lane; i < wave_dwords; i += 64) bits[i] = 0;
@@ -316,10 +319,11 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
     uint32_t *my_bits = bits + lane;                             // dword j at my_bits[64 j]
     uint8_t *cnt_b = reinterpret_cast<uint8_t *>(my_cnt), *bits_b = reinterpret_cast<uint8_t *>(my_bits);
     // Visit the chunk's 16-byte groups (8 records; a slice's records are padded with no-ops to a whole group), a
-    // cache line of records per trip with the next one in flight (see for_codes_all).
+    // cache line of records per trip with the next one in flight (see for_codes_all).  A record past the slice's last bin goes to
+    // the padding row by its index, as a one-byte record does: the no-op selector inside the slice is a bad record.
     auto for_groups = [&](auto &&f) { for_record_groups(r, i0, i1, f); };
     uint32_t high = 0;                                           // OR of all records: bits 12..15 must stay clear
-    const uint32_t k_pad = nk + 1;                               // R8: the row of a byte past the slice's last bin
+    const uint32_t k_pad = nk + 1;                               // the row of a record past the slice's last bin
     const uint32_t e_pad = (k_pad >> 1) * 256u | (k_pad & 1u) * 16u;
     // R8: the sixteen records of a group, their table entries (padding by index when masked) and bins
     auto group8 = [&](uint32_t base, const U4 &v, auto masked, uint32_t e[16], uint32_t bin[16]) {
@@ -340,12 +344,15 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
             __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(cnt_b + (e[j] & ~255u)), 1u << (e[j] & 31u), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
     });
-    else for_groups([&](const U4 &v) {                           // pass 1
+    else for_groups([&](uint32_t base, const U4 &v, auto masked) {      // pass 1
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         high |= (w[0] | w[1]) | (w[2] | w[3]);
         uint32_t e[8];
 #pragma unroll
-        for (uint32_t j = 0; j < 8; j++) e[j] = sel_tab[((w[j >> 1] >> ((j & 1) * 16)) >> 1) & 0x7ffu];
+        for (uint32_t j = 0; j < 8; j++) {
+            e[j] = sel_tab[((w[j >> 1] >> ((j & 1) * 16)) >> 1) & 0x7ffu];
+            if (decltype(masked)::value) e[j] = base + j < i1 ? e[j] : e_pad;
+        }
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++)                         // 1 << e: the shift takes the low five bits, 0 or 16
             __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(cnt_b + (e[j] & ~255u)), 1u << (e[j] & 31u), __ATOMIC_RELAXED,
@@ -380,11 +387,14 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
                                   __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     });
-    else for_groups([&](const U4 &v) {                           // pass 2
+    else for_groups([&](uint32_t base, const U4 &v, auto masked) {      // pass 2
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         uint32_t e[8], pos[8];
 #pragma unroll
-        for (uint32_t j = 0; j < 8; j++) e[j] = sel_tab[((w[j >> 1] >> ((j & 1) * 16)) >> 1) & 0x7ffu];
+        for (uint32_t j = 0; j < 8; j++) {
+            e[j] = sel_tab[((w[j >> 1] >> ((j & 1) * 16)) >> 1) & 0x7ffu];
+            if (decltype(masked)::value) e[j] = base + j < i1 ? e[j] : e_pad;
+        }
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++)
             pos[j] = __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(cnt_b + (e[j] & ~255u)), 1u << (e[j] & 31u), __ATOMIC_RELAXED,

@@ -4,6 +4,10 @@
 //   k_k2p_ranges_fp pass 1  lane per slice       the range recurrence (double-precision form); range and bytes emitted at every chunk start
 //   k_k2p_ranges_wave       wave per slice       the same for batches of up to 1 024 slices: the lanes unpack the operands side by side
 //   k_k2p_ranges   pass 1   lane per slice       the same in 64-bit integers: the slices the first form hands over (rare)
+//
+// Every form of pass 1 validates every record of the slices it walks (bit 15 clear, pos + neg > 0), off the range chain, and a
+// slice with a bad record ends AVR_SLICE_BAD_RECORD whatever else happens to it (note_status): the hand-over walks the whole slice
+// again and checks it again, and a segment goes on walking a slice that an earlier segment's pass 2 found too small for its region.
 //   k_k2p_zero     pass 2a  lane per chunk       zero the positions of the byte sums that are ADDED into
 //   k_k2p_code     pass 2b  lane per chunk       the coder from (low = 0, noted range); bytes added into 32-bit sums
 //   k_k2p_finish   pass 3   workgroup per slice  carries from the last byte, finish(), bytes out
@@ -38,6 +42,20 @@ __device__ __forceinline__ void note_status(int32_t *status, int32_t code) {
     if (code == AVR_SLICE_BAD_RECORD) atomicExch(status, code);
     else atomicCAS(status, AVR_SLICE_OK, code);
 }
+
+// Pass 1 validates what it walks, off the range chain: bit 15 clear (an OR of the records, `high`) and pos + neg > 0 (bits 1 .. 14 not all
+// clear) for every record in [0, n).  A record of total 0 reads as a 0 of probability one -- the padding's no-op, AVR_NOP_RANGE -- so it
+// is told apart by its index alone.  pk_min16: the smaller of each 16-bit half; a running minimum over the slice's records is at most 1
+// in a half iff one of them has total 0 and bit 15 clear (one with bit 15 set is caught by `high`).
+__device__ __forceinline__ uint32_t pk_min16(uint32_t a, uint32_t b) {
+    uint32_t d;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ bool has_total0(uint32_t min16) { return (min16 & 0xffffu) <= 1u || (min16 >> 16) <= 1u; }
+// a status pass 1 still walks: "no error yet", and a region too small, which pass 2 of an earlier segment may have found meanwhile -- a
+// bad record further on wins over it (note_status)
+__device__ __forceinline__ bool walks(int32_t st) { return st == AVR_SLICE_OK || st == AVR_SLICE_OVERFLOW; }
 
 struct K2Plan {
     const uint16_t *recs;
@@ -94,8 +112,9 @@ __global__ __launch_bounds__(64) void k_k2p_ranges(K2Plan p, uint32_t n_slices, 
     uint64_t range = kOne;                                       // arithmetic_code.h:96-97
     uint32_t pos = 0;
     bool ok = true;                                              // sticky: a bin of probability zero puts the slice in error
+    bool bad = false;                                            // a record with bit 15 set or pos + neg = 0 in [0, n): wins over the rest
     // eight records: operands first (they depend on the records alone), then the chain -- range_step, no branch in it
-    auto group = [&](const U4 &v) {
+    auto group = [&](uint32_t g, const U4 &v) {
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         uint32_t rec[8];
         double iv[8];
@@ -103,6 +122,7 @@ __global__ __launch_bounds__(64) void k_k2p_ranges(K2Plan p, uint32_t n_slices, 
         for (uint32_t k = 0; k < 8; k++) {
             rec[k] = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
             iv[k] = inv[((rec[k] >> 1) & 0x7fu) + ((rec[k] >> 8) & 0x7fu)];
+            bad |= g * 8 + k < n && ((rec[k] & 0x8000u) || !(rec[k] & 0x7ffeu));
         }
 #pragma unroll
         for (uint32_t k = 0; k < 8; k++) {
@@ -123,24 +143,26 @@ __global__ __launch_bounds__(64) void k_k2p_ranges(K2Plan p, uint32_t n_slices, 
         U4 nx2[4];
         line(g + 8, nx2);
         if ((g & (kChunk / 8 - 1)) == 0) { ck_range[c0 + (g >> 7)] = range; ck_pos[c0 + (g >> 7)] = pos; }
-        group(cur[0]); group(cur[1]); group(cur[2]); group(cur[3]);
+        group(g, cur[0]); group(g + 1, cur[1]); group(g + 2, cur[2]); group(g + 3, cur[3]);
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) { cur[k] = nx1[k]; nx1[k] = nx2[k]; }
     }
     if (g < n_groups) {                                          // the slice's last, partial line (chunks start on whole lines)
         if ((g & (kChunk / 8 - 1)) == 0) { ck_range[c0 + (g >> 7)] = range; ck_pos[c0 + (g >> 7)] = pos; }
-        for (uint32_t k = 0; g + k < n_groups; k++) group(cur[k]);
+        for (uint32_t k = 0; g + k < n_groups; k++) group(g + k, cur[k]);
     }
     if (n_groups == 0) { ck_range[c0] = range; ck_pos[c0] = 0; }  // an empty slice still has its one chunk
     fin_range[s] = range;
     fin_pos[s] = pos;
-    status[s] = ok ? (want_status == AVR_SLICE_OK ? AVR_SLICE_OK : AVR_SLICE_DONE) : AVR_SLICE_ZERO_PROB;   // DONE: parked for the hand-over's own passes 2, 3
+    status[s] = bad ? AVR_SLICE_BAD_RECORD : ok ? (want_status == AVR_SLICE_OK ? AVR_SLICE_OK : AVR_SLICE_DONE)   // DONE: parked for the
+                                                  : AVR_SLICE_ZERO_PROB;                                          // hand-over's own passes 2, 3
 }
 
 // Pass 1, double-precision form (range_step_fp, avr_k2p.h): the same chunk notes from a chain of 12 dependent
 // instructions per bin instead of 24.  A record's operands come from small LDS tables -- by total: { 1 / total,
 // 1 / (2 total) } and { total, 2^32 / total }, by (pos, bin): { +-pos, bin ? 0 : 1 }.  A slice with a new range below 2^39 anywhere (a record with pos or neg 0, or a bin of probability zero) is handed
-// to k_k2p_ranges (status AVR_SLICE_RETRY_SERIAL), which covers everything.  Also validates: bit 15 of a record must be clear.
+// to k_k2p_ranges (status AVR_SLICE_RETRY_SERIAL), which covers everything.  Also validates every record of the slice: bit 15 clear and
+// pos + neg > 0 (pk_min16 above; the slice's last group by index, its padding being records of total 0).
 struct TotA { double inv, h; };                           // by 2 total + bin: 1 / total, 1 / (2 total)
 struct TotB { double d, inv32; };                         // by 2 total + bin: total, 2^32 / total
 struct PosEntry { double ps, nb; };                       // by the record's low byte (2 pos + bin): +-pos, bin ? 0 : 1
@@ -170,7 +192,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
     }
     __syncthreads();
     const uint32_t s = block * 64 + threadIdx.x;
-    if (s >= n_slices || status[s] != AVR_SLICE_OK) return;
+    if (s >= n_slices || !walks(status[s])) return;
     const uint32_t n = p.n_bins[s], c0 = p.chunk_base[s];
     if (p.chunk_base[s + 1] - c0 >= long_chunks) return;
     const U4 *r = reinterpret_cast<const U4 *>(p.recs + p.rec_off[s]);
@@ -219,14 +241,29 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) v[k] = r[g + k < last ? g + k : last];
     };
+    // total 0 (see pk_min16): the minimum over the records of the groups walked, the slice's last group by its own records only
+    // (last_min: its padding halves read as 0xffff) -- the group to take it for is always the fourth of a line, or one of the tail's
+    uint32_t zmin = 0xffffffffu, last_min = 0xffffffffu;
+    auto group_min = [&](const U4 &v) { return pk_min16(pk_min16(v.x, v.y), pk_min16(v.z, v.w)); };
     U4 cur[4], nx1[4];
     BinFP oa[4], ob[4];
-    if (n_groups) { line(g_begin, cur); line(g_begin + 4, nx1); fetch(cur[0].x, cur[0].y, oa); }
+    if (n_groups) {
+        line(g_begin, cur); line(g_begin + 4, nx1); fetch(cur[0].x, cur[0].y, oa);
+        if (g_end == n_groups) {                                 // the segment ends the slice
+            const U4 v = r[last];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w}, in = n - last * 8;                   // 1 .. 8 records of the slice
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                last_min = pk_min16(last_min, w[k] | (2 * k < in ? 0u : 0xffffu) | (2 * k + 1 < in ? 0u : 0xffff0000u));
+        }
+    }
     uint32_t g = g_begin;
     for (; g + 4 <= g_end; g += 4) {                             // (g_end is a whole number of lines unless it is the slice's end)
         U4 nx2[4];
         line(g + 8, nx2);
         if ((g & (kChunk / 8 - 1)) == 0) note(g);
+        zmin = pk_min16(zmin, pk_min16(pk_min16(group_min(cur[0]), group_min(cur[1])),
+                                       pk_min16(group_min(cur[2]), g + 3 == last ? last_min : group_min(cur[3]))));
         __builtin_amdgcn_s_waitcnt(0xc07f);                      // lgkmcnt(0), here where it costs nothing: all that is in flight is the
                                                                  // trip before's last fetch, a walk old (else the compiler waits behind the next)
         fetch(cur[0].z, cur[0].w, ob); walk(oa);
@@ -242,6 +279,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
     }
     if (g < g_end) {                                             // the slice's last, partial line (chunks start on whole lines)
         if ((g & (kChunk / 8 - 1)) == 0) note(g);
+        for (uint32_t k = 0; k < 3 && g + k < g_end; k++) zmin = pk_min16(zmin, g + k == last ? last_min : group_min(cur[k]));
         fetch(cur[0].z, cur[0].w, ob); walk(oa); walk(ob);
         if (g + 1 < g_end) { fetch(cur[1].x, cur[1].y, oa); fetch(cur[1].z, cur[1].w, ob); walk(oa); walk(ob); }
         if (g + 2 < g_end) { fetch(cur[2].x, cur[2].y, oa); fetch(cur[2].z, cur[2].w, ob); walk(oa); walk(ob); }
@@ -254,7 +292,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
     }
     // (pass 2 of an earlier segment writes the same word from the second stream: a bad record wins over everything, and a slice that is
     // in error already is not asked to be walked again -- see note_status)
-    if (high & 0x80008000u) note_status(&status[s], AVR_SLICE_BAD_RECORD);
+    if ((high & 0x80008000u) || has_total0(zmin)) note_status(&status[s], AVR_SLICE_BAD_RECORD);
     else if (vmin_hi < kTwo39Hi) note_status(&status[s], AVR_SLICE_RETRY_SERIAL);   // the integer form walks it again, from the start
 }
 
@@ -273,7 +311,7 @@ __device__ __forceinline__ void ranges_wave_body(uint32_t s, uint32_t long_chunk
     __shared__ PosEntry pos_tab[256];
     __shared__ __attribute__((aligned(16))) uint8_t ring[2 * kRingBytes];
     const uint32_t lane = threadIdx.x;
-    if (s >= n_slices || status[s] != AVR_SLICE_OK) return;     // (the whole wave alike)
+    if (s >= n_slices || !walks(status[s])) return;             // (the whole wave alike)
     const uint32_t n = p.n_bins[s], c0 = p.chunk_base[s];
     if (p.chunk_base[s + 1] - c0 < long_chunks) return;          // (k_k2p_ranges_hybrid: a lane's)
     const uint32_t n_batches = (n + kRingBins - 1) / kRingBins;
@@ -296,8 +334,13 @@ __device__ __forceinline__ void ranges_wave_body(uint32_t s, uint32_t long_chunk
     uint32_t pos8 = seg_begin ? ck_pos[c0 + seg_begin] * 8u : 0u, high = 0;
     // a record behind the slice's last is read as 0: { -0, 1 }, a 0 of probability one (k_k2p_ranges_fp)
     auto load = [&](uint32_t b) -> uint32_t { const uint32_t i = b * kRingBins + lane; return i < n ? uint32_t(r[i]) : 0u; };
-    auto unpack = [&](uint32_t rec, uint32_t half) {             // this lane's record into slot `lane` of ring half `half`
+    // one inside it with total 0 is bad: checked where the record is unpacked, a batch after its load (at the load, the check would wait
+    // for the record there and then, where the walk has two batches to wait)
+    bool total0 = false;
+    auto unpack = [&](uint32_t rec, uint32_t b) {                // this lane's record of batch b into slot `lane` of ring half b & 1
+        const uint32_t half = b & 1u;
         high |= rec;
+        total0 |= b * kRingBins + lane < n && !(rec & 0x7ffeu);
         const uint32_t pos16 = (rec & 0xffu) << 4, tot16 = pos16 + (((rec >> 8) & 0x7fu) << 5);
         const TotA ta = *reinterpret_cast<const TotA *>(reinterpret_cast<const uint8_t *>(tot_a) + tot16);
         const TotB tb = *reinterpret_cast<const TotB *>(reinterpret_cast<const uint8_t *>(tot_b) + tot16);
@@ -312,11 +355,11 @@ __device__ __forceinline__ void ranges_wave_body(uint32_t s, uint32_t long_chunk
     };
     if (b_begin < b_end) {
         uint32_t rec1 = load(b_begin + 1);
-        unpack(load(b_begin), b_begin & 1u);
+        unpack(load(b_begin), b_begin);
         for (uint32_t b = b_begin; b < b_end; b++) {
             const uint32_t rec2 = load(b + 2);                   // two batches ahead of the walk (masked behind the slice's end)
             if ((b & (kChunk / kRingBins - 1)) == 0) note(b);
-            unpack(rec1, (b + 1) & 1u);                          // the next batch's operands: LDS works in order, the walk below finds its own complete
+            unpack(rec1, b + 1);                                 // the next batch's operands: LDS works in order, the walk below finds its own complete
             uint32_t base = (b & 1u) * kRingBytes;
             asm volatile("" : "+v"(base));                       // one base register, the 192 reads at immediate offsets
             BinFP oa[4], ob[4];
@@ -351,7 +394,7 @@ __device__ __forceinline__ void ranges_wave_body(uint32_t s, uint32_t long_chunk
         fin_range[s] = fp_to_u64(rg);
         fin_pos[s] = pos8 >> 3;
     }
-    const bool bad = __any((high & 0x8000u) != 0);
+    const bool bad = __any((high & 0x8000u) != 0 || total0);
     if (lane == 0) {
         if (bad) note_status(&status[s], AVR_SLICE_BAD_RECORD);
         else if (vmin_hi < kTwo39Hi) note_status(&status[s], AVR_SLICE_RETRY_SERIAL);   // the integer form walks it again, from the start

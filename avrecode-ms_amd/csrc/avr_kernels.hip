@@ -520,6 +520,7 @@ __global__ __launch_bounds__(64 * kK1MaxWaves) void k_cabac_encode(
             L.e.w.flush();
             if (st == AVR_SLICE_OK && L.e.w.n > cap) st = AVR_SLICE_OVERFLOW;
             if (missed) { st = AVR_SLICE_RETRY_SERIAL; L.e.w.n = 0; }   // whatever else: the bytes are not the slice's
+            else if (st == AVR_SLICE_BAD_RECORD) L.e.w.n = 0;       // no bytes, as on every path (what was written stays in the region)
         }
         if (active) { out_len[slice] = L.e.w.n; status[slice] = st; }
         else if (want_status == AVR_SLICE_OK) out_len[slice] = 0;

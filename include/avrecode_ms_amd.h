@@ -66,11 +66,24 @@ extern "C" {
 #define AVR_ERR_NOMEM      -4
 #define AVR_ERR_CAPACITY   -5   /* more slices / bins than the batch was created for */
 
-/* per-slice status written by the kernels */
+/* per-slice status written by the kernels.
+ *
+ * Malformed records -- one rule for every path that validates.  A slice with a record in [0, n_bins) that no recorder writes
+ * comes back AVR_SLICE_BAD_RECORD with length 0:
+ *   K1, two-byte   a bit of 12..15 set; a selector neither < n_states nor bypass / terminate (the no-op selector 1026 included:
+ *                  only the padding past n_bins may hold it); a put_terminate(1) that is not the slice's last bin
+ *   K1, one-byte   a selector in [n_states, 126); a put_terminate(1) that is not last; a rec_off that is not a multiple of 16
+ *   K2             bit 15 set, or pos + neg = 0
+ * Enforced by the packers (avr_pack_tiles_device, avr_pack_tiles8_device) with the tile coders behind them, by the K1p calls
+ * (avr_cabac_encode_chunked_device and its hinted, second-pass and parts forms, avr_cabac8_encode_chunked_device,
+ * avr_cabac_resolve_device), by K2p (avr_range_encode_chunked_device) and so by the batch API on either path: a slice's status
+ * does not depend on the path.  Precedence: AVR_SLICE_BAD_RECORD wins over AVR_SLICE_ZERO_PROB, AVR_SLICE_OVERFLOW and any
+ * hand-over inside a path, wherever in the slice the bad record sits.  The slice-major serial entry points
+ * (avr_cabac_encode_slices_device, avr_range_encode_slices_device) trust their input.  Resolved codes have no bad value. */
 #define AVR_SLICE_OK          0
 #define AVR_SLICE_ZERO_PROB   1  /* arithmetic_code.h:116-118 "emitted a zero-probability symbol" */
 #define AVR_SLICE_OVERFLOW    2  /* output region too small (never with the batch API's sizing) */
-#define AVR_SLICE_BAD_RECORD  3  /* selector out of range, or a bin after put_terminate(1) */
+#define AVR_SLICE_BAD_RECORD  3  /* a record the rule above calls malformed */
 
 #define AVR_SEL_BYPASS     1024
 #define AVR_SEL_TERMINATE  1025
@@ -224,9 +237,8 @@ int avr_multi_load(avr_multi *m, uint64_t *bins_per_device);
  *   tiles + (tile_off[t] + c*64 + l) * 16
  * so one wave-wide load instruction reads 1 KiB contiguous.  tile_off has n_tiles+1 entries
  * in units of 16-byte chunks. */
-/* Also validates every record (it is the one place each record is read exactly once): a K1
- * selector that is neither < n_states nor bypass/terminate, or a K2 record with pos+neg = 0 or
- * bit 15 set, sets status[slice] = AVR_SLICE_BAD_RECORD.  status must be zero-filled before. */
+/* Also validates every record (it is the one place each record is read exactly once) by the rule above (AVR_SLICE_*): a bad
+ * record sets status[slice] = AVR_SLICE_BAD_RECORD.  status must be zero-filled before. */
 int avr_pack_tiles_device(int device, void *stream, int kind, size_t n_states,
                           const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                           const uint32_t *order, size_t n_slices,
@@ -384,7 +396,8 @@ int avr_cabac_encode_chunked_device_parts(int device, void *stream, const uint16
  * walked by one lane per slice -- it is exact 63-bit arithmetic on its own previous value and does not decompose --
  * while low, the output bytes, the carries and finish() (arithmetic_code.h:128-144) are done per chunk of AVR_CHUNK_BINS
  * bins and per slice.  Of the plan only chunk_base, chunk_slice and total_chunks are used; out_total = out_off[n_slices];
- * out_off as for the other entry points (capacity n_bins + 16 per slice at least).  Input is the slice-major layout. */
+ * out_off as for the other entry points (capacity n_bins + 16 per slice at least).  Input is the slice-major layout; every record
+ * in [0, n_bins) is validated by the rule above (AVR_SLICE_*), the padding past it must be AVR_NOP_RANGE. */
 size_t avr_range_chunked_workspace_bytes(size_t n_slices, const avr_chunk_plan *plan, uint64_t out_total);
 int avr_range_encode_chunked_device(int device, void *stream,
                                     const uint16_t *recs, const uint64_t *rec_off,
