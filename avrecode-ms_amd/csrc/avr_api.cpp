@@ -90,8 +90,10 @@ struct PinBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
-// Host-side plan shared by the batch API and tests: process slices longest first, 64 per tile.
-void plan_tiles(const std::vector<uint32_t> &n_bins, std::vector<uint32_t> &order, std::vector<uint64_t> &tile_off) {
+// Host-side plan shared by the batch API and tests: process slices longest first, 64 per tile.  records_per_chunk: 8 for two-byte
+// records, 16 for one-byte tiles (k_pack_tiles8_narrow).
+void plan_tiles(const std::vector<uint32_t> &n_bins, std::vector<uint32_t> &order, std::vector<uint64_t> &tile_off,
+                uint32_t records_per_chunk = 8) {
     const size_t n = n_bins.size();
     order.resize(n);
     std::iota(order.begin(), order.end(), 0u);
@@ -99,7 +101,7 @@ void plan_tiles(const std::vector<uint32_t> &n_bins, std::vector<uint32_t> &orde
     const size_t n_tiles = (n + 63) / 64;
     tile_off.assign(n_tiles + 1, 0);
     for (size_t t = 0; t < n_tiles; t++) {
-        const uint64_t chunks = (uint64_t(n_bins[order[t * 64]]) + 7) / 8;   // sorted: first lane is the longest
+        const uint64_t chunks = (uint64_t(n_bins[order[t * 64]]) + records_per_chunk - 1) / records_per_chunk;   // sorted: first lane is the longest
         tile_off[t + 1] = tile_off[t] + chunks * 64;
     }
 }
@@ -454,7 +456,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     std::vector<uint64_t> tile_off;
     std::vector<uint64_t> &out_off = b->out_off;
     out_off.assign(n + 1, 0);
-    plan_tiles(b->n_bins, order, tile_off);
+    plan_tiles(b->n_bins, order, tile_off, b->recs8 ? 16 : 8);  // one-byte records: one-byte tiles (the chunked path has no tiles)
     // worst case is 8 bits per bin for either coder ("output sizing") + stop bytes
     for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + ((uint64_t(b->n_bins[i]) + 16 + 7) & ~uint64_t(7));
     const uint64_t total_recs = b->rec_off.back(), total_chunks = tile_off.back(), total_out = out_off.back();
@@ -484,7 +486,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     const avr::DenseHint hint{use_hint ? std::min<uint32_t>(b->dense_hint, uint32_t(ns)) : 0u, b->h_ndense.p, b->h_ndense.p + 1};
     b->hint_used = hint.rows;
     b->h_ndense.p[0] = b->h_ndense.p[1] = 0;
-    if (b->recs8 && chunked) {                                   // the one-byte K1p call needs no guess: its contexts are the slices' n_states
+    if (b->recs8) {                                              // neither one-byte path needs a guess: the contexts are the slices' n_states
         b->hint_used = 0;
         b->h_ndense.p[0] = uint32_t(ns);
     }
@@ -501,8 +503,9 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if (cabac && ns) AVR_HIP(hipMemcpyAsync(b->d_states.p, b->h_states.p, n * ns, hipMemcpyHostToDevice, s));
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
-    // Both K1 paths renumber the batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
+    // Both K1 paths renumber a two-byte batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
     // their census pass, the one-lane-per-slice kernel through launch_cabac_encode): records and states go in as they are.
+    // One-byte records name dense ids below n_states already: neither one-byte path counts or renumbers.
     if (chunked && !cabac) {
         // K2 for few, long slices: the range recurrence per slice, everything else per chunk (avr_k2p.hip)
         std::vector<uint32_t> chunk_base(n + 1, 0), chunk_slice;
@@ -558,14 +561,17 @@ static int submit_impl(avr_batch *b, bool use_hint) {
             AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(ns), &plan, wsp,
                                     b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p, &hint));
     } else {
-        if (b->recs8)                                            // one-byte records widened, validated and transposed in one pass
-            AVR_HIP(avr::launch_pack_tiles8(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
-                                            b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
+        if (b->recs8)                                            // one-byte records validated and transposed in one pass, as they are
+            AVR_HIP(avr::launch_pack_tiles8_narrow(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
+                                                   b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
         else
             AVR_HIP(avr::launch_pack_tiles(s, b->kind, uint32_t(ns), b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
                                            b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
         AVR_HIP(hipEventRecord(b->ev[2], s));
-        if (cabac)
+        if (b->recs8)                                            // no census, no guess, nothing waits
+            AVR_HIP(avr::launch_cabac8_encode(s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_states.p,
+                                              uint32_t(ns), b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p));
+        else if (cabac)
             AVR_HIP(avr::launch_cabac_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_states.p,
                                              uint32_t(ns), b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p,
                                              AVR_SLICE_OK, true, &hint));
@@ -874,6 +880,33 @@ int avr_pack_tiles8_device(int device, void *stream, size_t n_states, const uint
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_pack_tiles8(static_cast<hipStream_t>(stream), uint32_t(n_states), recs8, rec_off, n_bins, order,
                                     uint32_t(n_slices), tile_off, tiles, status));
+    return AVR_OK;
+}
+
+int avr_pack_tiles8_narrow_device(int device, void *stream, size_t n_states, const uint8_t *recs8, const uint64_t *rec_off,
+                                  const uint32_t *n_bins, const uint32_t *order, size_t n_slices, const uint64_t *tile_off, void *tiles,
+                                  int32_t *status) {
+    if (int rc = check_common(rec_off, n_bins, tile_off, n_slices)) return rc;
+    if (int rc = check_recs8(recs8, rec_off, n_states)) return rc;
+    if (n_slices && (!recs8 || !tiles || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (reinterpret_cast<uintptr_t>(tiles) & 15) return fail(AVR_ERR_INVALID, "tiles is not 16-byte aligned");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_pack_tiles8_narrow(static_cast<hipStream_t>(stream), uint32_t(n_states), recs8, rec_off, n_bins, order,
+                                           uint32_t(n_slices), tile_off, tiles, status));
+    return AVR_OK;
+}
+
+int avr_cabac8_encode_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                   uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states) {
+    if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
+    if (n_states > AVR_MAX_STATES8)
+        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    if (n_slices && (!tiles || !out || !out_len || !status || (n_states && !init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (reinterpret_cast<uintptr_t>(tiles) & 15) return fail(AVR_ERR_INVALID, "tiles is not 16-byte aligned");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_cabac8_encode(static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices), init_states,
+                                      uint32_t(n_states), out, out_off, out_len, status, final_states));
     return AVR_OK;
 }
 

@@ -105,6 +105,12 @@ hipError_t launch_synth_tiles(hipStream_t s, int workload, uint32_t scale, uint6
 // one-byte K1 records (AVR_KIND_CABAC8, slice i at byte rec_off[i], a multiple of 16) -> the two-byte tiles of launch_pack_tiles
 hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
                               const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);
+// the same records -> ONE-BYTE tiles (16 records a chunk), and the one-lane-per-slice coder on them: no census, no wait
+hipError_t launch_pack_tiles8_narrow(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                                     const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);
+hipError_t launch_cabac8_encode(hipStream_t s, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins, const uint32_t *order,
+                                uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, uint8_t *out, const uint64_t *out_off,
+                                uint32_t *out_len, int32_t *status, uint8_t *final_states);
 hipError_t launch_context_census(hipStream_t s, const uint16_t *recs, uint64_t n, uint32_t *bitmap);
 hipError_t launch_context_remap(hipStream_t s, uint16_t *recs, uint64_t n, const uint16_t *table);
 hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_src, uint8_t *dst, uint32_t n_dst,

@@ -358,17 +358,22 @@ constexpr uint32_t kK1MaxWaves = 16;
 // FORM: 1 = normalised form (CabacLaneN: shipped; its output in 16-byte stores), 5 = that with 8-byte stores, 4 = with four state bytes read ahead,
 // 0 = the coder as cabac_code.h writes it (CabacLane), 2 = that with its digits
 // staged in LDS (CabacLaneS), 3 = the normalised form with them (CabacLaneNS); 0, 2 and 3 are measured variants of the test build.
-template <bool TILED, int FORM>
-__global__ __launch_bounds__(64 * kK1MaxWaves) void k_cabac_encode(
+// REC_BYTES: 2 = two-byte records (AVR_KIND_CABAC, AVR_NOP_CABAC padding), 1 = ONE-BYTE tiles (AVR_KIND_CABAC8, 16 records a chunk:
+// k_pack_tiles8_narrow) -- FORM 1 only, no renumbering (table / index null, n_rows = n_states <= AVR_MAX_STATES8: the selectors are
+// dense ids already), at most kK1Waves waves: reading sixteen selectors ahead takes registers, and a 1024-thread bound caps a lane at 128.
+template <bool TILED, int FORM, int REC_BYTES = 2>
+__global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) void k_cabac_encode(
     const void *recs, const uint64_t *off, const uint32_t *n_bins, const uint32_t *order,
     uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const uint16_t *table, const uint16_t *index, uint32_t n_rows,
     uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
     uint8_t *final_states, int32_t want_status) {
     extern __shared__ uint32_t lds[];                            // per wave: state dwords [(n_rows + 4 + 3) / 4][64]; FORM 2: then 16 x 64 staging slots per wave
     constexpr bool NORM = FORM == 1 || FORM == 3 || FORM == 4 || FORM == 5;           // 5: FORM 1 with 8-byte output stores (rounds 1-3)
+    constexpr bool W8 = REC_BYTES == 1;
+    static_assert(REC_BYTES == 2 || (W8 && TILED && FORM == 1), "one-byte records: tiles, FORM 1");
     __shared__ uint2 tab[136];                                   // 128 states + pseudo-states 128..135
     __shared__ uint4 tabn[NORM ? 272 : 1];                       // the normalised form's: by (state, bin)
-    __shared__ uint32_t sel_off[2048];                           // selector -> byte offset of its state in the lane's column (up to 256 rows of 256 bytes, + 3)
+    __shared__ uint32_t sel_off[W8 ? 128 : 2048];                // selector -> byte offset of its state in the lane's column (up to 256 rows of 256 bytes, + 3)
 
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -394,6 +399,12 @@ __global__ __launch_bounds__(64 * kK1MaxWaves) void k_cabac_encode(
     }
     if constexpr (NORM)
         for (uint32_t i = threadIdx.x; i < 272; i += blockDim.x) tabn[i] = CabacLaneN::norm_entry(i >> 1, i & 1u);
+    if constexpr (W8) {                                          // a one-byte selector: a context's row as it is, 126 bypass, 127 terminate
+        for (uint32_t sel = threadIdx.x; sel < 128; sel += blockDim.x) {
+            const uint32_t k = sel < n_states ? sel : sel == AVR_SEL8_BYPASS ? n_rows : sel == AVR_SEL8_TERMINATE ? n_rows + 1 : n_rows + 2;
+            sel_off[sel] = ((k >> 2) << 8) + (k & 3);
+        }
+    } else
     for (uint32_t base = threadIdx.x; base < 2048; base += 8 * blockDim.x) {     // (eight entries a trip: their loads in flight together)
         uint32_t dense[8];
 #pragma unroll
@@ -459,7 +470,7 @@ __global__ __launch_bounds__(64 * kK1MaxWaves) void k_cabac_encode(
     else L.e.init(0x7F800000u, out + o0, cap);                   // cabac_code.h:30
 
     const ChunkSource<TILED> src(recs, off, in_range ? g : 0, slice);
-    const uint32_t n_chunks = (nb + 7) >> 3;
+    const uint32_t n_chunks = W8 ? (nb + 15) >> 4 : (nb + 7) >> 3;
     const uint4 nop4 = make_uint4(AVR_NOP_CABAC2, AVR_NOP_CABAC2, AVR_NOP_CABAC2, AVR_NOP_CABAC2);
     // every load is unconditional (the index clamped to the slice's last chunk; what a clamped load returns is never coded): a load
     // inside a branch is waited for before the branch ends -- the "two chunks ahead" of rounds 1-3 waited out a memory latency per
@@ -491,23 +502,49 @@ __global__ __launch_bounds__(64 * kK1MaxWaves) void k_cabac_encode(
             if constexpr (FORM == 2 || FORM == 3) { if (k == 7) L.rows(); }
         }
     };
+    // One-byte records: sixteen bins a chunk.  A byte has no no-op value (with n_states = 126 every selector means something), so the
+    // bytes past n_bins are told apart by their index -- in the slice's last chunk only, which the loop below leaves to a pass of its own:
+    // `valid` is 16 in the loop (the compare folds away) and the slice's n_bins & 15 after it; a padding byte goes to the no-op row.
+    const uint32_t nop_off = (((n_rows + 2) >> 2) << 8) + ((n_rows + 2) & 3);
+    auto code16 = [&](const uint4 &v, uint32_t valid) {
+        if constexpr (W8) {
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            uint32_t offs[16];
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++) offs[k] = k < valid ? sel_off[(w[k >> 2] >> (8 * (k & 3) + 1)) & 0x7fu] : nop_off;
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++) {
+                L.bin(w[k >> 2] >> (8 * (k & 3)), offs[k], tabn, st_lane);
+                if ((k & 3) == 3) L.template digits<true>();
+            }
+        }
+    };
     // The records come two chunks ahead, marked non-temporal (read once: nothing of them need stay in L2).
     uint4 ca = nop4, cb = nop4;
     if (n_chunks) { ca = src.load_nt(0); cb = src.load_nt(min(1u, last_chunk)); }
-    for (uint32_t c = 0; c < n_chunks; c++) {
+    const uint32_t n_whole = W8 ? nb >> 4 : n_chunks;            // chunks coded in the loop: every one of them all the slice's
+    for (uint32_t c = 0; c < n_whole; c++) {
         const uint4 nx2 = src.load_nt(min(c + 2, last_chunk));
-        code8(ca);
+        if constexpr (W8) code16(ca, 16);
+        else code8(ca);
         ca = cb;
         cb = nx2;
     }
-    constexpr uint32_t kTerm1 = (AVR_SEL_TERMINATE << 1) | 1;
+    if constexpr (W8)
+        if (nb & 15) code16(ca, nb & 15);                        // ca is chunk n_whole, the slice's last
+    constexpr uint32_t kTerm1 = W8 ? (AVR_SEL8_TERMINATE << 1) | 1 : (AVR_SEL_TERMINATE << 1) | 1;
     bool after_finish = false;                                   // a bin after the put_terminate(1), which was finish()
     if (active && nb) {
         const uint32_t tstate = st_lane[(((n_rows + 1) >> 2) << 8) + ((n_rows + 1) & 3)];
         if (tstate != 130u) {
             const uint4 v = src.load(last_chunk);
-            const uint32_t i = (nb - 1) & 7u, d = i < 2 ? v.x : i < 4 ? v.y : i < 6 ? v.z : v.w;
-            after_finish = tstate != 131u || ((d >> ((i & 1u) * 16)) & 0xffffu) != kTerm1;
+            if constexpr (W8) {                                  // the last record is byte (n_bins - 1) & 15 of the last chunk
+                const uint32_t i = (nb - 1) & 15u, d = i < 4 ? v.x : i < 8 ? v.y : i < 12 ? v.z : v.w;
+                after_finish = tstate != 131u || ((d >> ((i & 3u) * 8)) & 0xffu) != kTerm1;
+            } else {
+                const uint32_t i = (nb - 1) & 7u, d = i < 2 ? v.x : i < 4 ? v.y : i < 6 ? v.z : v.w;
+                after_finish = tstate != 131u || ((d >> ((i & 1u) * 16)) & 0xffffu) != kTerm1;
+            }
         }
     }
     if (in_range) {
@@ -753,6 +790,36 @@ __global__ __launch_bounds__(64) void k_pack_tiles8(
                 if (k & 1) o[k >> 1] |= r << 16; else o[k >> 1] = r;
             }
             v = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+        dst[size_t(c) * 64] = v;
+    }
+    if (active && bad) status[slice] = AVR_SLICE_BAD_RECORD;
+}
+
+// The same records into ONE-BYTE tiles (include/avrecode_ms_amd.h: sixteen records a 16-byte chunk), what k_cabac_encode<true, 1, 1>
+// reads: validated (the rule of k_pack_tiles8) and transposed in one pass, every byte as it came -- the bytes past n_bins too, which
+// the coder tells apart by their index.  A lane writes its slice's own chunks only; the rest of its tile column is never read.
+__global__ __launch_bounds__(64) void k_pack_tiles8_narrow(
+    uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+    const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, uint4 *tiles, int32_t *status) {
+    const uint32_t lane = threadIdx.x, t = blockIdx.x;
+    const uint32_t g = t * 64 + lane;
+    const bool active = g < n_slices;
+    const uint32_t slice = active ? (order ? order[g] : g) : 0;
+    const uint32_t nb = active ? n_bins[slice] : 0;
+    const uint32_t my_chunks = (nb + 15) >> 4;
+    const uint64_t off = active ? rec_off[slice] : 0;
+    const uint4 *src = reinterpret_cast<const uint4 *>(recs8 + (off & ~uint64_t(15)));
+    uint4 *dst = tiles + tile_off[t] + lane;
+    bool bad = (off & 15) != 0;
+    for (uint32_t c = 0; c < my_chunks; c++) {
+        const uint4 v = src[c];
+        const uint32_t valid = nb - c * 16;                      // records valid in this chunk (>= 1)
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {                      // a selector in [n_states, AVR_SEL8_BYPASS): no context of the slice
+            const uint32_t sel8 = (w[k >> 2] >> (8 * (k & 3) + 1)) & 0x7fu;
+            bad |= k < valid && sel8 - n_states < AVR_SEL8_BYPASS - n_states;
         }
         dst[size_t(c) * 64] = v;
     }
@@ -1023,6 +1090,19 @@ hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, cons
     return err;
 }
 
+// The one-lane-per-slice kernel on one-byte tiles: the selectors are dense ids below n_states <= AVR_MAX_STATES8 already, so there
+// is nothing to count or renumber -- one launch, kK1Waves waves a workgroup (at most 33 dwords of states a lane: 33.8 KiB of LDS for four waves).
+hipError_t launch_cabac8_encode(hipStream_t s, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins, const uint32_t *order,
+                                uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, uint8_t *out, const uint64_t *out_off,
+                                uint32_t *out_len, int32_t *status, uint8_t *final_states) {
+    if (n_slices == 0) return hipSuccess;
+    const uint32_t lds = kK1Waves * ((n_states + 4 + 3) / 4) * 256;
+    const dim3 grid((n_slices + 64 * kK1Waves - 1) / (64 * kK1Waves)), block(64 * kK1Waves);
+    hipLaunchKernelGGL((k_cabac_encode<true, 1, 1>), grid, block, lds, s, tiles, tile_off, n_bins, order, n_slices, init_states,
+                       n_states, nullptr, nullptr, n_states, out, out_off, out_len, status, final_states, int32_t(AVR_SLICE_OK));
+    return hipGetLastError();
+}
+
 hipError_t launch_range_encode(bool tiled, hipStream_t s, const void *recs, const uint64_t *off,
                                const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices,
                                uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
@@ -1049,6 +1129,15 @@ hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const uint8_t *r
     if (n_slices == 0) return hipSuccess;
     const dim3 grid((n_slices + 63) / 64), block(64);
     hipLaunchKernelGGL(k_pack_tiles8, grid, block, 0, s, n_states, recs8, rec_off, n_bins, order, n_slices, tile_off,
+                       reinterpret_cast<uint4 *>(tiles), status);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_tiles8_narrow(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                                     const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status) {
+    if (n_slices == 0) return hipSuccess;
+    const dim3 grid((n_slices + 63) / 64), block(64);
+    hipLaunchKernelGGL(k_pack_tiles8_narrow, grid, block, 0, s, n_states, recs8, rec_off, n_bins, order, n_slices, tile_off,
                        reinterpret_cast<uint4 *>(tiles), status);
     return hipGetLastError();
 }

@@ -20,17 +20,18 @@ def _stream_ptr(torch):
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def plan_tiles(n_bins):
+def plan_tiles(n_bins, records_per_chunk=8):
     """Processing order and tile offsets for per-slice bin counts (int32 tensor, any device).
 
     Slices are processed longest first, 64 per tile (one wave); a tile is as long as its
     longest slice.  Returns (order int32[n], tile_off int64[n_tiles+1] in 16-byte chunks).
+    records_per_chunk: 8 for two-byte records, 16 for one-byte tiles (avr_pack_tiles8_narrow_device).
     Same plan as plan_tiles() in csrc/avr_api.cpp.
     """
     import torch
     n = n_bins.numel()
     order = torch.argsort(n_bins.to(torch.int64), descending=True, stable=True)
-    chunks = (n_bins.to(torch.int64)[order] + 7) // 8
+    chunks = (n_bins.to(torch.int64)[order] + records_per_chunk - 1) // records_per_chunk
     tile_max = chunks[::64]
     tile_off = torch.zeros(tile_max.numel() + 1, dtype=torch.int64, device=n_bins.device)
     tile_off[1:] = torch.cumsum(tile_max * 64, 0)
@@ -60,8 +61,9 @@ class DeviceWorkload:
     """A batch of slices resident in HBM in the wave-interleaved tile layout.
 
     KIND_CABAC8: K1 from one-byte records (bin | dense selector << 1).  Such a workload keeps the records slice-major, one byte
-    each (rec8_flat, rec8_off: byte offsets, multiples of 16), for encode_chunked(), and the two-byte tiles avr_pack_tiles8_device
-    makes of them for encode()."""
+    each (rec8_flat, rec8_off: byte offsets, multiples of 16), for encode_chunked(), and tiles for encode(): by default the two-byte
+    tiles avr_pack_tiles8_device makes of them (encode() then blocks like any two-byte K1 call), with narrow_tiles=True the one-byte
+    tiles of avr_pack_tiles8_narrow_device (encode() is avr_cabac8_encode_tiles_device: nothing waits)."""
 
     def __init__(self, kind, device_index, n_bins, order, tile_off, tiles, init_states, n_states):
         import torch
@@ -108,14 +110,17 @@ class DeviceWorkload:
         return w
 
     @classmethod
-    def from_host(cls, kind, recs_list, init_states_list=None, device_index=0, pad_bytes=None):
+    def from_host(cls, kind, recs_list, init_states_list=None, device_index=0, pad_bytes=None, narrow_tiles=False):
         """Upload per-slice uint16 record arrays and pack them into tiles on the device.  KIND_CABAC8: uint8 records, slice-major
         at multiples of 16 bytes; the bytes between a slice's last record and the next slice are taken from pad_bytes (a uint8
-        array, repeated over the whole buffer; default zeros) -- the kernels must not code them, whatever they hold."""
+        array, repeated over the whole buffer; default zeros) -- the kernels must not code them, whatever they hold.
+        narrow_tiles (KIND_CABAC8 only): one-byte tiles for encode(), which then never blocks."""
         import numpy as np
         import torch
         if kind == KIND_CABAC8:
-            return cls._from_host8(recs_list, init_states_list, device_index, pad_bytes)
+            return cls._from_host8(recs_list, init_states_list, device_index, pad_bytes, narrow_tiles)
+        if narrow_tiles:
+            raise AvrError("narrow_tiles: one-byte tiles hold KIND_CABAC8 records only")
         L = lib()
         dev = torch.device("cuda", device_index)
         n = len(recs_list)
@@ -148,7 +153,7 @@ class DeviceWorkload:
         return w
 
     @classmethod
-    def _from_host8(cls, recs_list, init_states_list, device_index, pad_bytes):
+    def _from_host8(cls, recs_list, init_states_list, device_index, pad_bytes, narrow_tiles=False):
         import numpy as np
         import torch
         dev = torch.device("cuda", device_index)
@@ -165,34 +170,35 @@ class DeviceWorkload:
             init = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.uint8) for s in init_states_list])
                                     if n_states else np.zeros(1, np.uint8)).to(dev)
             w = cls._pack8(device_index, torch.from_numpy(flat).to(dev), torch.from_numpy(rec_off).to(dev),
-                           torch.from_numpy(nb).to(dev), init, n_states)
+                           torch.from_numpy(nb).to(dev), init, n_states, narrow_tiles)
             torch.cuda.synchronize(dev)
         return w
 
     @classmethod
-    def _pack8(cls, device_index, rec8_flat, rec8_off, n_bins, init_states, n_states):
-        """A KIND_CABAC8 workload from one-byte slice-major records on the device: tiles by avr_pack_tiles8_device."""
+    def _pack8(cls, device_index, rec8_flat, rec8_off, n_bins, init_states, n_states, narrow_tiles=False):
+        """A KIND_CABAC8 workload from one-byte slice-major records on the device: two-byte tiles by avr_pack_tiles8_device, or
+        one-byte tiles by avr_pack_tiles8_narrow_device (narrow_tiles)."""
         import torch
         if n_states > MAX_STATES8:
             raise AvrError(f"n_states {n_states} > {MAX_STATES8}: one-byte records name at most {MAX_STATES8} contexts")
         dev = n_bins.device
         n = n_bins.numel()
-        order, tile_off = plan_tiles(n_bins)
+        order, tile_off = plan_tiles(n_bins, 16 if narrow_tiles else 8)
         tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
         pack_status = torch.zeros(n, dtype=torch.int32, device=dev)
-        _check(lib().avr_pack_tiles8_device(device_index, _stream_ptr(torch), n_states, rec8_flat.data_ptr(), rec8_off.data_ptr(),
-                                            n_bins.data_ptr(), order.data_ptr(), n, tile_off.data_ptr(), tiles.data_ptr(),
-                                            pack_status.data_ptr()))
+        pack = lib().avr_pack_tiles8_narrow_device if narrow_tiles else lib().avr_pack_tiles8_device
+        _check(pack(device_index, _stream_ptr(torch), n_states, rec8_flat.data_ptr(), rec8_off.data_ptr(),
+                    n_bins.data_ptr(), order.data_ptr(), n, tile_off.data_ptr(), tiles.data_ptr(), pack_status.data_ptr()))
         w = cls(KIND_CABAC8, device_index, n_bins, order, tile_off, tiles, init_states, n_states)
-        w.rec8_flat, w.rec8_off = rec8_flat, rec8_off
+        w.rec8_flat, w.rec8_off, w.narrow_tiles = rec8_flat, rec8_off, bool(narrow_tiles)
         w.status.copy_(pack_status)
         return w
 
-    def to_cabac8(self):
+    def to_cabac8(self, narrow_tiles=False):
         """This K1 workload as one-byte records (a new KIND_CABAC8 workload on the same device): selector s < n_states stays s,
         bypass becomes SEL8_BYPASS, terminate SEL8_TERMINATE.  Needs n_states <= MAX_STATES8 -- after densify() for a stream that
         numbers its contexts sparsely.  The padding bytes are whatever the two-byte layout had there, narrowed (no-op records
-        become a context's byte): never coded."""
+        become a context's byte): never coded.  narrow_tiles: one-byte tiles for encode() (see from_host)."""
         import torch
         if self.kind != KIND_CABAC or self.n_states > MAX_STATES8:
             raise AvrError(f"to_cabac8 needs a KIND_CABAC workload with n_states <= {MAX_STATES8} (densify() first)")
@@ -213,14 +219,23 @@ class DeviceWorkload:
             flat8 = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
             flat8[:total] = (((sel8 << 1) | (r & 1)) & 0xff).to(torch.uint8)
             del r, sel, sel8
-            w = DeviceWorkload._pack8(self.device_index, flat8, off8, self.n_bins, self.init_states, self.n_states)
+            w = DeviceWorkload._pack8(self.device_index, flat8, off8, self.n_bins, self.init_states, self.n_states, narrow_tiles)
             torch.cuda.synchronize(dev)
         return w
 
     def encode(self):
         """One pass of the hot path over the batch (enqueued on torch's current stream).  K1: sized by the context count the previous
         run of this object reported (none yet: the call asks the device and waits); exact whatever the guess.  settle() after a
-        synchronisation takes the count over for the next run."""
+        synchronisation takes the count over for the next run.  KIND_CABAC8 with narrow_tiles: avr_cabac8_encode_tiles_device, which
+        has nothing to count and never blocks."""
+        if getattr(self, "narrow_tiles", False):
+            import torch
+            _check(lib().avr_cabac8_encode_tiles_device(
+                self.device_index, _stream_ptr(torch), self.tiles.data_ptr(), self.tile_off.data_ptr(), self.n_bins.data_ptr(),
+                self.order.data_ptr(), self.n_slices, self.init_states.data_ptr() if self.init_states is not None else None, self.n_states,
+                self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
+                self.final_states.data_ptr() if self.final_states is not None else None))
+            return
         if self.kind == KIND_CABAC and self._counts is not None:
             import torch
             self._hinted_path = "tiles"

@@ -74,7 +74,7 @@ extern "C" {
  *                  only the padding past n_bins may hold it); a put_terminate(1) that is not the slice's last bin
  *   K1, one-byte   a selector in [n_states, 126); a put_terminate(1) that is not last; a rec_off that is not a multiple of 16
  *   K2             bit 15 set, or pos + neg = 0
- * Enforced by the packers (avr_pack_tiles_device, avr_pack_tiles8_device) with the tile coders behind them, by the K1p calls
+ * Enforced by the packers (avr_pack_tiles_device, avr_pack_tiles8_device, avr_pack_tiles8_narrow_device) with the tile coders behind them, by the K1p calls
  * (avr_cabac_encode_chunked_device and its hinted, second-pass and parts forms, avr_cabac8_encode_chunked_device,
  * avr_cabac_resolve_device), by K2p (avr_range_encode_chunked_device) and so by the batch API on either path: a slice's status
  * does not depend on the path.  Precedence: AVR_SLICE_BAD_RECORD wins over AVR_SLICE_ZERO_PROB, AVR_SLICE_OVERFLOW and any
@@ -151,9 +151,10 @@ int avr_batch_add_slice_range(avr_batch *b, const uint16_t *recs, size_t n);
 int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n);
 /* K1 from ONE-BYTE records (AVR_KIND_CABAC8, above): the same slice as avr_batch_add_slice_cabac would take, in half the bytes
  * over PCIe -- which is what bounds the batch API end to end (2 B per bin against 0.1 B of output).  init_states: n_states <=
- * AVR_MAX_STATES8 bytes, indexed by the dense selector.  The device reads the one-byte records as they came, with no two-byte copy:
- * a batch of many short slices through avr_pack_tiles8_device's packer (widened, validated and transposed in one pass) and the
- * one-lane-per-slice kernel, a batch of few long ones through avr_cabac8_encode_chunked_device (no census, no host round trip).
+ * AVR_MAX_STATES8 bytes, indexed by the dense selector.  The device reads the one-byte records as they came, with no two-byte copy
+ * and no widening: a batch of many short slices through avr_pack_tiles8_narrow_device and avr_cabac8_encode_tiles_device (one-byte
+ * tiles, one lane per slice), a batch of few long ones through avr_cabac8_encode_chunked_device -- either way no census and no host
+ * round trip, so avr_batch_submit of a one-byte batch never waits, its first run included.
  * Same bytes, final states and statuses as avr_batch_add_slice_cabac -- a selector >= n_states that is neither bypass nor
  * terminate comes back as AVR_SLICE_BAD_RECORD. */
 int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n,
@@ -167,8 +168,9 @@ int avr_batch_reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *ini
 
 /* avr_batch_run = avr_batch_submit + avr_batch_wait.
  * avr_batch_submit enqueues the whole run on the batch's own stream -- H2D from pinned memory, the kernels, the
- * lengths on their way back -- and returns without waiting for the device (the first CABAC-record run of a batch
- * object waits once for a 4-byte context count; later runs are sized by that count and checked in avr_batch_wait).
+ * lengths on their way back -- and returns without waiting for the device (the first two-byte CABAC-record run of a batch
+ * object waits once for a 4-byte context count; later runs are sized by that count and checked in avr_batch_wait; a one-byte
+ * (AVR_KIND_CABAC8) batch never waits).
  * avr_batch_wait blocks until the results are in host memory.  Between the two calls the batch must not be
  * touched (add / reset / get fail with AVR_ERR_INVALID).  Two or three batch objects used in turn keep the copy
  * engines and the kernels of consecutive batches overlapped:
@@ -182,11 +184,11 @@ int avr_batch_get(avr_batch *b, size_t slice, const uint8_t **bytes, size_t *len
 /* K1 only: the slice's state bytes after its last bin (what cabac_code.h:43-47 leaves in *state). */
 int avr_batch_get_states(avr_batch *b, size_t slice, const uint8_t **states, size_t *n_states);
 /* How the last run went: [0] 1 = intra-slice parallel kernels, 0 = one lane per slice; [1] context rows the kernels
- * were sized by from the previous run's count (0: the run asked the device and waited); [2] contexts the batch uses
- * (as the sampled census saw them) -- except for a one-byte (AVR_KIND_CABAC8) batch on the intra-slice parallel kernels, which
- * take no census: there it is the batch's declared n_states, every one of which has a row; [3] bit 0 = avr_batch_wait found the guess too small and ran the batch
- * again, bit 1 = it ran the second pass of the intra-slice parallel path (slices with a bin in a context the sampled
- * census missed).  CABAC-record batches; zeros otherwise. */
+ * were sized by from the previous run's count (0: the run asked the device and waited, or needed no count); [2] contexts the
+ * batch uses (as the sampled census saw them) -- except for a one-byte (AVR_KIND_CABAC8) batch, on either path: it takes no census,
+ * so [1] is 0 and [2] is the batch's declared n_states, every one of which has a row; [3] bit 0 = avr_batch_wait found the guess
+ * too small and ran the batch again, bit 1 = it ran the second pass of the intra-slice parallel path (slices with a bin in a context
+ * the sampled census missed).  CABAC-record batches; zeros otherwise. */
 int avr_batch_run_info(avr_batch *b, uint32_t info[4]);
 /* milliseconds of the last run: [0] H2D, [1] pack kernel, [2] encode kernel, [3] D2H */
 int avr_batch_timings(avr_batch *b, float ms[4]);
@@ -215,14 +217,16 @@ int avr_multi_load(avr_multi *m, uint64_t *bins_per_device);
 /* ------------------------------------------------------------------ device-resident API
  * All pointers below are DEVICE pointers on `device`; `stream` is a hipStream_t (NULL = the
  * null stream).  Calls enqueue work on `stream` and return, with ONE exception: the K1 entry points that take
- * (bin, selector) records -- avr_cabac_encode_tiles_device / _slices_device / _chunked_device and
+ * two-byte (bin, selector) records -- avr_cabac_encode_tiles_device / _slices_device / _chunked_device and
  * avr_cabac_resolve_device -- size their launches by the number of contexts the batch uses, which the device counts:
  * they wait on `stream` once for that 4-byte count (the chunked forms a second time, for the 4-byte count of slices that
  * need their second pass), i.e. they block the calling thread until the stream has drained up to their census kernel.
  * A caller that must not block uses the batch API (avr_batch_submit sizes the launches by the previous batch's count and
  * checks afterwards), the same scheme on its own buffers (avr_cabac_encode_tiles_device_hinted / _chunked_device_hinted below: the
- * caller passes the count an earlier call reported and looks at what this one reports when it next synchronises), or resolved
- * codes (avr_cabac_encode_resolved_device / _codes_device and every K2 entry: no wait).
+ * caller passes the count an earlier call reported and looks at what this one reports when it next synchronises), one-byte records
+ * (avr_pack_tiles8_narrow_device + avr_cabac8_encode_tiles_device, avr_cabac8_encode_chunked_device: no wait, no guess), or resolved
+ * codes (avr_cabac_encode_resolved_device / _codes_device and every K2 entry: no wait).  avr_cabac_encode_tiles_device blocks behind
+ * avr_pack_tiles8_device's two-byte tiles as behind any other.
  * These are what the batch API is made of and what bench.py times with inputs already resident in HBM (its K1 steps: the hinted calls).
  * ONE THREAD PER STREAM: the library keeps a few kilobytes of scratch (and, for the chunked K2, a second stream with its
  * events) per (device, stream); a call's kernels find them there, so two host threads must not enqueue on the same stream
@@ -268,6 +272,38 @@ int avr_cabac_encode_tiles_device(int device, void *stream,
                                   const uint8_t *init_states, size_t n_states,
                                   uint8_t *out, const uint64_t *out_off,
                                   uint32_t *out_len, int32_t *status, uint8_t *final_states);
+
+/* ONE-BYTE tile layout (AVR_KIND_CABAC8 records as they are, no widening): the wave-interleaved layout above with SIXTEEN one-byte
+ * records per 16-byte chunk.  Chunk c of lane l of tile t is the 16 bytes at
+ *   tiles + (tile_off[t] + 64*c + l) * 16
+ * and holds records 16c .. 16c+15 of slice order[64t + l]; a tile holds max-over-its-lanes ceil(n_bins/16) chunks (tile_off in
+ * 16-byte units, as above).  The bytes of a slice's last chunk past n_bins are padding: never coded, whatever they hold -- a byte has
+ * no no-op value (with n_states = 126 every selector means something), so the coder tells padding apart by its index.
+ *
+ * avr_pack_tiles8_narrow_device: the arguments and the slice-major input of avr_pack_tiles8_device (rec_off in bytes, multiples of 16,
+ * reads starting at multiples of 16), the same validation (a selector in [n_states, 126) or a rec_off that is not a multiple of 16:
+ * AVR_SLICE_BAD_RECORD for that slice alone; status zero-filled before) and the same refusals before anything touches a device,
+ * tiles not 16-byte aligned among them; the records are transposed into one-byte tiles in the same pass.  A lane writes its own
+ * slice's chunks only: the rest of its column of a tile is left as it was (never read).
+ *
+ * avr_cabac8_encode_tiles_device: the one-lane-per-slice coder on one-byte tiles -- the arguments of avr_cabac_encode_tiles_device,
+ * with n_states <= AVR_MAX_STATES8, and the same bytes, final states and statuses as it gives on the same slices as two-byte records
+ * (a slice whose status is already non-zero is skipped with length 0; a put_terminate(1) that is not the slice's last bin:
+ * AVR_SLICE_BAD_RECORD with length 0; AVR_SLICE_OVERFLOW for a region too small).  The selectors are dense ids below n_states already,
+ * so the call has nothing to count or renumber: it NEVER BLOCKS THE CALLING THREAD -- no census, no read-back, no guess, no second
+ * launch, no allocation; every kernel is enqueued on `stream` and the call returns.  Refused before anything touches a device
+ * (AVR_ERR_INVALID): n_states > AVR_MAX_STATES8, a null pointer with n_slices > 0 (init_states may be null when n_states is 0;
+ * final_states may be null), tiles not 16-byte aligned. */
+int avr_pack_tiles8_narrow_device(int device, void *stream, size_t n_states,
+                                  const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                                  const uint32_t *order, size_t n_slices,
+                                  const uint64_t *tile_off, void *tiles, int32_t *status);
+int avr_cabac8_encode_tiles_device(int device, void *stream,
+                                   const void *tiles, const uint64_t *tile_off,
+                                   const uint32_t *n_bins, const uint32_t *order, size_t n_slices,
+                                   const uint8_t *init_states, size_t n_states,
+                                   uint8_t *out, const uint64_t *out_off,
+                                   uint32_t *out_len, int32_t *status, uint8_t *final_states);
 
 /* K2. */
 int avr_range_encode_tiles_device(int device, void *stream,
