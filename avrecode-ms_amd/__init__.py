@@ -31,14 +31,15 @@ HOOKS_LIB_PATH = os.path.join(_HERE, "libavrecode_hip_hooks.so")   # -DAVR_TEST_
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avrecode_ms_amd.h")
 
 KIND_CABAC, KIND_RANGE, KIND_CABAC_CODES, KIND_CABAC8 = 0, 1, 2, 3
+KIND_RANGE_KEYS, EST_KEYS = 4, 1026                           # key records: the estimators are resolved on the device
 SEL_BYPASS, SEL_TERMINATE = 1024, 1025
 SEL8_BYPASS, SEL8_TERMINATE, MAX_STATES8 = 126, 127, 126      # one-byte records (KIND_CABAC8)
 SLICE_OK, SLICE_ZERO_PROB, SLICE_OVERFLOW, SLICE_BAD_RECORD = 0, 1, 2, 3
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_api.cpp"]
-_DEPS = _SOURCES + ["avr_coder.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_synth.h", "avr_tables.h"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_api.cpp"]
+_DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_synth.h", "avr_tables.h"]
 
 
 class AvrError(RuntimeError):
@@ -145,6 +146,12 @@ SIGNATURES = {
     "avr_batch_add_slice_range": (c_int, [c_void_p, c_void_p, c_size_t]),
     "avr_batch_add_slice_codes": (c_int, [c_void_p, c_void_p, c_size_t]),
     "avr_batch_add_slice_cabac8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "avr_batch_begin_group": (c_int, [c_void_p, c_void_p]),
+    "avr_batch_add_slice_range_keys": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "avr_batch_get_estimators": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "avr_range_resolve_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
+    "avr_range_resolve_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "avr_batch_reserve_slice": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, POINTER(c_void_p)]),
     "avr_batch_submit": (c_int, [c_void_p]),
     "avr_batch_wait": (c_int, [c_void_p]),
@@ -377,6 +384,30 @@ class Batch:
         r = np.ascontiguousarray(recs, dtype=np.uint16)
         return _check(self._L.avr_batch_add_slice_range(self._h, r.ctypes.data, r.size))
 
+    def begin_group(self, est=None) -> int:
+        """Key records: the slices added from here on form a new group, which shares one table of EST_KEYS estimators -- fresh
+        {1, 1}, or `est`: EST_KEYS x 2 uint8 {pos, neg} (the get_estimators() of the group's earlier part).  Returns the group's index."""
+        import numpy as np
+        if est is None:
+            return _check(self._L.avr_batch_begin_group(self._h, None))
+        e = np.ascontiguousarray(est, dtype=np.uint8)
+        if e.size != EST_KEYS * 2:
+            raise AvrError(f"a start table has {EST_KEYS} x 2 entries, not {e.size}")
+        return _check(self._L.avr_batch_begin_group(self._h, e.ctypes.data))
+
+    def add_slice_range_keys(self, recs) -> int:
+        """K2 from key records (bin | key << 1; keys 0..1023, SEL_BYPASS, SEL_TERMINATE): the estimators are resolved on the GPU."""
+        import numpy as np
+        r = np.ascontiguousarray(recs, dtype=np.uint16)
+        return _check(self._L.avr_batch_add_slice_range_keys(self._h, r.ctypes.data, r.size))
+
+    def get_estimators(self, group: int):
+        """The group's table after the run: EST_KEYS x 2 uint8 {pos, neg}, in the layout begin_group() takes."""
+        import numpy as np
+        p, n = c_void_p(), c_size_t()
+        _check(self._L.avr_batch_get_estimators(self._h, group, ctypes.byref(p), ctypes.byref(n)))
+        return np.frombuffer(ctypes.string_at(p.value, n.value * 2), np.uint8).reshape(n.value, 2).copy()
+
     def add_slice_cabac8(self, recs8, init_states) -> int:
         """K1 from one-byte records (bin | dense selector << 1; selectors SEL8_BYPASS / SEL8_TERMINATE): half the bytes over PCIe."""
         import numpy as np
@@ -503,7 +534,7 @@ class MultiBatch:
 
 from .device import DeviceWorkload, encode_tiles, plan_tiles, synth_config  # noqa: E402  (torch-backed helpers)
 
-__all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE",
+__all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS",
            "SEL_BYPASS", "SEL_TERMINATE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
            "make_cabac_records", "make_range_records", "plan_tiles", "synth_config", "tail_patch"]

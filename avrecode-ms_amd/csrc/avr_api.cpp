@@ -113,6 +113,7 @@ struct avr_batch {
     size_t max_slices = 0, max_bins = 0, total_bins = 0;
     int kind = -1;
     bool recs8 = false;                     // the slices came as one-byte records (AVR_KIND_CABAC8); kind is AVR_KIND_CABAC
+    bool keys = false;                      // the slices came as key records (AVR_KIND_RANGE_KEYS); kind is AVR_KIND_RANGE
     size_t n_states = 0;
     bool ran = false;
     hipStream_t stream = nullptr;
@@ -142,6 +143,15 @@ struct avr_batch {
     DevBuf<uint32_t> d_chunk_base, d_chunk_slice, d_blk_base, d_blk_slice;
     DevBuf<uint8_t> d_workspace;
     int last_path = 0;                      // 0 = one lane per slice, 1 = chunked
+
+    // key records: the groups (first slice of each), their start tables where the caller gave one, the tables after the run
+    std::vector<uint32_t> group_first;
+    std::vector<uint8_t> est_in;            // one table a group, fresh ones included
+    PinBuf<uint8_t> h_est_in, h_est_out;
+    bool any_est_in = false, est_out_fetched = false;
+    DevBuf<uint16_t> d_keys;
+    DevBuf<uint32_t> d_group_first, d_est_chunk_base, d_est_chunk_slice;
+    DevBuf<uint8_t> d_est_in, d_est_out, d_est_ws;
 
     // submit / wait: nothing the device reads may be pageable or local to a call
     PinBuf<uint8_t> h_plan;                 // the plan arrays of the run in flight
@@ -263,6 +273,8 @@ void avr_batch_destroy(avr_batch *b) {
     b->d_out.release(); b->d_dense.release();
     b->d_res_off.release(); b->d_dig_off.release(); b->d_chunk_base.release(); b->d_chunk_slice.release();
     b->d_blk_base.release(); b->d_blk_slice.release(); b->d_workspace.release();
+    b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release(); b->d_est_chunk_base.release();
+    b->d_est_chunk_slice.release(); b->d_est_in.release(); b->d_est_out.release(); b->d_est_ws.release();
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
     if (b->stream) { avr::forget_part_streams(b->stream); avr::forget_stream(b->stream); (void)hipStreamDestroy(b->stream); }
     delete b;
@@ -271,11 +283,34 @@ void avr_batch_destroy(avr_batch *b) {
 int avr_batch_reset(avr_batch *b) {
     if (!b) return fail(AVR_ERR_INVALID, "null batch");
     if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
-    b->kind = -1; b->recs8 = false; b->n_states = 0; b->ran = false; b->total_bins = 0;
+    b->kind = -1; b->recs8 = false; b->keys = false; b->n_states = 0; b->ran = false; b->total_bins = 0;
+    b->group_first.clear(); b->est_in.clear(); b->any_est_in = false; b->est_out_fetched = false;
     b->rec_off.assign(1, 0);
     b->n_bins.clear();
     b->dense_off.clear();
     return AVR_OK;
+}
+
+constexpr size_t kEstTable = size_t(AVR_EST_KEYS) * 2;           // bytes of one table of estimators
+
+int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in) {
+    if (!b) return fail(AVR_ERR_INVALID, "null batch");
+    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
+    if (b->kind >= 0 && !b->keys) return fail(AVR_ERR_INVALID, "a batch holds slices of one kind only: groups belong to key records");
+    if (b->group_first.size() >= b->max_slices) return fail(AVR_ERR_CAPACITY, "batch holds max_slices=%zu groups", b->max_slices);
+    for (size_t k = 0; est_in && k < AVR_EST_KEYS; k++) {
+        const unsigned pos = est_in[2 * k], neg = est_in[2 * k + 1];
+        if (pos < 1 || neg < 1 || pos + neg > 0x60)
+            return fail(AVR_ERR_INVALID, "start table entry %zu = {%u, %u}: need pos >= 1, neg >= 1, pos + neg <= 0x60", k, pos, neg);
+    }
+    const size_t g = b->group_first.size();
+    b->est_in.resize((g + 1) * kEstTable);
+    uint8_t *dst = b->est_in.data() + g * kEstTable;
+    if (est_in) memcpy(dst, est_in, kEstTable); else memset(dst, 1, kEstTable);    // fresh: {1, 1}
+    b->any_est_in |= est_in != nullptr;
+    b->group_first.push_back(uint32_t(b->n_bins.size()));
+    return int(g);
 }
 
 // Room for one more slice in the pinned staging buffer (padding written); *where = its first element.
@@ -283,19 +318,27 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
     if (!b) return fail(AVR_ERR_INVALID, "null batch");
     if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
     if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
-    if (kind != AVR_KIND_CABAC && kind != AVR_KIND_RANGE && kind != AVR_KIND_CABAC_CODES && kind != AVR_KIND_CABAC8)
+    if (kind != AVR_KIND_CABAC && kind != AVR_KIND_RANGE && kind != AVR_KIND_CABAC_CODES && kind != AVR_KIND_CABAC8 &&
+        kind != AVR_KIND_RANGE_KEYS)
         return fail(AVR_ERR_INVALID, "unknown kind %d", kind);
+    // key records are K2 records before their estimators are resolved: the batch is an AVR_KIND_RANGE batch whose records the device makes
+    const bool keys = kind == AVR_KIND_RANGE_KEYS;
+    if (keys) kind = AVR_KIND_RANGE;
     // one-byte records are K1 records in another width: the batch is an AVR_KIND_CABAC batch whose staging buffer holds bytes
     const bool recs8 = kind == AVR_KIND_CABAC8;
     if (recs8) {
         if (n_states > AVR_MAX_STATES8) return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
         kind = AVR_KIND_CABAC;
     }
-    if (b->kind >= 0 && (b->kind != kind || b->recs8 != recs8)) return fail(AVR_ERR_INVALID, "a batch holds slices of one kind only");
+    if ((b->kind >= 0 && (b->kind != kind || b->recs8 != recs8 || b->keys != keys)) || (!keys && !b->group_first.empty()))
+        return fail(AVR_ERR_INVALID, "a batch holds slices of one kind only");
     if (n > 0xfffffff0u) return fail(AVR_ERR_INVALID, "slice too long");
     if (b->n_bins.size() >= b->max_slices) return fail(AVR_ERR_CAPACITY, "batch holds max_slices=%zu slices", b->max_slices);
     if (b->total_bins + n > b->max_bins) return fail(AVR_ERR_CAPACITY, "batch holds max_bins=%zu records", b->max_bins);
     const size_t idx = b->n_bins.size();
+    if (keys && b->group_first.empty()) {                        // no group begun: a fresh one
+        if (int rc = avr_batch_begin_group(b, nullptr); rc < 0) return rc;
+    }
     if (kind == AVR_KIND_CABAC) {
         if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
         if (!init_states && n_states) return fail(AVR_ERR_INVALID, "null init_states");
@@ -335,6 +378,7 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
     b->n_bins.push_back(uint32_t(n));
     b->kind = kind;
     b->recs8 = recs8;
+    b->keys = keys;
     return int(idx);
 }
 
@@ -355,6 +399,14 @@ int avr_batch_add_slice_range(avr_batch *b, const uint16_t *recs, size_t n) {
     if (!recs && n) return fail(AVR_ERR_INVALID, "null records");
     void *dst = nullptr;
     const int idx = reserve_slice(b, AVR_KIND_RANGE, n, nullptr, 0, &dst);
+    if (idx >= 0 && n) memcpy(dst, recs, n * sizeof(uint16_t));
+    return idx;
+}
+
+int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n) {
+    if (!recs && n) return fail(AVR_ERR_INVALID, "null records");
+    void *dst = nullptr;
+    const int idx = reserve_slice(b, AVR_KIND_RANGE_KEYS, n, nullptr, 0, &dst);
     if (idx >= 0 && n) memcpy(dst, recs, n * sizeof(uint16_t));
     return idx;
 }
@@ -445,6 +497,40 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
 
 // Everything of a run up to the lengths on their way back.  `use_hint`: size the kernels by the context count of this
 // object's previous run instead of asking the device and waiting (avr::DenseHint); avr_batch_wait checks the guess.
+// A batch of key records: the estimators of every group resolved on the device, d_keys -> d_recs (K2 range records with their
+// padding), the groups' tables after the run left in d_est_out.  Enqueues and returns.
+static int resolve_keys(avr_batch *b, uint32_t n32) {
+    const size_t n = n32, n_groups = b->group_first.size();
+    std::vector<uint32_t> chunk_base(n + 1, 0), chunk_slice, group_first(b->group_first);
+    group_first.push_back(n32);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t nc = uint32_t(std::max<uint64_t>(1, (uint64_t(b->n_bins[i]) + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS));
+        chunk_base[i + 1] = chunk_base[i] + nc;
+        chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
+    }
+    const size_t ws = avr::est_workspace_bytes(n, n_groups, chunk_base.back());
+    int rc;
+    if ((rc = b->d_est_chunk_base.reserve(n + 1)) || (rc = b->d_est_chunk_slice.reserve(chunk_slice.size())) ||
+        (rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(ws + 256)) ||
+        (rc = b->d_est_out.reserve(n_groups * kEstTable)) || (b->any_est_in && (rc = b->d_est_in.reserve(n_groups * kEstTable))))
+        return rc;
+    hipStream_t s = b->stream;
+    AVR_STAGE(b->d_est_chunk_base.p, chunk_base.data(), n + 1);
+    AVR_STAGE(b->d_est_chunk_slice.p, chunk_slice.data(), chunk_slice.size());
+    AVR_STAGE(b->d_group_first.p, group_first.data(), n_groups + 1);
+    if (b->any_est_in) {                                         // through pinned memory: the copy must not read pageable memory after the call
+        if ((rc = b->h_est_in.reserve(n_groups * kEstTable))) return rc;
+        memcpy(b->h_est_in.p, b->est_in.data(), n_groups * kEstTable);
+        AVR_HIP(hipMemcpyAsync(b->d_est_in.p, b->h_est_in.p, n_groups * kEstTable, hipMemcpyHostToDevice, s));
+    }
+    uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_est_ws.p) + 255) & ~uintptr_t(255));
+    b->est_out_fetched = false;
+    AVR_HIP(avr::launch_est_resolve(s, b->d_keys.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p, uint32_t(n_groups),
+                                    b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, b->d_est_chunk_base.p,
+                                    b->d_est_chunk_slice.p, chunk_base.back(), wsp, b->d_recs.p, b->d_status.p));
+    return AVR_OK;
+}
+
 static int submit_impl(avr_batch *b, bool use_hint) {
     const size_t n = b->n_bins.size();
     const uint32_t n32 = uint32_t(n);
@@ -479,7 +565,10 @@ static int submit_impl(avr_batch *b, bool use_hint) {
                   (rc = b->h_final.reserve(n * std::max<size_t>(ns, 1)))))
         return rc;
     const size_t n_chunks_max = size_t(b->total_bins / AVR_CHUNK_BINS) + n + 1, n_blks_max = size_t(b->total_bins / AVR_SORT_BLOCK_BINS) + n + 1;
-    if ((rc = b->h_plan.reserve(64 * 16 + (n + 1) * 64 + (n_tiles + 1) * 8 + (chunked ? (n_chunks_max + n_blks_max) * 4 : 0)))) return rc;
+    const size_t n_groups = b->group_first.size();
+    if ((rc = b->h_plan.reserve(64 * 16 + (n + 1) * 64 + (n_tiles + 1) * 8 + (chunked ? (n_chunks_max + n_blks_max) * 4 : 0) +
+                                (b->keys ? (n_chunks_max + n + n_groups + 3) * 4 + 256 : 0)))) return rc;
+    if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
 
     hipStream_t s = b->stream;
     b->plan_used = 0;
@@ -492,7 +581,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     }
     AVR_HIP(hipEventRecord(b->ev[0], s));
     if (b->recs8) AVR_HIP(hipMemcpyAsync(b->d_recs8.p, b->h_recs.p, total_recs, hipMemcpyHostToDevice, s));        // one byte a record
-    else AVR_HIP(hipMemcpyAsync(b->d_recs.p, b->h_recs.p, total_recs * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    else AVR_HIP(hipMemcpyAsync(b->keys ? b->d_keys.p : b->d_recs.p, b->h_recs.p, total_recs * sizeof(uint16_t), hipMemcpyHostToDevice, s));
     AVR_STAGE(b->d_rec_off.p, b->rec_off.data(), n + 1);
     AVR_STAGE(b->d_out_off.p, out_off.data(), n + 1);
     AVR_STAGE(b->d_n_bins.p, b->n_bins.data(), n);
@@ -506,6 +595,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     // Both K1 paths renumber a two-byte batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
     // their census pass, the one-lane-per-slice kernel through launch_cabac_encode): records and states go in as they are.
     // One-byte records name dense ids below n_states already: neither one-byte path counts or renumbers.
+    if (b->keys && (rc = resolve_keys(b, n32))) return rc;       // key records: d_keys -> d_recs, inside slot [1] of the timings
     if (chunked && !cabac) {
         // K2 for few, long slices: the range recurrence per slice, everything else per chunk (avr_k2p.hip)
         std::vector<uint32_t> chunk_base(n + 1, 0), chunk_slice;
@@ -682,6 +772,23 @@ int avr_batch_get_states(avr_batch *b, size_t slice, const uint8_t **states, siz
     if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
     if (states) *states = b->h_final.p + slice * b->n_states;
     if (n_states) *n_states = b->n_states;
+    return AVR_OK;
+}
+
+int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg, size_t *n_keys) {
+    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (!b->keys) return fail(AVR_ERR_INVALID, "not a batch of key records");
+    if (group >= b->group_first.size()) return fail(AVR_ERR_INVALID, "group %zu out of range", group);
+    if (!b->est_out_fetched) {                                   // on first use: most callers want the table of a file's last batch only
+        if (int rc = select_device(b->device)) return rc;
+        const size_t bytes = b->group_first.size() * kEstTable;
+        if (int rc = b->h_est_out.reserve(bytes)) return rc;
+        AVR_HIP(hipMemcpyAsync(b->h_est_out.p, b->d_est_out.p, bytes, hipMemcpyDeviceToHost, b->stream));
+        AVR_HIP(hipStreamSynchronize(b->stream));
+        b->est_out_fetched = true;
+    }
+    if (pos_neg) *pos_neg = b->h_est_out.p + group * kEstTable;
+    if (n_keys) *n_keys = AVR_EST_KEYS;
     return AVR_OK;
 }
 
@@ -1123,6 +1230,36 @@ int avr_range_encode_chunked_device(int device, void *stream, const uint16_t *re
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_k2p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), plan->chunk_base,
                             plan->chunk_slice, plan->total_chunks, out_total, workspace, out, out_off, out_len, status));
+    return AVR_OK;
+}
+
+size_t avr_range_resolve_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan) {
+    if (!plan) return 0;
+    return avr::est_workspace_bytes(n_slices, n_groups, plan->total_chunks);
+}
+
+int avr_range_resolve_device(int device, void *stream, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins,
+                             size_t n_slices, const uint32_t *group_first, size_t n_groups, const uint8_t *est_in, uint8_t *est_out,
+                             const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, uint16_t *recs_out, int32_t *status) {
+    if (int rc = check_common(rec_off, n_bins, keys, n_slices)) return rc;
+    if (n_groups > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_groups out of range");
+    if (n_slices && (n_groups == 0 || n_groups > n_slices))
+        return fail(AVR_ERR_INVALID, "n_groups %zu: a batch of %zu slices has between 1 and %zu groups", n_groups, n_slices, n_slices);
+    if (n_slices && (!group_first || !recs_out || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice))) return fail(AVR_ERR_INVALID, "null plan pointer");
+    if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
+    if (workspace_bytes < avr::est_workspace_bytes(n_slices, n_groups, plan->total_chunks))
+        return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than avr_range_resolve_workspace_bytes()", workspace_bytes);
+    if (n_slices && recs_out == keys) return fail(AVR_ERR_INVALID, "recs_out must not alias keys");
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(recs_out)) & 15)
+        return fail(AVR_ERR_INVALID, "keys / recs_out not 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(est_in) | reinterpret_cast<uintptr_t>(est_out)) & 1)
+        return fail(AVR_ERR_INVALID, "est_in / est_out not 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AVR_ERR_INVALID, "workspace not 256-byte aligned");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_est_resolve(static_cast<hipStream_t>(stream), keys, rec_off, n_bins, uint32_t(n_slices), group_first,
+                                    uint32_t(n_groups), est_in, est_out, plan->chunk_base, plan->chunk_slice, plan->total_chunks,
+                                    workspace, recs_out, status));
     return AVR_OK;
 }
 

@@ -148,6 +148,12 @@ size_t k2p_workspace_bytes(size_t n_slices, uint32_t total_chunks, uint64_t out_
 hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
                       const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, uint64_t out_total,
                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);
+// the compress direction's estimators (avr_est.hip): key records -> K2 range records, per group of slices; never waits
+size_t est_workspace_bytes(size_t n_slices, size_t n_groups, uint32_t total_chunks);
+hipError_t launch_est_resolve(hipStream_t s, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                              const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in, uint8_t *est_out,
+                              const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, void *workspace,
+                              uint16_t *recs_out, int32_t *status);
 hipError_t launch_synth_slices(hipStream_t s, int workload, uint32_t scale, uint64_t seed, uint64_t first_slice,
                                int kind, uint32_t n_slices, const uint64_t *rec_off, uint16_t *recs,
                                uint8_t *init_states, uint32_t n_states);

@@ -173,7 +173,10 @@ class context_ids {
 // compress direction: every decoded bin becomes a range record (what encoder.put would have read)
 class compress_recorder {
   public:
-    explicit compress_recorder(h264_model *model) : model_(model) { model_->reset(); }  // recode.cpp:1162-1163
+    // key_mode (residual hooks off only): a record is the bin and the identity of its context, symbol | key << 1 -- what the
+    // decompress direction records -- and the estimator behind the key is looked up and updated on the device
+    // (AVR_KIND_RANGE_KEYS); the model is not touched (its state tracking is a no-op while coding_type stays PIP_UNKNOWN).
+    explicit compress_recorder(h264_model *model, bool key_mode = false) : model_(model), key_mode_(key_mode) { model_->reset(); }  // recode.cpp:1162-1163
 
     // compressor::cabac_decoder::execute_symbol (recode.cpp:1167-1180): the bins of a significance
     // map are held back until the block's nonzero count is known (QUEUE_MODE), everything else is
@@ -188,6 +191,7 @@ class compress_recorder {
         }
     }
     void begin_coding_type(CodingType ct, int zigzag_index, int param0, int param1) {   // :1201-1209
+        if (key_mode_) throw std::runtime_error("compress_recorder: key records know no coding types (residual hooks are on)");
         const bool begin_queue = model_->begin_coding_type(ct, zigzag_index, param0, param1);
         if (begin_queue && (ct == PIP_SIGNIFICANCE_MAP || ct == PIP_SIGNIFICANCE_EOB)) {
             if (queueing_ != PIP_UNKNOWN || !queue_.empty()) throw std::runtime_error("compress_recorder: nested queues are not supported");   // :1243-1245
@@ -225,9 +229,14 @@ class compress_recorder {
   private:
     // h264_symbol::execute (recode.cpp:1075-1103) with the coder call replaced by a record
     void execute(int symbol, int context) {
+        if (__builtin_expect(key_mode_, 0)) { execute_key(symbol, context); return; }   // off the path of the default mode
         if (model_->coding_type != PIP_SIGNIFICANCE_EOB) record(symbol, model_->get_model_key(context));   // :1080
         model_->update_state(symbol, context);                                          // :1094
         if (context == kKeyTerminate && symbol) finished_ = true;                       // :1099-1102
+    }
+    void execute_key(int symbol, int context) {                                         // key mode: the bin and its key, nothing else
+        recs_.push_back(uint16_t((symbol & 1) | (context << 1)));
+        if (context == kKeyTerminate && symbol) finished_ = true;
     }
     void record(int symbol, const model_key &key) {                                     // :823-827 inputs
         const h264_model::estimator *e = model_->lookup(key);
@@ -235,6 +244,7 @@ class compress_recorder {
     }
     struct queued { int symbol, context; };
     h264_model *model_;
+    bool key_mode_ = false;
     std::vector<uint16_t> recs_;
     std::vector<queued> queue_;                                                          // symbol_buffer, :1273
     CodingType queueing_ = PIP_UNKNOWN;

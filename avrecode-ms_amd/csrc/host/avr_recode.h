@@ -160,12 +160,17 @@ class compressor {                                       // recode.cpp:1109-1316
         d->decode_video(&h, [](void *o, uint8_t *buf, int size) { return static_cast<compressor *>(o)->read_packet(buf, size); }, this);
         cabac_contexts.clear();
     }
+    // The adaptive estimators on the device: the recorders write key records and the file's slices go into the batch as one group
+    // of AVR_KIND_RANGE_KEYS slices (fresh estimators: h264_model starts a file so).  Before prepare(); residual hooks off only.
+    void set_device_estimators(bool on) { device_estimators_ = on; }
     size_t pending_slices() const { return pending_.size(); }
     size_t pending_bins() const { size_t bins = 0; for (auto &p : pending_) bins += p.recs.size(); return bins; }
     void add_to(avr_batch *b) {                          // the slice indices the batch hands out are consecutive: the first one is kept
         first_in_batch_ = -1;
+        if (device_estimators_ && !pending_.empty()) gpu_check(avr_batch_begin_group(b, nullptr));
         for (auto &p : pending_) {
-            const int idx = avr_batch_add_slice_range(b, p.recs.data(), p.recs.size());
+            const int idx = device_estimators_ ? avr_batch_add_slice_range_keys(b, p.recs.data(), p.recs.size())
+                                               : avr_batch_add_slice_range(b, p.recs.data(), p.recs.size());
             gpu_check(idx);
             if (first_in_batch_ < 0) first_in_batch_ = idx;
             std::vector<uint16_t>().swap(p.recs);        // the batch has its copy
@@ -205,7 +210,7 @@ class compressor {                                       // recode.cpp:1109-1316
             if (block_ < 0) return;                      // skipped: hooks off for this slice (:1146-1152)
             c->out_.block[block_].has_size = true;       // :1154
             c->out_.block[block_].size = size;
-            recorder_.reset(new compress_recorder(&c->model_));   // :1161-1163
+            recorder_.reset(new compress_recorder(&c->model_, c->device_estimators_));   // :1161-1163
         }
         ~cabac_decoder() { if (recorder_) c_->pending_.push_back({block_, recorder_->records()}); }
         bool hooked() const { return block_ >= 0; }
@@ -290,6 +295,7 @@ class compressor {                                       // recode.cpp:1109-1316
 
     struct pending { int block; std::vector<uint16_t> recs; };
     int first_in_batch_ = -1;
+    bool device_estimators_ = false;
     std::string original_;
     int device_;
     int read_offset_ = 0, prev_coded_block_end_ = 0;

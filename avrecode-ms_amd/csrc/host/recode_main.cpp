@@ -14,6 +14,10 @@
 // Environment: AVR_DEVICE = HIP device index (default 0); AVR_MODEL_HOOKS=1 = the stream decoder also fires begin / end_sub_mb
 // and begin / end_coding_type around residual blocks (all eleven hooks of recode.cpp:219-235 live: the significance-map side of
 // h264_model), for compress AND decompress of the same file -- the reference's fork leaves those four uncalled, so off by default.
+// AVR_DEVICE_ESTIMATORS=1 = the compress direction records (bin, model key) and the GPU looks up and updates the adaptive
+// estimators (AVR_KIND_RANGE_KEYS, one group a file) where the host does it per bin otherwise; the .recode bytes are the same
+// either way.  Off by default.  No effect together with AVR_MODEL_HOOKS=1 (the significance-map keys are not among the 1026 the
+// device keeps), which the command says once on stderr.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +39,18 @@ using namespace avr;
 
 int device() { const char *d = getenv("AVR_DEVICE"); return d ? atoi(d) : 0; }
 bool model_hooks() { const char *d = getenv("AVR_MODEL_HOOKS"); return d && atoi(d) != 0; }
+bool device_estimators() {
+    static const bool on = [] {
+        const char *d = getenv("AVR_DEVICE_ESTIMATORS");
+        if (!d || atoi(d) == 0) return false;
+        if (model_hooks()) {
+            std::cerr << "AVR_DEVICE_ESTIMATORS has no effect with AVR_MODEL_HOOKS=1: the host resolves the estimators\n";
+            return false;
+        }
+        return true;
+    }();
+    return on;
+}
 
 std::string slurp(const std::string &path) {
     std::ifstream f(path, std::ios::binary);
@@ -46,6 +62,7 @@ std::string slurp(const std::string &path) {
 
 std::string compress_bytes(const std::string &original) {            // compressor::run, recode.cpp:1122-1132
     host::compressor c(original, device());
+    c.set_device_estimators(device_estimators());
     h264::h264_stream_decoder d;
     d.residual_hooks = model_hooks();
     return c.run(&d);
@@ -242,6 +259,7 @@ void perf_test_driver(const std::string &directory_path) {
     const unsigned hw = std::thread::hardware_concurrency();
     const unsigned threads = std::min<unsigned>(hw ? hw : 4, 32);
     shared_batch batch_in, batch_out;
+    const bool on_device = device_estimators();                      // read here, once, not in the files' threads
     for (size_t base = 0; base < files.size(); base += window) {
         const size_t n = std::min(window, files.size() - base);
         std::vector<file_job> jobs(n);
@@ -257,6 +275,7 @@ void perf_test_driver(const std::string &directory_path) {
                 dump_stream_info(j.path.string(), j.original, int(base + i), captured);
                 j.log_text = captured.str();
                 j.c.reset(new host::compressor(j.original, device()));
+                j.c->set_device_estimators(on_device);
                 h264::h264_stream_decoder dec;
                 dec.residual_hooks = model_hooks();
                 dec.dry_run_threads = 1;                             // the cores are taken by the files

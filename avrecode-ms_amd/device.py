@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 
-from . import KIND_CABAC, KIND_CABAC8, KIND_RANGE, MAX_STATES8, NOP_CABAC, NOP_RANGE, AvrError, SynthConfig, _check, lib
+from . import EST_KEYS, KIND_CABAC, KIND_CABAC8, KIND_RANGE, KIND_RANGE_KEYS, MAX_STATES8, NOP_CABAC, NOP_RANGE, AvrError, SynthConfig, _check, lib
 
 
 def synth_config(workload: int, scale_permille: int = 1000, first_slice: int = 0) -> SynthConfig:
@@ -150,6 +150,76 @@ class DeviceWorkload:
         w = cls(kind, device_index, n_bins, order, tile_off, tiles, init, n_states)
         w.rec_flat, w.rec_off = d_flat, d_off
         w.status.copy_(pack_status)
+        return w
+
+    @classmethod
+    def from_host_keys(cls, recs_list, group_first, tables=None, device_index=0, gap=0):
+        """KEY records (bin | model key << 1) from the host with their groups: group g = slices group_first[g] .. group_first[g + 1]
+        (len(group_first) = groups + 1), each group starting from tables[g] (EST_KEYS x 2 uint8 {pos, neg}) or, tables=None, fresh.
+        `gap`: groups of eight records left unused between slices.  The padding and the gaps hold 0xeeee (a malformed record:
+        the kernels must not read it as one).  resolve_range() gives the AVR_KIND_RANGE workload."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", device_index)
+        nb = np.array([len(r) for r in recs_list], dtype=np.int32)
+        rec_off = np.zeros(len(recs_list) + 1, dtype=np.int64)
+        rec_off[1:] = np.cumsum((nb.astype(np.int64) + 7) // 8 * 8 + 8 * gap)
+        flat = np.full(int(rec_off[-1]) + 8, 0xEEEE, dtype=np.uint16)
+        for i, r in enumerate(recs_list):
+            flat[rec_off[i]:rec_off[i] + len(r)] = r
+        with torch.cuda.device(dev):
+            est_in = None if tables is None else torch.from_numpy(np.ascontiguousarray(np.stack(tables), np.uint8)).to(dev)
+            return cls.from_device_keys(torch.from_numpy(flat.view(np.int16)).to(dev), torch.from_numpy(rec_off).to(dev),
+                                        torch.from_numpy(nb).to(dev), group_first, est_in, device_index)
+
+    @classmethod
+    def from_device_keys(cls, key_flat, rec_off, n_bins, group_first, est_in=None, device_index=0):
+        """The same from slice-major key records already on the device (a synthetic K1 record is a key record)."""
+        import numpy as np
+        import torch
+        dev = n_bins.device
+        order, tile_off = plan_tiles(n_bins)
+        tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
+        w = cls(KIND_RANGE_KEYS, device_index, n_bins, order, tile_off, tiles, None, 0)
+        w.key_flat, w.rec_off = key_flat, rec_off
+        w.group_first = torch.from_numpy(np.asarray(group_first, dtype=np.int32)).to(dev)
+        w.n_groups = w.group_first.numel() - 1
+        w.est_in = est_in
+        w.est_out = torch.empty(max(w.n_groups, 1) * EST_KEYS * 2, dtype=torch.uint8, device=dev)
+        w.rec_flat = torch.empty_like(key_flat)
+        return w
+
+    def resolve_keys(self):
+        """avr_range_resolve_device alone: the K2 records (slice-major, self.rec_off) of this key workload, the groups' tables
+        in self.est_out; enqueues and returns."""
+        import torch
+        if self.kind != KIND_RANGE_KEYS:
+            raise AvrError("not a workload of key records")
+        p = self._chunk_plan()
+        L = lib()
+        if "ws_est" not in p:
+            n = L.avr_range_resolve_workspace_bytes(self.n_slices, self.n_groups, ctypes.byref(p["plan"]))
+            p["ws_est"] = torch.empty(n + 256, dtype=torch.uint8, device=self.n_bins.device)
+            p["ws_est_bytes"] = n
+        _check(L.avr_range_resolve_device(
+            self.device_index, _stream_ptr(torch), self.key_flat.data_ptr(), self.rec_off.data_ptr(), self.n_bins.data_ptr(),
+            self.n_slices, self.group_first.data_ptr(), self.n_groups, self.est_in.data_ptr() if self.est_in is not None else None,
+            self.est_out.data_ptr(), ctypes.byref(p["plan"]), (p["ws_est"].data_ptr() + 255) // 256 * 256, p["ws_est_bytes"],
+            self.rec_flat.data_ptr(), self.status.data_ptr()))
+        return self.rec_flat
+
+    def resolve_range(self):
+        """The resolved AVR_KIND_RANGE workload on the device: the estimators resolved (resolve_keys) and the records packed into
+        tiles, its status carrying what the resolver found malformed.  encode() / encode_chunked() of the result code it."""
+        import torch
+        self.status.zero_()
+        recs = self.resolve_keys()
+        w = DeviceWorkload(KIND_RANGE, self.device_index, self.n_bins, self.order, self.tile_off, self.tiles, None, 0)
+        w.rec_flat, w.rec_off = recs, self.rec_off
+        w.status.copy_(self.status)
+        _check(lib().avr_pack_tiles_device(self.device_index, _stream_ptr(torch), KIND_RANGE, 0, recs.data_ptr(), self.rec_off.data_ptr(),
+                                           self.n_bins.data_ptr(), self.order.data_ptr(), self.n_slices, self.tile_off.data_ptr(),
+                                           self.tiles.data_ptr(), w.status.data_ptr()))
         return w
 
     @classmethod

@@ -33,6 +33,11 @@
  *       bit 0      bin value
  *       bits 1..7  pos, bits 8..14 neg : the {pos,neg} estimator of the bin's model key at
  *                  the moment it is coded (recode.cpp:823-827, 1064); p(1) = (range/(pos+neg))*pos
+ *   key record (compress direction before its estimators are resolved, AVR_KIND_RANGE_KEYS), uint16_t: the bits of the CABAC record
+ *       bit 0      bin value
+ *       bits 1..11 model key: 0..1023 a context id, AVR_SEL_BYPASS, AVR_SEL_TERMINATE -- the 1026 keys h264_model keeps in flat_[]
+ *                  (residual hooks off); bits 12..15 zero.  The device looks up and updates the key's {pos, neg} estimator
+ *                  (recode.cpp:823-827, 1037-1052) and makes the range record: the same two bytes feed both directions.
  *
  * Environment.  The library reads three variables, once per process; NONE of them can change a coded byte -- they pick
  * between mappings that produce the same bytes (tests/ run all of them against the oracle):
@@ -74,9 +79,12 @@ extern "C" {
  *                  only the padding past n_bins may hold it); a put_terminate(1) that is not the slice's last bin
  *   K1, one-byte   a selector in [n_states, 126); a put_terminate(1) that is not last; a rec_off that is not a multiple of 16
  *   K2             bit 15 set, or pos + neg = 0
+ *   key records    a bit of 12..15 set, or a key above AVR_SEL_TERMINATE.  The later slices of the record's GROUP have no defined
+ *                  estimators, so that slice AND EVERY LATER SLICE OF ITS GROUP come back AVR_SLICE_BAD_RECORD with length 0; earlier
+ *                  slices and other groups are coded.  (No rule about put_terminate(1): K2 has none.)
  * Enforced by the packers (avr_pack_tiles_device, avr_pack_tiles8_device, avr_pack_tiles8_narrow_device) with the tile coders behind them, by the K1p calls
  * (avr_cabac_encode_chunked_device and its hinted, second-pass and parts forms, avr_cabac8_encode_chunked_device,
- * avr_cabac_resolve_device), by K2p (avr_range_encode_chunked_device) and so by the batch API on either path: a slice's status
+ * avr_cabac_resolve_device), by K2p (avr_range_encode_chunked_device), by avr_range_resolve_device and so by the batch API on either path: a slice's status
  * does not depend on the path.  Precedence: AVR_SLICE_BAD_RECORD wins over AVR_SLICE_ZERO_PROB, AVR_SLICE_OVERFLOW and any
  * hand-over inside a path, wherever in the slice the bad record sits.  The slice-major serial entry points
  * (avr_cabac_encode_slices_device, avr_range_encode_slices_device) trust their input.  Resolved codes have no bad value. */
@@ -102,6 +110,8 @@ extern "C" {
 #define AVR_KIND_RANGE 1         /* K2: recoded_code::encoder    (recode.cpp:322-323)   */
 #define AVR_KIND_CABAC_CODES 2   /* K1 from resolved codes: one byte per bin, see avr_batch_add_slice_codes */
 #define AVR_KIND_CABAC8 3        /* K1 from ONE-BYTE records (bin, dense selector), see avr_batch_add_slice_cabac8 */
+#define AVR_KIND_RANGE_KEYS 4    /* K2 from KEY records (bin, model key): the estimators are resolved on the device, see avr_batch_begin_group */
+#define AVR_EST_KEYS 1026        /* estimators to a table: keys 0 .. AVR_SEL_TERMINATE */
 
 /* One-byte K1 records (AVR_KIND_CABAC8): bit 0 = the bin, bits 1..7 = a dense selector -- 0 .. 125 the slice's contexts in the
  * order the recorder met them (its ids are dense by first appearance already: INTEGRATION.md), AVR_SEL8_BYPASS, AVR_SEL8_TERMINATE.
@@ -159,8 +169,23 @@ int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n);
  * terminate comes back as AVR_SLICE_BAD_RECORD. */
 int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n,
                                const uint8_t *init_states, size_t n_states);
-/* Zero-copy form of the four calls above: room for a slice of n elements (uint16_t records for AVR_KIND_CABAC /
- * AVR_KIND_RANGE, uint8_t codes for AVR_KIND_CABAC_CODES, uint8_t records for AVR_KIND_CABAC8) in the batch's pinned staging buffer, which the H2D copy
+/* K2 from KEY records (AVR_KIND_RANGE_KEYS, above): the compress-direction adapter records what the decompress-direction one
+ * records -- the bin and the identity of its context -- and the device resolves the adaptive {pos, neg} estimators.
+ * Estimators belong to a GROUP: a run of consecutive slices, in the order they are added, that share one table of AVR_EST_KEYS
+ * estimators (a file's slices).  avr_batch_begin_group: the slices added from here on form a new group, which starts from fresh
+ * estimators {1, 1} (est_in NULL) or from est_in: AVR_EST_KEYS pairs of bytes {pos, neg}, each with pos >= 1, neg >= 1 and
+ * pos + neg <= 0x60 (else AVR_ERR_INVALID).  Returns the group's index.  The first slice of a batch opens a fresh group if none
+ * was begun; a batch of this kind holds only this kind.  avr_batch_submit runs the resolver (avr_range_resolve_device) and then the
+ * K2 path it would choose for the same slices as AVR_KIND_RANGE; it does not wait.  Bytes, lengths and statuses are those of an
+ * AVR_KIND_RANGE batch fed the resolved records.  avr_batch_get_estimators: the group's table after its last bin, in the layout
+ * begin_group takes (valid until the next reset / destroy; undefined for a group with a malformed record).  A group split over two
+ * batches -- the second begun from the first one's table -- gives the bytes and the table of the unsplit group.
+ * avr_multi has no key records: a group must stay on one device. */
+int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in);
+int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n);
+int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg, size_t *n_keys);
+/* Zero-copy form of the calls above: room for a slice of n elements (uint16_t records for AVR_KIND_CABAC /
+ * AVR_KIND_RANGE / AVR_KIND_RANGE_KEYS, uint8_t codes for AVR_KIND_CABAC_CODES, uint8_t records for AVR_KIND_CABAC8) in the batch's pinned staging buffer, which the H2D copy
  * reads directly; the caller writes exactly n elements to *buffer before avr_batch_submit / avr_batch_run (the padding
  * after them is already in place).  init_states / n_states as for avr_batch_add_slice_cabac (copied now), ignored
  * for the other kinds.  A recorder that appends here saves one pass over its records.  Returns the slice index. */
@@ -188,9 +213,10 @@ int avr_batch_get_states(avr_batch *b, size_t slice, const uint8_t **states, siz
  * batch uses (as the sampled census saw them) -- except for a one-byte (AVR_KIND_CABAC8) batch, on either path: it takes no census,
  * so [1] is 0 and [2] is the batch's declared n_states, every one of which has a row; [3] bit 0 = avr_batch_wait found the guess
  * too small and ran the batch again, bit 1 = it ran the second pass of the intra-slice parallel path (slices with a bin in a context
- * the sampled census missed).  CABAC-record batches; zeros otherwise. */
+ * the sampled census missed).  CABAC-record batches; zeros otherwise, except that [0] is also 1 when a K2 batch ran K2p (a test of key
+ * records sees through it which K2 path coded the batch). */
 int avr_batch_run_info(avr_batch *b, uint32_t info[4]);
-/* milliseconds of the last run: [0] H2D, [1] pack kernel, [2] encode kernel, [3] D2H */
+/* milliseconds of the last run: [0] H2D, [1] pack kernel (for key records: the estimator resolver and the pack kernel), [2] encode kernel, [3] D2H */
 int avr_batch_timings(avr_batch *b, float ms[4]);
 
 /* ------------------------------------------------------------------ one batch over several GPUs
@@ -441,6 +467,34 @@ int avr_range_encode_chunked_device(int device, void *stream,
                                     const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
                                     uint8_t *out, const uint64_t *out_off, uint64_t out_total,
                                     uint32_t *out_len, int32_t *status);
+
+/* The compress direction's estimators on the device (avrecode-ms_amd/csrc/avr_est.h): KEY records in, K2 range records out.
+ * keys / recs_out: the slice-major layout above with the same rec_off (16-byte aligned, recs_out must not alias keys).  recs_out
+ * gets bin | pos << 1 | neg << 8 for [0, n_bins) of every slice and AVR_NOP_RANGE from there to the slice's next multiple of 8 records
+ * (what lies between that and the next slice's rec_off is not touched), so it goes straight into
+ * avr_pack_tiles_device(AVR_KIND_RANGE) + avr_range_encode_tiles_device or into avr_range_encode_chunked_device.
+ *   group_first   n_groups + 1 entries on the DEVICE, group g = slices [group_first[g], group_first[g + 1]), group_first[0] = 0,
+ *                 non-decreasing, group_first[n_groups] = n_slices; trusted like rec_off.  1 <= n_groups <= n_slices.
+ *   est_in        n_groups tables of AVR_EST_KEYS byte pairs {pos, neg} (2-byte aligned; trusted: pos, neg >= 1, pos + neg <= 0x60),
+ *                 or NULL: every group starts fresh {1, 1}
+ *   est_out       the same layout, every group's table after its last bin, or NULL: not wanted
+ *   plan          chunk_base, chunk_slice and total_chunks are used
+ *   workspace     avr_range_resolve_workspace_bytes(...) bytes, 256-byte aligned:
+ *                 align256(4 n_slices) + align256(4 n_groups) + 2 ceil(total_chunks / 16) * 6168
+ *   status        in/out, zero-filled before (or a packer's / an earlier call's): a malformed record (rule above) sets
+ *                 AVR_SLICE_BAD_RECORD for its slice and every later slice of the group; the records of such slices are undefined
+ * The call enqueues on `stream` and returns: it never waits for the device, whatever the shape -- groups of one short slice each and
+ * one group of all slices run through the same kernels (a group inside one window of 16 chunks is resolved by one wave start to end;
+ * a longer one in rows of a window each, with one short chain per key over the rows).  Refused before anything touches a device
+ * (AVR_ERR_INVALID): a null pointer with n_slices > 0, n_groups of 0 or above n_slices, a null plan, a workspace smaller than
+ * avr_range_resolve_workspace_bytes, recs_out == keys, misaligned keys / recs_out / est_in / est_out / workspace. */
+size_t avr_range_resolve_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan);
+int avr_range_resolve_device(int device, void *stream,
+                             const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins, size_t n_slices,
+                             const uint32_t *group_first, size_t n_groups,
+                             const uint8_t *est_in, uint8_t *est_out,
+                             const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
+                             uint16_t *recs_out, int32_t *status);
 
 /* The two stages of K1p on their own.
  *
