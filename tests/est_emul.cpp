@@ -236,7 +236,8 @@ struct Emul {
 extern "C" {
 
 // The resolver of avr_range_resolve_device with chunks of chunk_bins bins and windows of `window` chunks.  info[0] = chunks,
-// info[1] = rows that a spanning group used, info[2] = groups that span.  Returns 0.
+// info[1] = rows that a spanning group used, info[2] = groups that span, info[3] = block heads beyond a group's first block
+// (kb > 0: the blocks that read the aggregates of the blocks before them).  Returns 0.
 int est_emul_resolve(const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
                      const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in, uint8_t *est_out,
                      uint32_t chunk_bins, uint32_t window, uint16_t *recs_out, int32_t *status, uint32_t *info) {
@@ -268,12 +269,15 @@ int est_emul_resolve(const uint16_t *keys, const uint64_t *rec_off, const uint32
     for (uint32_t w = n_windows; w-- > 0;) e.emit(w);             // any order: a window's walk depends on no other window's
     for (uint32_t i = 0; i < n_slices; i++) if (i >= e.group_bad[e.slice_group[i]]) status[i] = 3;
     if (info) {
-        info[0] = e.total_chunks; info[1] = info[2] = 0;
+        info[0] = e.total_chunks; info[1] = info[2] = info[3] = 0;
         for (uint32_t w = 0; w < n_windows; w++) {
             Row rows2[2];
+            BlockHead heads[2];
             e.rows_of(w, rows2);
+            window_block_heads(w, window, rows2, heads);
             info[1] += (rows2[0].c0 < rows2[0].c1) + (rows2[1].c0 < rows2[1].c1);
             info[2] += rows2[1].c0 < rows2[1].c1;
+            info[3] += (heads[0].any && heads[0].kb > 0) + (heads[1].any && heads[1].kb > 0);
         }
     }
     return 0;

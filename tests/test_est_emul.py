@@ -146,6 +146,47 @@ def test_groups_without_slices_and_empty_batches(emul):
     assert np.array_equal(est_out[0], tables[0]) and np.array_equal(est_out[2], tables[2])
 
 
+@pytest.mark.parametrize("name", sorted(rk.ROW_BLOCK_CASES))
+def test_row_block_inputs_reach_the_blocks_they_are_meant_to(emul, name):
+    """The inputs of tests/test_gpu_range_keys_scale.py at the device's sizes: each makes the rows, the blocks beyond a group's first and
+    the windows with two block heads it is there for (by the definitions, range_keys.row_plan, and as the emulation counts them), and
+    the emulation resolves it exactly."""
+    slices, gf = rk.row_block_case(name)
+    rows, later, two = rk.ROW_BLOCK_PLANS[name]
+    plan = rk.row_plan(slices, gf)
+    assert (plan["rows"], plan["later_blocks"], plan["two_head_windows"]) == (rows, later, two)
+    assert name.startswith("rows64") or later > 0                  # (64 rows: the largest group of one block)
+    rng = np.random.default_rng(77)
+    info, _ = check(emul, slices, gf, rk.CHUNK, rk.WINDOW, [rk.random_table(rng) for _ in range(len(gf) - 1)], gap=1)
+    assert info == [plan["chunks"], plan["total_rows"], len(rows), later]
+
+
+def test_plain_compiled_rule_equals_the_python_rule():
+    """tests/est_plain.cpp (the reference of the full-size GPU comparisons) against range_keys.resolve: random streams in every mix,
+    fresh and given tables, empty slices and groups, gaps, malformed records of every kind at any place."""
+    rng = np.random.default_rng(4242)
+    for k in range(40):
+        n_slices = int(rng.integers(1, 14))
+        mode = ("skew", "flat", "one")[k % 3]
+        slices = [rk.random_keys(rng, 0 if rng.random() < 0.2 else int(rng.integers(1, 4000)), mode) for _ in range(n_slices)]
+        cuts = sorted(rng.integers(0, n_slices + 1, int(rng.integers(0, 5))).tolist())
+        gf = [0] + cuts + [n_slices]                                 # (a repeated cut: a group without slices)
+        tables = None if k % 2 else [rk.random_table(rng) for _ in range(len(gf) - 1)]
+        if k % 4 >= 2:
+            for _ in range(int(rng.integers(1, 3))):
+                i = int(rng.integers(0, n_slices))
+                if slices[i].size:
+                    slices[i][int(rng.integers(0, slices[i].size))] = (0x1000, 0x8001, 1026 << 1, (2047 << 1) | 1)[int(rng.integers(0, 4))]
+        want, want_tabs = rk.resolve(slices, gf, tables)
+        recs, rec_off, n_bins = rk.layout(slices, gap=k % 3)
+        out, status, est_out = rk.plain_resolve(recs, rec_off, n_bins, gf, None if tables is None else np.stack(tables))
+        exp, mask = rk.expected_layout(want, rec_off, n_bins)
+        assert np.array_equal(out[mask], exp[mask]) and (out[~mask] == 0xABCD).all(), f"round {k}"
+        assert status.tolist() == [rk.BAD_RECORD if w is None else 0 for w in want]
+        for g, t in enumerate(want_tabs):
+            assert np.array_equal(est_out[g], t if t is not None else np.full((rk.N_KEYS, 2), 0xCC, np.uint8)), f"round {k} group {g}"
+
+
 def test_workspace_is_small_for_many_one_slice_groups(emul):
     """A batch of 1 Mi one-slice groups pays far less than one estimator table (1026 x 2 bytes) per group."""
     n = 1 << 20
