@@ -539,3 +539,113 @@ int t_roundtrip(const uint8_t *file, size_t file_len, size_t n_slices, const uin
 }
 
 }  // extern "C"
+
+// ---- what the parser did, bin by bin (tests/test_h264_walker.py): every slice of a file through slice_parser over the build's
+// own CABAC engine, with a bin source that writes down the REAL ctxIdx (state - states_base) of every context-coded bin -- the
+// recorders above only number contexts by first appearance.  Parameter sets and slice headers are read as pass 1 of
+// h264_stream_decoder::decode_video reads them (x264's SEI included); nothing of the product headers is changed for this.
+namespace {
+struct trace_bins {
+    avr::h264::engine_bins e;
+    const uint8_t *base;
+    std::vector<uint16_t> *log;
+    trace_bins(const uint8_t *buf, size_t size, const uint8_t *states_base, std::vector<uint16_t> *out) : e(buf, size), base(states_base), log(out) {}
+    int get(uint8_t *state) { const int b = e.get(state); log->push_back(uint16_t(((state - base) << 1) | b)); return b; }
+    int bypass() { const int b = e.bypass(); log->push_back(uint16_t((1024 << 1) | b)); return b; }
+    int terminate() { const int b = e.terminate() != 0; log->push_back(uint16_t((1025 << 1) | b)); return b; }
+};
+struct trace_args {
+    const uint8_t *file; size_t len; uint16_t *recs; size_t recs_cap; uint64_t *rec_end; int32_t *fields; char *reasons; size_t reasons_cap;
+    size_t slice_cap; uint64_t *n_slices;
+};
+enum { kTraceFields = 16 };
+int trace_run(void *p) {
+    using namespace avr::h264;
+    trace_args *a = static_cast<trace_args *>(p);
+    const std::vector<uint8_t> data(a->file, a->file + a->len);
+    std::vector<nal_ref> nals;
+    if (!mp4_nals(data, &nals)) nals = annexb_nals(data);
+    std::vector<sps_t> sps(32);
+    std::vector<pps_t> pps(256);
+    int x264_build = -1, slice_no = 0;
+    std::vector<mb_info> mbs;
+    std::vector<uint16_t> log;
+    std::string reasons;
+    size_t n = 0, at = 0;
+    for (const nal_ref &nal : nals) {
+        if (nal.size < 2) continue;
+        const uint8_t header = data[nal.offset];
+        const int type = header & 31, ref_idc = (header >> 5) & 3;
+        if (type != 1 && type != 5 && type != 6 && type != 7 && type != 8) continue;
+        const std::vector<uint8_t> rbsp = unescape(&data[nal.offset + 1], nal.size - 1);
+        if (type == 6) {
+            static const char tag[] = "x264 - core ";
+            const size_t k = sizeof tag - 1;
+            for (size_t i = 0; i + k < rbsp.size(); i++)
+                if (!memcmp(&rbsp[i], tag, k)) {
+                    int build = 0;
+                    for (size_t j = i + k; j < rbsp.size() && rbsp[j] >= '0' && rbsp[j] <= '9' && build < 100000; j++) build = build * 10 + (rbsp[j] - '0');
+                    x264_build = build;
+                    break;
+                }
+            continue;
+        }
+        if (type == 7 || type == 8) {
+            try { if (type == 7) parse_sps(rbsp, sps.data()); else parse_pps(rbsp, pps.data()); } catch (const bad_stream &) {}
+            continue;
+        }
+        if (n >= a->slice_cap) throw std::runtime_error("t_parse_trace: more slices than room for them");
+        int32_t *f = a->fields + kTraceFields * n;
+        std::fill(f, f + kTraceFields, 0);
+        std::string why;
+        log.clear();
+        try {
+            slice_header sh = parse_slice_header(rbsp, type, ref_idc, sps.data(), pps.data());
+            if (sh.data_offset >= rbsp.size()) throw bad_stream("slice without data");
+            sh.x264_old_444_cbf = sh.chroma_array_type == 3 && x264_build >= 0 && x264_build < 151;
+            const int32_t head[kTraceFields] = {0, sh.first_mb, sh.type, sh.qp, sh.cabac_init_idc, sh.refs[0], sh.refs[1], int32_t(sh.data_offset),
+                                                sh.chroma_array_type, sh.transform_8x8_mode, sh.direct_8x8_inference, sh.width_mbs, sh.height_mbs,
+                                                sh.x264_old_444_cbf, 0, 0};
+            std::copy(head, head + kTraceFields, f);
+            const size_t n_mbs = size_t(sh.width_mbs) * sh.height_mbs;
+            if (mbs.size() != n_mbs) mbs.assign(n_mbs, mb_info());
+            uint8_t states[1024];
+            const uint8_t *payload = rbsp.data() + sh.data_offset;
+            const size_t size = rbsp.size() - sh.data_offset;
+            trace_bins bins(payload, size, states, &log);
+            slice_parser<trace_bins> parser(bins, sh, states, mbs, ++slice_no, model_hooks());
+            f[14] = parser.run();
+            const size_t read = bins.e.d.bit_position();          // as h264_stream_decoder::ends_cleanly: the stop bit, in the last byte
+            f[15] = read > 0 && read <= size * 8 && ((payload[(read - 1) >> 3] >> (7 - ((read - 1) & 7))) & 1) && ((read - 1) >> 3) == size - 1;
+        } catch (const unsupported &e) { f[0] = 1; why = e.what(); }
+        catch (const std::exception &e) { f[0] = 2; why = e.what(); }
+        if (at + log.size() > a->recs_cap) throw std::runtime_error("t_parse_trace: more records than room for them");
+        std::copy(log.begin(), log.end(), a->recs + at);
+        at += log.size();
+        a->rec_end[n++] = at;
+        reasons += why + "\n";
+    }
+    *a->n_slices = n;
+    if (reasons.size() + 1 > a->reasons_cap) throw std::runtime_error("t_parse_trace: reasons do not fit");
+    memcpy(a->reasons, reasons.c_str(), reasons.size() + 1);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+// Per slice (stream order): fields[16 i ..] = status (0 parsed, 1 unsupported, 2 failed), first_mb, type (0 P, 1 B, 2 I), qp, cabac_init_idc,
+// refs[0], refs[1], data_offset, chroma format, transform_8x8_mode, direct_8x8_inference, width, height in macroblocks, x264_old_444_cbf,
+// macroblocks parsed, payload ended cleanly; recs[rec_end[i-1] .. rec_end[i]) = (ctxIdx | 1024 bypass | 1025 terminate) << 1 | bin of every
+// bin read (what was read before a refusal included); reasons = one line per slice, empty when parsed.
+int t_parse_trace(const uint8_t *file, size_t len, uint16_t *recs, size_t recs_cap, uint64_t *rec_end, int32_t *fields, char *reasons,
+                  size_t reasons_cap, size_t slice_cap, uint64_t *n_slices, char *err, size_t err_cap) {
+    trace_args a{file, len, recs, recs_cap, rec_end, fields, reasons, reasons_cap, slice_cap, n_slices};
+    return guarded(trace_run, &a, err, err_cap);
+}
+
+// The parser's initial context states for one slice (avr_h264_tables.h): 1024 bytes of 2 * pStateIdx + valMPS.  The walker of
+// tests/h264_walker.py has no copy of Tables 9-12 .. 9-33 of its own and takes them from here.
+void t_init_states(int intra, int slice_qp, int idc, uint8_t *out) {
+    for (int c = 0; c < 1024; c++) out[c] = avr::h264::init_state(c, intra != 0, slice_qp, idc);
+}
+}  // extern "C"
