@@ -49,8 +49,8 @@ struct TestHooks {
     uint32_t k1_words8;              // one-lane-per-slice K1: the output in 8-byte stores (rounds 1-3), not 16-byte ones
     uint32_t k1_waves;               // one-lane-per-slice K1: waves to a workgroup (0 = the built-in count)
     uint32_t k2p_wave;               // K2p pass 1: 1 = a wave per slice, 2 = a lane per slice, 3 = a lane per slice and a wave each for the longest (0 = by slice count)
-    uint32_t k1p_keep_retry;         // K1p from resolved codes: the slices phase D hands over keep AVR_SLICE_RETRY_SERIAL (no serial kernel after it), so a
-                                     // test sees which slices phase D coded itself
+    uint32_t k1p_keep_retry;         // K1p (every form): the slices that leave the parallel path -- declined by the scheme, handed over by phase D -- keep
+                                     // AVR_SLICE_RETRY_SERIAL (no serial kernel after it), so a test sees which slices phase D coded itself
 };
 #ifdef AVR_TEST_HOOKS
 TestHooks &test_hooks();

@@ -1729,7 +1729,7 @@ static hipError_t k1p_pass(hipStream_t s, const Plan &p, uint32_t n_slices, cons
     if (e != hipSuccess) return e;
     w += resolve_ws_bytes(n_slices, n_states, pl);
     e = launch_code(s, p, n_slices, pl, w, res, kMaxStretch, out, out_off, out_len, status, st, true);
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;    // (test hook: the hand-overs stay visible, uncoded)
     // slices the scheme declined (status AVR_SLICE_RETRY_SERIAL) are coded by the serial kernel
     return launch_cabac_encode(false, s, p.recs, p.rec_off, p.n_bins, nullptr, n_slices, init_states, n_states, out, out_off,
                                out_len, status, nullptr, AVR_SLICE_RETRY_SERIAL);
@@ -1817,7 +1817,7 @@ hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_
     if (e != hipSuccess) return e;
     w += resolve_ws_bytes(n_slices, n_states, pl);
     e = launch_code(s, p, n_slices, pl, w, res, kMaxStretch, out, out_off, out_len, status, st, true);
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
     hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((n_slices + 63) / 64), dim3(64), 0, s, res, nullptr, pl->chunk_base, n_bins,
                        nullptr, n_slices, out, out_off, out_len, status, int32_t(AVR_SLICE_RETRY_SERIAL));
     return hipGetLastError();

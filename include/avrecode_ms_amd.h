@@ -254,6 +254,12 @@ int avr_multi_load(avr_multi *m, uint64_t *bins_per_device);
  * codes (avr_cabac_encode_resolved_device / _codes_device and every K2 entry: no wait).  avr_cabac_encode_tiles_device blocks behind
  * avr_pack_tiles8_device's two-byte tiles as behind any other.
  * These are what the batch API is made of and what bench.py times with inputs already resident in HBM (its K1 steps: the hinted calls).
+ * MEMORY: what a workspace (or a code buffer, or an output array) holds on entry is arbitrary -- no call needs it cleared, and a workspace may
+ * be handed from one batch to another as it stands.  A call writes nothing outside [workspace, workspace + workspace_bytes) and the documented
+ * extents of its output arrays: out[out_off[i] .. out_off[i] + out_len[i]) of every slice (nothing else of `out`, not a byte past out_off[n_slices]),
+ * n_slices entries of out_len and status, n_slices * n_states final states, res_total + 32 bytes of codes, tile_off[n_tiles] * 16 bytes of tiles.
+ * STREAMS: whatever a call runs on streams of its own is joined back: work enqueued on `stream` behind the call sees all of its results
+ * and may overwrite its workspace (tests/test_gpu_workspace.py holds the library to all three).
  * ONE THREAD PER STREAM: the library keeps a few kilobytes of scratch (and, for the chunked K2, a second stream with its
  * events) per (device, stream); a call's kernels find them there, so two host threads must not enqueue on the same stream
  * at the same time.  What is kept for a batch's own stream is released by avr_batch_destroy.
