@@ -382,6 +382,14 @@ AVR_HD uint32_t ref_digits(uint32_t t) { return t <= 21 ? 0 : (t - 21 + 15) / 16
 //   void flush()                                   no store() follows: whatever the adder holds back goes out
 // A stretch shares its first two digits with the windows of earlier stretches and its final
 // window (two digits) with later ones; everything between is its own (argument in DESIGN.md).
+// An adder may take the stretch's digits itself instead of one store() / add() each, by offering (kStaged = true)
+//   void begin(uint32_t g0)                        the index of the stretch's first digit
+//   void push(uint32_t i, uint32_t v)              digit i, after digit i - 1; one lane's call, anywhere
+//   void push2(uint32_t nd, uint32_t a, uint32_t b)   the next nd = 0, 1 or 2 digits: a, then b; unconditional work only
+//   void look(uint32_t i)                          after a push2, i = index of the next digit: the place to make room, reached
+//                                                  by a wave's lanes together; at most one push2 between two looks
+//   void flush(uint32_t i)                         in place of flush()
+// and has to bring about the same sums: add for digits g0 and g0 + 1, exclusive positions after them.
 //
 // The coder is kept in normalised form: R in [256, 511] as in B1, and low as a 64-bit integer L2 in
 // units of half the reference's scale, i.e. with the reference's range R << e (arithmetic_code.h:107-114,
@@ -393,6 +401,16 @@ AVR_HD uint32_t ref_digits(uint32_t t) { return t <= 21 ? 0 : (t - 21 + 15) / 16
 // bin, at the same place for every lane of a wave -- where the reference's form has one lane or
 // another emitting at almost every bin.  A digit taken late has the carries of the bins in between
 // already in it (it can reach 2^17); the sums are integers and phase D carries them on.
+//
+// The look of the bulk loop has no loop and no branch of its own.  Four bins shift by at most 28 and a look leaves
+// sp <= 14, so with s1 = sp + 1 in [-6, 43] there are nd = max(0, s1 >> 4) = 0, 1 or 2 digits due, and for nd > 0 the bits
+// that stay are the low ks = 16 + (s1 & 15) = s1 - 16 (nd - 1).  Both digits come off in one shift, t = L2 >> ks: the
+// older one is t >> 16 with every carry above it (nd == 2) or t itself (nd == 1), the younger t & 0xffff.  What stays fits
+// 32 bits: for nd > 0 it is below 2^31, and for nd == 0 the coder's interval [L2, L2 + 2 R) lies inside the one the last
+// look left, below 2^(16 + s1') + 2^10 with s1' >= 0, scaled by the d = s1 - s1' <= 15 shifts since: L2 < 2^(s1 + 16) +
+// 2^(10 + d) < 2^32 (before the stretch's first digit L2 + 2 R <= 2 * 510 << d with d <= s1 + 6 <= 21).
+template <class A, class = void> struct adder_is_staged { static constexpr bool value = false; };
+template <class A> struct adder_is_staged<A, decltype(void(A::kStaged))> { static constexpr bool value = A::kStaged; };
 template <class Src, class Adder>
 AVR_HD void c_stretch_in(const Src &src, const Stretch &st, const Entry &en, uint32_t chunk,
                          const CodeEntryC *codes, Adder &S) {
@@ -403,6 +421,8 @@ AVR_HD void c_stretch_in(const Src &src, const Stretch &st, const Entry &en, uin
     uint64_t L2 = 0;
     int sp = int(phase) - 7;                               // e = 22 - phase at the start (cabac_code.h:30 shifted onto the digit grid)
     uint32_t j = 0;                                        // digits produced
+    constexpr bool staged = adder_is_staged<Adder>::value;
+    if constexpr (staged) S.begin(g0);
     auto bin_e = [&](const CodeEntryC &e) {
         uint32_t v;
         const uint32_t sh = step_range_c(e, &R, &v);
@@ -410,14 +430,29 @@ AVR_HD void c_stretch_in(const Src &src, const Stretch &st, const Entry &en, uin
         sp += int(sh);
     };
     auto bin = [&](uint32_t c) { bin_e(codes[c]); };
+    auto put = [&](uint32_t d) {                           // the stretch's next digit
+        if constexpr (staged) S.push(g0 + j, d);
+        else if (j < 2) S.add(g0 + j, d);
+        else S.store(g0 + j, d);
+        j++;
+    };
     auto digits = [&]() {                                  // every digit that is due, oldest (topmost) first
         while (sp >= 15) {
             const uint32_t d = uint32_t(L2 >> (sp + 1));
             L2 &= (uint64_t(2) << sp) - 1;
-            if (j < 2) S.add(g0 + j, d); else S.store(g0 + j, d);
-            j++;
+            put(d);
             sp -= 16;
         }
+    };
+    auto digits2 = [&]() {                                 // the same after four bins of the bulk: see above
+        const int s1 = sp + 1;
+        const uint32_t nd = uint32_t(s1 > 0 ? s1 : 0) >> 4, ks = 16 + (uint32_t(s1) & 15u);
+        const uint64_t t = L2 >> ks;
+        const uint32_t a = nd == 2 ? uint32_t(t >> 16) : uint32_t(t), b = uint32_t(t) & 0xffffu;
+        L2 = uint32_t(L2) & (nd ? (1u << ks) - 1 : ~0u);
+        sp -= int(16 * nd);
+        if constexpr (staged) { S.push2(nd, a, b); j += nd; S.look(g0 + j); }
+        else { if (nd) put(a); if (nd == 2) put(b); }
     };
     const uint32_t to = st.end;
     if (from < to) {
@@ -425,7 +460,7 @@ AVR_HD void c_stretch_in(const Src &src, const Stretch &st, const Entry &en, uin
             CodeEntryC e[4];
             code_entries4(codes, d, e);
             bin_e(e[0]); bin_e(e[1]); bin_e(e[2]); bin_e(e[3]);
-            digits();
+            digits2();
         };
         auto group16 = [&](const U4 &v) { four(v.x); four(v.y); four(v.z); four(v.w); };
         // code by code up to a 16-byte boundary, 16-byte groups up to a cache line, then lines, and back down
@@ -448,7 +483,8 @@ AVR_HD void c_stretch_in(const Src &src, const Stretch &st, const Entry &en, uin
         for (; base + 16 <= to; base += 16) group16(src.load16(base));
         if (base < to) for_codes_in(src, base, to, [&](uint32_t, uint32_t c) { bin(c); digits(); return false; });
     }
-    S.flush();
+    if constexpr (staged) S.flush(g0 + j);
+    else S.flush();
     // what is left is the coder's window: the top of digit g0 + j (with any carry) and 15 - e bits of the next
     if (sp >= 0) {
         S.add(g0 + j, uint32_t(L2 >> (sp + 1)));

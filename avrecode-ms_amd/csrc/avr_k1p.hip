@@ -1259,35 +1259,71 @@ __global__ __launch_bounds__(256) void k_k1p_b2(Plan p, const int32_t *status, c
 
 // A stretch's own digit sums go out in aligned 16-byte blocks of four: a lane's stretch is somewhere of its own in the slice's
 // sums, so a 4-byte store per digit is a partial cache line per digit per lane (round 2: 487 MB written for 62 MB of sums).
+//
+// The digits are staged (avr_k1p.h, c_stretch_in) in LDS: kRing dwords per lane, slot s of lane l of wave w at word
+// (w * kRing + s) * 64 + l, so whatever slots a wave's lanes are at, they hit 64 different banks.  Taking a look's digits
+// is two unconditional writes, at slots cnt and cnt + 1 (whichever of them is not due lands in a slot that is free and is
+// written over by the next look), and cnt += nd.  The staged digits go out where the wave's lanes are together: when the look's
+// ballot finds a lane with kFull or more, and at the stretch's end.  kFull from the worst case, not the average: a look
+// adds at most two digits (four bins, seven shifts each) and a drain leaves at most three (an incomplete block), so a look
+// leaves cnt <= kFull - 1; a push() of the code-by-code head and tail, which drains for itself from kFull on, leaves cnt <=
+// kFull; so the two writes of the next look reach slot kFull + 1 = kRing - 1 at the most.  A lane at the top rate (six shifts
+// a bin) drains the wave every fifth look or so while its neighbours' slots are empty; on a video stream it is every 150 bins or so.
+constexpr uint32_t kRing = 16, kFull = kRing - 2;
 struct DeviceAdder {
+    static constexpr bool kStaged = true;
     uint32_t *S;
-    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0, have = 0, blk = 0;  // the block being filled: its digits, which of them are in (bits), its first index
-    __device__ __forceinline__ void store(uint32_t i, uint32_t v) {       // consecutive i
-        const uint32_t a = (uint32_t(reinterpret_cast<uintptr_t>(S) >> 2) + i) & 3u;     // where the digit sits in its aligned 16 bytes
-        if (have == 0) blk = i - a;
-        b0 = a == 0 ? v : b0; b1 = a == 1 ? v : b1; b2 = a == 2 ? v : b2; b3 = a == 3 ? v : b3;
-        have |= 1u << a;
-        if (a == 3) {
-            if (have == 15u) *reinterpret_cast<uint4 *>(S + blk) = make_uint4(b0, b1, b2, b3);
-            else flush();
-            have = 0;
-        }
+    uint32_t *ring;                                              // the lane's slot 0
+    uint32_t g0 = 0, cnt = 0;                                    // the stretch's first digit; digits staged: slot s holds digit (next) - cnt + s
+    __device__ __forceinline__ void begin(uint32_t g) { g0 = g; }
+    __device__ __forceinline__ void push2(uint32_t nd, uint32_t a, uint32_t b) {
+        ring[cnt * 64] = a;
+        ring[cnt * 64 + 64] = b;
+        cnt += nd;
     }
-    __device__ void flush() {
-        if (have & 1u) S[blk] = b0;
-        if (have & 2u) S[blk + 1] = b1;
-        if (have & 4u) S[blk + 2] = b2;
-        if (have & 8u) S[blk + 3] = b3;
-        have = 0;
+    __device__ __forceinline__ void look(uint32_t i) { if (__ballot(cnt >= kFull) != 0) drain(i, false); }
+    __device__ __forceinline__ void push(uint32_t i, uint32_t v) {      // head and tail of a stretch, code by code
+        if (cnt >= kFull) drain(i, false);
+        ring[cnt * 64] = v;
+        cnt++;
+    }
+    __device__ __forceinline__ void flush(uint32_t i) { drain(i, true); }
+    // Digits i - cnt .. i - 1: the stretch's first two as atomic adds, then dword stores up to an aligned 16 bytes (the ragged
+    // first block; held back until there is enough to get there), whole blocks as one store each, and at the stretch's end the
+    // ragged last block as dwords.  What stays (at most three) moves to the front.
+    // (a function of its own, by value: inlined at every look it costs the bulk loop fifty registers; the pointers with their
+    // address spaces, which a call boundary otherwise forgets, turning every access into a flat one on a 64-bit address)
+    typedef __attribute__((address_space(1))) uint32_t GlobalWord;
+    typedef __attribute__((address_space(3))) uint32_t LdsWord;
+    __device__ __forceinline__ void drain(uint32_t i, bool last) { cnt = drain_staged((GlobalWord *)S, (LdsWord *)ring, g0, cnt, i, last); }
+    static __device__ __noinline__ uint32_t drain_staged(GlobalWord *S, LdsWord *ring, uint32_t g0, uint32_t cnt, uint32_t i, bool last) {
+        const uint32_t first = i - cnt, word = uint32_t(reinterpret_cast<uintptr_t>(S) >> 2) + first;
+        uint32_t k = 0;
+#pragma unroll 1
+        while (k < cnt) {                                        // one digit or one block per trip: rare, and short on registers
+            const uint32_t a = (word + k) & 3u, left = cnt - k;  // where digit first + k sits in its aligned 16 bytes
+            LdsWord *r = ring + k * 64;
+            if (first + k < g0 + 2) { atomicAdd((uint32_t *)&S[first + k], r[0]); k++; }
+            else if (a == 0 && left >= 4) { *(uint4 *)(S + first + k) = make_uint4(r[0], r[64], r[128], r[192]); k += 4; }
+            else if (last || (a != 0 && left >= 4 - a)) { S[first + k] = r[0]; k++; }
+            else break;
+        }
+        cnt -= k;
+        if (k != 0) {
+#pragma unroll 1
+            for (uint32_t m = 0; m < cnt; m++) ring[m * 64] = ring[(k + m) * 64];
+        }
+        return cnt;
     }
     __device__ void add(uint32_t i, uint32_t v) { atomicAdd(&S[i], v); }
 };
 
 template <bool TILE_CODES>
-__global__ __launch_bounds__(256) void k_k1p_c(Plan p, uint32_t total_chunks, const uint8_t *res,
-                                               const Stretch *st, const Entry *en, const SliceTotals *tot,
-                                               uint32_t *S) {
+__global__ __launch_bounds__(256, 7) void k_k1p_c(Plan p, uint32_t total_chunks, const uint8_t *res,
+                                                  const Stretch *st, const Entry *en, const SliceTotals *tot,
+                                                  uint32_t *S) {
     __shared__ CodeEntryC codes[256];
+    __shared__ uint32_t ring[kRing * 256];
     codes[threadIdx.x] = code_entry_c(device_code_entry(threadIdx.x));
     __syncthreads();
     const uint32_t gc = blockIdx.x * 256 + threadIdx.x;
@@ -1298,6 +1334,7 @@ __global__ __launch_bounds__(256) void k_k1p_c(Plan p, uint32_t total_chunks, co
     if (tot[slice].bad) return;
     DeviceAdder add;
     add.S = S + p.dig_off[slice];
+    add.ring = ring + (threadIdx.x >> 6) * (kRing * 64) + (threadIdx.x & 63u);
     if (TILE_CODES) c_stretch_in(TileCodes{res, p.chunk_base[slice]}, o, en[gc], gc - p.chunk_base[slice], codes, add);
     else c_stretch(res + p.res_off[slice], o, en[gc], gc - p.chunk_base[slice], codes, add);
 }
