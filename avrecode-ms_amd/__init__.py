@@ -35,11 +35,13 @@ KIND_RANGE_KEYS, EST_KEYS = 4, 1026                           # key records: the
 SEL_BYPASS, SEL_TERMINATE = 1024, 1025
 SEL8_BYPASS, SEL8_TERMINATE, MAX_STATES8 = 126, 127, 126      # one-byte records (KIND_CABAC8)
 SLICE_OK, SLICE_ZERO_PROB, SLICE_OVERFLOW, SLICE_BAD_RECORD = 0, 1, 2, 3
+SLICE_VERIFY_FAILED, VERIFY_NONE = 4, 0xFFFFFFFF             # only ever set by the K2 verifier; "no bad bin"
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_api.cpp"]
-_DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_synth.h", "avr_tables.h"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_verify.hip", "avr_api.cpp"]
+_DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_synth.h", "avr_tables.h",
+                    "avr_verify.h"]
 
 
 class AvrError(RuntimeError):
@@ -160,6 +162,13 @@ SIGNATURES = {
     "avr_batch_get_states": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
     "avr_batch_timings": (c_int, [c_void_p, POINTER(c_float)]),
     "avr_batch_run_info": (c_int, [c_void_p, POINTER(ctypes.c_uint32)]),
+    "avr_batch_set_verify": (c_int, [c_void_p, c_int]),
+    "avr_batch_get_verify": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_batch_verify_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "avr_range_verify_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avr_range_verify_slices_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avr_multi_create": (c_void_p, [c_void_p, c_size_t, c_size_t, c_size_t]),
     "avr_multi_destroy": (None, [c_void_p]),
     "avr_multi_add_slice_cabac": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
@@ -278,7 +287,8 @@ def test_hooks(**hooks):
     """FOR tests/ ONLY.  Inside the block, lib() is libavrecode_hip_hooks.so -- the same sources built with
     -DAVR_TEST_HOOKS -- with the named hooks set (csrc/avr_internal.h: k1p_force_retry_every, census_stride,
     chain_lanes, k1_form_ref, k1_path [1 serial, 2 chunked], no_dense, no_hint, k2p_seg_len, local_waves, k2p_wave); all of them keep the bytes exact and
-    only force paths that real batches take rarely -- except k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
+    only force paths that real batches take rarely -- except verify_flip, which corrupts one slice's first byte on the device in front of the verifier (a batch with
+    set_verify on) so that a test sees a failure travel through the batch API, and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
     AVR_SLICE_RETRY_SERIAL) so that a test can see which ones it coded itself.  The product library has no such switches."""
     global _lib, _hooks_lib
     if _hooks_lib is None:
@@ -463,6 +473,23 @@ class Batch:
         _check(self._L.avr_batch_timings(self._h, ms))
         return dict(zip(("h2d_ms", "pack_ms", "encode_ms", "d2h_ms"), list(ms)))
 
+    def set_verify(self, on: bool = True):
+        """K2 batches (KIND_RANGE, KIND_RANGE_KEYS): from the next submit on, every coded slice is decoded back on the device against
+        its records, behind the encode kernels.  A slice that does not decode comes back with SLICE_VERIFY_FAILED."""
+        _check(self._L.avr_batch_set_verify(self._h, 1 if on else 0))
+
+    def get_verify(self, i: int) -> int:
+        """Index of slice i's first bin that decoded to another value, or VERIFY_NONE."""
+        v = c_uint32()
+        _check(self._L.avr_batch_get_verify(self._h, i, ctypes.byref(v)))
+        return v.value
+
+    def verify_ms(self) -> float:
+        """Milliseconds of the verifier in the last run (0 with verify off); timings()["encode_ms"] is the encode alone."""
+        ms = c_float()
+        _check(self._L.avr_batch_verify_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
 
 class MultiBatch:
     """One batch sharded over several GPUs (avr_multi_*): LPT by bin count, a host thread and an avr_batch per device."""
@@ -535,6 +562,6 @@ class MultiBatch:
 from .device import DeviceWorkload, encode_tiles, plan_tiles, synth_config  # noqa: E402  (torch-backed helpers)
 
 __all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS",
-           "SEL_BYPASS", "SEL_TERMINATE",
+           "SEL_BYPASS", "SEL_TERMINATE", "SLICE_VERIFY_FAILED", "VERIFY_NONE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
            "make_cabac_records", "make_range_records", "plan_tiles", "synth_config", "tail_patch"]

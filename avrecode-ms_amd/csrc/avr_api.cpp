@@ -163,6 +163,14 @@ struct avr_batch {
     uint32_t hint_used = 0;                 // what the run in flight was sized by (0: it asked the device and waited)
     uint32_t info[4] = {0, 0, 0, 0};        // avr_batch_run_info
     avr_chunk_plan plan{};                  // of the chunked run in flight (device arrays of this batch)
+
+    // verification of a K2 run (avr_batch_set_verify): off by default, and then none of this is touched
+    bool verify = false;                    // the setting: the next submit enqueues the verifier behind the encode
+    bool verified = false;                  // the run in flight / the last run had it
+    hipEvent_t vev[3] = {};                 // end of the encode, start and end of the verifier (created when verify is first set)
+    float verify_ms = 0;
+    DevBuf<uint32_t> d_first_bad;
+    PinBuf<uint32_t> h_first_bad;
 };
 
 // One plan array to the device through the batch's pinned arena: the copy is asynchronous for real (a copy from
@@ -219,6 +227,7 @@ int avr_test_hook_set(const char *name, uint32_t value) {
     else if (!strcmp(name, "chain_whole")) h.chain_whole = value;
     else if (!strcmp(name, "chain_segments")) h.chain_segments = value;
     else if (!strcmp(name, "chain_force_redo")) h.chain_force_redo = value;
+    else if (!strcmp(name, "verify_flip")) h.verify_flip = value;
     else if (!strcmp(name, "reset")) h = avr::TestHooks{};
     else return fail(AVR_ERR_INVALID, "unknown test hook %s", name);
     return AVR_OK;
@@ -275,7 +284,9 @@ void avr_batch_destroy(avr_batch *b) {
     b->d_blk_base.release(); b->d_blk_slice.release(); b->d_workspace.release();
     b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release(); b->d_est_chunk_base.release();
     b->d_est_chunk_slice.release(); b->d_est_in.release(); b->d_est_out.release(); b->d_est_ws.release();
+    b->d_first_bad.release(); b->h_first_bad.release();
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : b->vev) if (e) (void)hipEventDestroy(e);
     if (b->stream) { avr::forget_part_streams(b->stream); avr::forget_stream(b->stream); (void)hipStreamDestroy(b->stream); }
     delete b;
 }
@@ -531,6 +542,24 @@ static int resolve_keys(avr_batch *b, uint32_t n32) {
     return AVR_OK;
 }
 
+// The verifier behind the encode kernels of a K2 run, between events of its own (the encode's slot of the timings ends at vev[0]).
+static int enqueue_verify(avr_batch *b, uint32_t n32, bool tiled) {
+    hipStream_t s = b->stream;
+    AVR_HIP(hipEventRecord(b->vev[0], s));
+#ifdef AVR_TEST_HOOKS
+    if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
+#endif
+    AVR_HIP(hipEventRecord(b->vev[1], s));
+    if (tiled)
+        AVR_HIP(avr::launch_range_verify(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
+                                         b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_first_bad.p));
+    else
+        AVR_HIP(avr::launch_range_verify(false, s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, nullptr, n32, b->d_out.p,
+                                         b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_first_bad.p));
+    AVR_HIP(hipEventRecord(b->vev[2], s));
+    return AVR_OK;
+}
+
 static int submit_impl(avr_batch *b, bool use_hint) {
     const size_t n = b->n_bins.size();
     const uint32_t n32 = uint32_t(n);
@@ -569,6 +598,8 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if ((rc = b->h_plan.reserve(64 * 16 + (n + 1) * 64 + (n_tiles + 1) * 8 + (chunked ? (n_chunks_max + n_blks_max) * 4 : 0) +
                                 (b->keys ? (n_chunks_max + n + n_groups + 3) * 4 + 256 : 0)))) return rc;
     if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
+    b->verified = b->verify && !cabac;
+    if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
 
     hipStream_t s = b->stream;
     b->plan_used = 0;
@@ -613,6 +644,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
         AVR_HIP(avr::launch_k2p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_chunk_base.p, b->d_chunk_slice.p,
                                 chunk_base.back(), total_out, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p));
+        if (b->verified && (rc = enqueue_verify(b, n32, false))) return rc;      // over the slice-major records K2p read
     } else if (chunked) {
         std::vector<uint64_t> res_off(n + 1, 0), dig_off(n + 1, 0);
         std::vector<uint32_t> chunk_base(n + 1, 0), blk_base(n + 1, 0), chunk_slice, blk_slice;
@@ -668,6 +700,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         else
             AVR_HIP(avr::launch_range_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
                                              b->d_out_off.p, b->d_out_len.p, b->d_status.p));
+        if (b->verified && (rc = enqueue_verify(b, n32, true))) return rc;       // over the tiles the encoder read
     }
     return enqueue_lengths(b, n32);
 }
@@ -681,6 +714,7 @@ static int enqueue_lengths(avr_batch *b, uint32_t n32) {
     AVR_HIP(hipMemcpyAsync(b->h_out_len.p, b->d_out_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     AVR_HIP(hipMemcpyAsync(b->h_status.p, b->d_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (with_states) AVR_HIP(hipMemcpyAsync(b->h_final.p, b->d_final.p, n * ns, hipMemcpyDeviceToHost, s));
+    if (b->verified) AVR_HIP(hipMemcpyAsync(b->h_first_bad.p, b->d_first_bad.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return AVR_OK;
 }
 
@@ -691,6 +725,9 @@ int avr_batch_submit(avr_batch *b) {
     b->ran = false;                                              // a batch may be submitted again after avr_batch_wait: same slices, coded anew
     const size_t n = b->n_bins.size();
     b->dense_off.assign(n + 1, 0);
+    if (b->verify && b->kind >= 0 && b->kind != AVR_KIND_RANGE)
+        return fail(AVR_ERR_INVALID, "verification exists for the compress direction only: not for a K1 batch");
+    b->verified = false;
     if (n == 0) { b->in_flight = true; return AVR_OK; }
     const bool use_hint = b->dense_hint > 0 && !avr::no_hint();
     if (int rc = submit_impl(b, use_hint)) { (void)hipStreamSynchronize(b->stream); return rc; }
@@ -746,6 +783,11 @@ int avr_batch_wait(avr_batch *b) {
     AVR_HIP(hipEventRecord(b->ev[4], s));
     AVR_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&b->ms[i], b->ev[i], b->ev[i + 1]);
+    b->verify_ms = 0;
+    if (b->verified) {                                           // the encode's slot ends where the verifier's events begin
+        (void)hipEventElapsedTime(&b->ms[2], b->ev[2], b->vev[0]);
+        (void)hipEventElapsedTime(&b->verify_ms, b->vev[1], b->vev[2]);
+    }
     b->ran = true;                                               // only now: the getters hand out h_out / h_status
     return AVR_OK;
 }
@@ -801,6 +843,30 @@ int avr_batch_run_info(avr_batch *b, uint32_t info[4]) {
 int avr_batch_timings(avr_batch *b, float ms[4]) {
     if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
     memcpy(ms, b->ms, sizeof b->ms);
+    return AVR_OK;
+}
+
+int avr_batch_set_verify(avr_batch *b, int on) {
+    if (!b) return fail(AVR_ERR_INVALID, "null batch");
+    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    if (on && !b->vev[0]) {
+        if (int rc = select_device(b->device)) return rc;
+        for (auto &e : b->vev) AVR_HIP(hipEventCreate(&e));
+    }
+    b->verify = on != 0;
+    return AVR_OK;
+}
+
+int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad) {
+    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
+    if (first_bad) *first_bad = b->verified ? b->h_first_bad.p[slice] : AVR_VERIFY_NONE;
+    return AVR_OK;
+}
+
+int avr_batch_verify_ms(avr_batch *b, float *ms) {
+    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
+    *ms = b->verify_ms;
     return AVR_OK;
 }
 
@@ -1035,6 +1101,17 @@ int avr_range_encode_tiles_device(int device, void *stream, const void *tiles, c
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_range_encode(true, static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices),
                                      out, out_off, out_len, status));
+    return AVR_OK;
+}
+
+int avr_range_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
+                                  const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
+                                  const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
+    if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
+    if (n_slices && (!tiles || !out || !out_len || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_range_verify(true, static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices),
+                                     out, out_off, out_len, status, first_bad));
     return AVR_OK;
 }
 
@@ -1337,6 +1414,17 @@ int avr_range_encode_slices_device(int device, void *stream, const uint16_t *rec
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_range_encode(false, static_cast<hipStream_t>(stream), recs, rec_off, n_bins, order, uint32_t(n_slices),
                                      out, out_off, out_len, status));
+    return AVR_OK;
+}
+
+int avr_range_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
+                                   const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
+    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
+    if (n_slices && (!recs || !out || !out_len || !status || !first_bad)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_range_verify(false, static_cast<hipStream_t>(stream), recs, rec_off, n_bins, order, uint32_t(n_slices),
+                                     out, out_off, out_len, status, first_bad));
     return AVR_OK;
 }
 

@@ -209,4 +209,29 @@ struct RangeEncoder64 {
     }
 };
 
+// ------------------------------------------------------------------ record fetch
+
+// Where lane `lane` of processing slot `g` finds chunk c (8 records = 16 bytes).
+template <bool TILED>
+struct ChunkSource {
+    const uint4 *p;
+    uint32_t stride;       // in uint4
+    __device__ ChunkSource(const void *recs, const uint64_t *off, uint32_t g, uint32_t slice) {
+        if (TILED) {       // off = tile_off (16-byte units), one entry per 64 slots
+            p = reinterpret_cast<const uint4 *>(recs) + off[g >> 6] + (g & 63);
+            stride = 64;
+        } else {           // off = rec_off (records), indexed by slice
+            p = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(recs) + off[slice]);
+            stride = 1;
+        }
+    }
+    __device__ __forceinline__ uint4 load(uint32_t c) const { return p[size_t(c) * stride]; }
+    // the same read marked non-temporal: records are read once, and what they would push out of L2 are the output lines being filled
+    __device__ __forceinline__ uint4 load_nt(uint32_t c) const {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p + size_t(c) * stride));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+};
+
 }  // namespace avr

@@ -49,6 +49,7 @@ struct TestHooks {
     uint32_t k1_words8;              // one-lane-per-slice K1: the output in 8-byte stores (rounds 1-3), not 16-byte ones
     uint32_t k1_waves;               // one-lane-per-slice K1: waves to a workgroup (0 = the built-in count)
     uint32_t k2p_wave;               // K2p pass 1: 1 = a wave per slice, 2 = a lane per slice, 3 = a lane per slice and a wave each for the longest (0 = by slice count)
+    uint32_t verify_flip;            // batch API with verify on: k > 0 complements bit 7 of byte 0 of slice k - 1's output region between the encode and the verifier
     uint32_t k1p_keep_retry;         // K1p (every form): the slices that leave the parallel path -- declined by the scheme, handed over by phase D -- keep
                                      // AVR_SLICE_RETRY_SERIAL (no serial kernel after it), so a test sees which slices phase D coded itself
 };
@@ -92,6 +93,13 @@ hipError_t launch_range_encode(bool tiled, hipStream_t s, const void *recs, cons
                                const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices,
                                uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
                                int32_t *status);
+// the K2 verifier (avr_verify.hip): decodes every AVR_SLICE_OK slice back against its records; writes status and first_bad only
+hipError_t launch_range_verify(bool tiled, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
+                               const uint32_t *order, uint32_t n_slices, const uint8_t *out, const uint64_t *out_off,
+                               const uint32_t *out_len, int32_t *status, uint32_t *first_bad);
+#ifdef AVR_TEST_HOOKS
+hipError_t launch_verify_flip(hipStream_t s, uint8_t *out, const uint64_t *out_off, uint32_t slice);
+#endif
 hipError_t launch_pack_tiles(hipStream_t s, int kind, uint32_t n_states, const uint16_t *recs,
                              const uint64_t *rec_off, const uint32_t *n_bins, const uint32_t *order,
                              uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);

@@ -73,6 +73,14 @@ struct phase_timer {
 
 inline void gpu_check(int rc) { if (rc < 0) throw std::runtime_error(std::string("avr: ") + avr_last_error()); }
 
+// AVR_TIMING=1: the verifier's share of a batch that ran with avr_batch_set_verify, as a phase of its own (device time, between its events)
+inline void report_verify_ms(avr_batch *b) {
+    if (!getenv("AVR_TIMING")) return;
+    float ms = 0;
+    gpu_check(avr_batch_verify_ms(b, &ms));
+    fprintf(stderr, "[timing] %-28s %8.1f ms\n", "compress: GPU verify (a5)", double(ms));
+}
+
 struct batch_holder {                                    // RAII around the C ABI's avr_batch
     avr_batch *b;
     batch_holder(int device, size_t max_slices, size_t max_bins) : b(avr_batch_create(device, max_slices, max_bins)) {
@@ -163,6 +171,9 @@ class compressor {                                       // recode.cpp:1109-1316
     // The adaptive estimators on the device: the recorders write key records and the file's slices go into the batch as one group
     // of AVR_KIND_RANGE_KEYS slices (fresh estimators: h264_model starts a file so).  Before prepare(); residual hooks off only.
     void set_device_estimators(bool on) { device_estimators_ = on; }
+    // The file's own batch (run()) with the verifier behind the encode: every coded slice decoded back on the device against its
+    // records (avr_batch_set_verify).  A caller with a batch of its own (add_to / take_from) sets that on its batch.
+    void set_verify(bool on) { verify_ = on; }
     size_t pending_slices() const { return pending_.size(); }
     size_t pending_bins() const { size_t bins = 0; for (auto &p : pending_) bins += p.recs.size(); return bins; }
     void add_to(avr_batch *b) {                          // the slice indices the batch hands out are consecutive: the first one is kept
@@ -181,6 +192,11 @@ class compressor {                                       // recode.cpp:1109-1316
             const uint8_t *bytes; size_t len; int status;
             gpu_check(avr_batch_get(b, size_t(first_in_batch_) + i, &bytes, &len, &status));
             if (status == AVR_SLICE_ZERO_PROB) throw std::runtime_error("Encoder error: emitted a zero-probability symbol.");   // arithmetic_code.h:117
+            if (status == AVR_SLICE_VERIFY_FAILED) {         // the verifier's (a batch with avr_batch_set_verify): the bytes must not reach a container
+                uint32_t bin = AVR_VERIFY_NONE;
+                gpu_check(avr_batch_get_verify(b, size_t(first_in_batch_) + i, &bin));
+                throw std::runtime_error("Verify error: recoded block does not decode to its bins (slice " + std::to_string(i) + ", bin " + std::to_string(bin) + ")");
+            }
             if (status != AVR_SLICE_OK) throw std::runtime_error("avr: slice status " + std::to_string(status));
             Block &blk = out_.block[pending_[i].block];
             blk.has_cabac = true;                        // out->set_cabac, recode.cpp:1101
@@ -289,13 +305,15 @@ class compressor {                                       // recode.cpp:1109-1316
         if (pending_.empty()) return;
         batch_holder bh(device_, pending_.size(), pending_bins() + 8);
         add_to(bh.b);
+        if (verify_) gpu_check(avr_batch_set_verify(bh.b, 1));
         gpu_check(avr_batch_run(bh.b));
+        if (verify_) report_verify_ms(bh.b);
         take_from(bh.b);
     }
 
     struct pending { int block; std::vector<uint16_t> recs; };
     int first_in_batch_ = -1;
-    bool device_estimators_ = false;
+    bool device_estimators_ = false, verify_ = false;
     std::string original_;
     int device_;
     int read_offset_ = 0, prev_coded_block_end_ = 0;

@@ -18,6 +18,10 @@
 // estimators (AVR_KIND_RANGE_KEYS, one group a file) where the host does it per bin otherwise; the .recode bytes are the same
 // either way.  Off by default.  No effect together with AVR_MODEL_HOOKS=1 (the significance-map keys are not among the 1026 the
 // device keeps), which the command says once on stderr.
+// AVR_VERIFY=1 = the K2 batches of compress, roundtrip and test <dir> run with the verifier on (avr_batch_set_verify): every coded
+// slice is decoded back on the device against its records before its bytes go into a container, with or without
+// AVR_DEVICE_ESTIMATORS=1; a slice that does not decode ends the file with "Verify error: ..." (exit status 1, as with the other
+// coder errors).  The .recode bytes are the same either way.  Read here, not by the library.  Off by default.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +56,8 @@ bool device_estimators() {
     return on;
 }
 
+bool verify() { static const bool on = [] { const char *d = getenv("AVR_VERIFY"); return d && atoi(d) != 0; }(); return on; }
+
 std::string slurp(const std::string &path) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("cannot open " + path);
@@ -63,6 +69,7 @@ std::string slurp(const std::string &path) {
 std::string compress_bytes(const std::string &original) {            // compressor::run, recode.cpp:1122-1132
     host::compressor c(original, device());
     c.set_device_estimators(device_estimators());
+    c.set_verify(verify());
     h264::h264_stream_decoder d;
     d.residual_hooks = model_hooks();
     return c.run(&d);
@@ -260,6 +267,7 @@ void perf_test_driver(const std::string &directory_path) {
     const unsigned threads = std::min<unsigned>(hw ? hw : 4, 32);
     shared_batch batch_in, batch_out;
     const bool on_device = device_estimators();                      // read here, once, not in the files' threads
+    const bool verify_on = verify();
     for (size_t base = 0; base < files.size(); base += window) {
         const size_t n = std::min(window, files.size() - base);
         std::vector<file_job> jobs(n);
@@ -292,7 +300,9 @@ void perf_test_driver(const std::string &directory_path) {
                 const auto t0 = std::chrono::steady_clock::now();
                 avr_batch *b = batch_in.get(slices, bins + 8);
                 for (file_job &j : jobs) if (!j.failed) j.c->add_to(b);
+                if (verify_on) host::gpu_check(avr_batch_set_verify(b, 1));
                 host::gpu_check(avr_batch_run(b));
+                if (verify_on) host::report_verify_ms(b);
                 for (file_job &j : jobs) if (!j.failed) { try { j.c->take_from(b); } catch (const std::exception &e) { log_exception(j, e); } }
                 const double ms = ms_since(t0);
                 for (file_job &j : jobs) j.c_gpu_ms = bins ? ms * double(j.c_bins) / double(bins) : 0;

@@ -298,6 +298,7 @@ class DeviceWorkload:
         run of this object reported (none yet: the call asks the device and waits); exact whatever the guess.  settle() after a
         synchronisation takes the count over for the next run.  KIND_CABAC8 with narrow_tiles: avr_cabac8_encode_tiles_device, which
         has nothing to count and never blocks."""
+        self._verify_layout = "tiles"
         if getattr(self, "narrow_tiles", False):
             import torch
             _check(lib().avr_cabac8_encode_tiles_device(
@@ -548,6 +549,7 @@ class DeviceWorkload:
     def encode_chunked(self):
         """K1 / K2 through the intra-slice parallel kernels (same bytes as encode())."""
         import torch
+        self._verify_layout = "slices"
         recs, rec_off = self._slice_major()
         p = self._chunk_plan()
         if self.kind == KIND_CABAC8:                         # one-byte records: nothing to guess, nothing waits
@@ -642,6 +644,7 @@ class DeviceWorkload:
     def encode_slice_major(self):
         """Same result from the slice-major layout (only for workloads built with from_host)."""
         import torch
+        self._verify_layout = "slices"
         L = lib()
         sp = _stream_ptr(torch)
         if self.kind == KIND_CABAC:
@@ -654,6 +657,32 @@ class DeviceWorkload:
                 self.device_index, sp, self.rec_flat.data_ptr(), self.rec_off.data_ptr(), self.n_bins.data_ptr(),
                 self.order.data_ptr(), self.n_slices, self.out.data_ptr(), self.out_off.data_ptr(),
                 self.out_len.data_ptr(), self.status.data_ptr()))
+
+    def verify(self):
+        """K2 only, behind encode() / encode_chunked() / encode_slice_major() on torch's current stream: every AVR_SLICE_OK slice
+        decoded back on the device against its records (avr_range_verify_tiles_device after encode(), avr_range_verify_slices_device
+        after the two slice-major calls).  Returns the first_bad tensor (int32; VERIFY_NONE reads as -1) and leaves the statuses in
+        self.status: SLICE_VERIFY_FAILED for a slice whose bytes do not decode to its bins.  Enqueues and returns."""
+        import torch
+        if self.kind != KIND_RANGE:
+            raise AvrError("verify: the verifier exists for K2 (KIND_RANGE) workloads only")
+        layout = getattr(self, "_verify_layout", None)
+        if layout is None:
+            raise AvrError("verify: nothing was encoded yet")
+        L = lib()
+        first_bad = torch.empty(self.n_slices, dtype=torch.int32, device=self.n_bins.device)
+        if layout == "tiles":
+            _check(L.avr_range_verify_tiles_device(
+                self.device_index, _stream_ptr(torch), self.tiles.data_ptr(), self.tile_off.data_ptr(), self.n_bins.data_ptr(),
+                self.order.data_ptr(), self.n_slices, self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(),
+                self.status.data_ptr(), first_bad.data_ptr()))
+        else:
+            recs, rec_off = self._slice_major()
+            _check(L.avr_range_verify_slices_device(
+                self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(), None,
+                self.n_slices, self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
+                first_bad.data_ptr()))
+        return first_bad
 
     # ---- accounting (DESIGN.md "algorithmic bytes")
     def output_bytes(self) -> int:

@@ -92,6 +92,10 @@ extern "C" {
 #define AVR_SLICE_ZERO_PROB   1  /* arithmetic_code.h:116-118 "emitted a zero-probability symbol" */
 #define AVR_SLICE_OVERFLOW    2  /* output region too small (never with the batch API's sizing) */
 #define AVR_SLICE_BAD_RECORD  3  /* a record the rule above calls malformed */
+/* Only ever set by the verifier (avr_range_verify_*_device, avr_batch_set_verify), and only on a slice that was AVR_SLICE_OK: the
+ * slice's coded bytes do not decode back to the bins of its records.  The slice's bytes and length stay retrievable as they are. */
+#define AVR_SLICE_VERIFY_FAILED 4           /* only ever set by the verifier */
+#define AVR_VERIFY_NONE 0xFFFFFFFFu
 
 #define AVR_SEL_BYPASS     1024
 #define AVR_SEL_TERMINATE  1025
@@ -219,6 +223,20 @@ int avr_batch_run_info(avr_batch *b, uint32_t info[4]);
 /* milliseconds of the last run: [0] H2D, [1] pack kernel (for key records: the estimator resolver and the pack kernel), [2] encode kernel, [3] D2H */
 int avr_batch_timings(avr_batch *b, float ms[4]);
 
+/* Verification of a K2 batch (AVR_KIND_RANGE, AVR_KIND_RANGE_KEYS) on the device: off by default, and then nothing of a run differs.
+ * avr_batch_set_verify(b, 1): from the next avr_batch_submit on, the verifier (avr_range_verify_tiles_device on the one-lane-per-slice
+ * path, avr_range_verify_slices_device over the slice-major records on the K2p path -- for key records, the resolver's output) is
+ * enqueued behind the encode kernels on the batch's stream; avr_batch_submit still does not wait.  The setting stays until it is set
+ * again (avr_batch_reset keeps it); AVR_ERR_INVALID while the batch is in flight.  A slice whose bytes do not decode to its bins
+ * comes back from avr_batch_get with AVR_SLICE_VERIFY_FAILED, its bytes and length as the encoder left them, and
+ * avr_batch_get_verify gives the index of its first bad bin -- AVR_VERIFY_NONE for every other slice, and for every slice of a run
+ * with verify off.  avr_batch_timings()[2] stays the encode alone: the verifier sits between two events of its own, and
+ * avr_batch_verify_ms reports them (0 for a run with verify off).  Verification exists for the compress direction only: with verify
+ * on, avr_batch_submit of a K1 batch returns AVR_ERR_INVALID. */
+int avr_batch_set_verify(avr_batch *b, int on);
+int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad);
+int avr_batch_verify_ms(avr_batch *b, float *ms);
+
 /* ------------------------------------------------------------------ one batch over several GPUs
  * Slices are independent (one coder object each in the reference, recode.cpp:1270, :1525), so a batch shards
  * with no exchange between devices: avr_multi_run sorts the slices by bin count, hands them out longest first to
@@ -343,6 +361,28 @@ int avr_range_encode_tiles_device(int device, void *stream,
                                   const uint32_t *n_bins, const uint32_t *order, size_t n_slices,
                                   uint8_t *out, const uint64_t *out_off,
                                   uint32_t *out_len, int32_t *status);
+
+/* K2 verifier: the decoder of the recoded coder (arithmetic_code.h:209-298) over slices whose records are known, one lane per slice
+ * -- what the encoder was given, (range / (pos + neg)) * pos from each record, the decoder is given too, and the bin it decodes is
+ * compared with the record's.  It shares nothing with the encoders' carry handling or finish(), so it checks all three K2 paths.
+ * Layouts, `order`, out_off and out_len as for avr_range_encode_tiles_device / avr_range_encode_slices_device (padding records must
+ * be no-ops); run it behind the encode on the same stream.  status is in/out:
+ *   a slice whose status is not AVR_SLICE_OK on entry is skipped: its status stays, first_bad[slice] = AVR_VERIFY_NONE;
+ *   an AVR_SLICE_OK slice has its n_bins records decoded in order from out[out_off[i] .. out_off[i] + min(out_len[i], capacity));
+ *   at the first bin that decodes to another value the lane stops: first_bad[slice] = that bin's index, status[slice] =
+ *   AVR_SLICE_VERIFY_FAILED; otherwise first_bad[slice] = AVR_VERIFY_NONE and the status stays AVR_SLICE_OK.
+ * first_bad may be NULL in the tiles call (the status alone is wanted).  Nothing else is written: not out, out_len, records or tiles.
+ * Bytes at or past a slice's length read as zero whatever the region holds there, and nothing outside a slice's region is read.
+ * The calls enqueue on `stream` and return: they never block, allocate or use a workspace.  Refused before anything touches a
+ * device (AVR_ERR_INVALID): a null pointer with n_slices > 0 (order may be NULL in the slices call). */
+int avr_range_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off,
+                                  const uint32_t *n_bins, const uint32_t *order, size_t n_slices,
+                                  const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                  int32_t *status, uint32_t *first_bad /* may be NULL */);
+int avr_range_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off,
+                                   const uint32_t *n_bins, const uint32_t *order /* may be NULL */, size_t n_slices,
+                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                   int32_t *status, uint32_t *first_bad);
 
 /* K1, intra-slice parallel form ("K1p", avrecode-ms_amd/csrc/avr_k1p.h): the same bytes as
  * avr_cabac_encode_tiles_device, produced by many lanes per slice -- for batches of few, long
