@@ -476,7 +476,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
         return rc;
     avr_chunk_plan plan{b->d_res_off.p, b->d_chunk_base.p, b->d_chunk_slice.p, nullptr, nullptr, b->d_dig_off.p,
                         total_codes, dig_off.back(), chunk_base.back(), 0};
-    const size_t ws = avr::k1p_code_workspace_bytes(n, &plan);
+    const size_t ws = avr::code_layout(n, &plan).total;
     if ((rc = b->d_workspace.reserve(ws + 256))) return rc;
     hipStream_t s = b->stream;
     b->plan_used = 0;
@@ -519,7 +519,7 @@ static int resolve_keys(avr_batch *b, uint32_t n32) {
         chunk_base[i + 1] = chunk_base[i] + nc;
         chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
     }
-    const size_t ws = avr::est_workspace_bytes(n, n_groups, chunk_base.back());
+    const size_t ws = avr::est_layout(n, n_groups, chunk_base.back()).total;
     int rc;
     if ((rc = b->d_est_chunk_base.reserve(n + 1)) || (rc = b->d_est_chunk_slice.reserve(chunk_slice.size())) ||
         (rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(ws + 256)) ||
@@ -635,7 +635,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
             chunk_base[i + 1] = chunk_base[i] + nc;
             chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
         }
-        const size_t ws = avr::k2p_workspace_bytes(n, chunk_base.back(), total_out);
+        const size_t ws = avr::k2p_layout(n, chunk_base.back(), total_out).total;
         if ((rc = b->d_chunk_base.reserve(n + 1)) || (rc = b->d_chunk_slice.reserve(chunk_slice.size())) || (rc = b->d_workspace.reserve(ws + 256)))
             return rc;
         AVR_STAGE(b->d_chunk_base.p, chunk_base.data(), n + 1);
@@ -665,7 +665,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
             return rc;
         avr_chunk_plan plan{b->d_res_off.p, b->d_chunk_base.p, b->d_chunk_slice.p, b->d_blk_base.p, b->d_blk_slice.p, b->d_dig_off.p,
                             res_off.back(), dig_off.back(), chunk_base.back(), blk_base.back()};
-        const size_t ws = avr::k1p_workspace_bytes(n, uint32_t(ns), &plan);
+        const size_t ws = avr::k1p_layout(n, uint32_t(ns), &plan).total;
         if ((rc = b->d_workspace.reserve(ws + 256))) return rc;
         b->plan = plan;
         AVR_STAGE(b->d_res_off.p, res_off.data(), n + 1);
@@ -677,11 +677,11 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         AVR_HIP(hipEventRecord(b->ev[2], s));
         uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
         if (b->recs8)                                            // one-byte records: no census, no guess to check, nothing waits
-            AVR_HIP(avr::launch_k1p8(s, b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(ns), &plan, wsp,
-                                     b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p));
+            AVR_HIP(avr::launch_k1p8(s, b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
+                                     avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
         else
-            AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(ns), &plan, wsp,
-                                    b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p, &hint));
+            AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
+                                    avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}, &hint));
     } else {
         if (b->recs8)                                            // one-byte records validated and transposed in one pass, as they are
             AVR_HIP(avr::launch_pack_tiles8_narrow(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
@@ -760,8 +760,8 @@ int avr_batch_wait(avr_batch *b) {
         }
         if (b->last_path == 1 && b->h_ndense.p[1]) {             // slices with a context the sampled census missed: their second pass
             uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
-            AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_states.p, uint32_t(b->n_states), &b->plan,
-                                          wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p));
+            AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(b->n_states), &b->plan, wsp,
+                                          avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
             if ((rc = enqueue_lengths(b, n32))) return rc;
             AVR_HIP(hipStreamSynchronize(s));
             b->info[3] |= 2;
@@ -1115,31 +1115,37 @@ int avr_range_verify_tiles_device(int device, void *stream, const void *tiles, c
     return AVR_OK;
 }
 
+static int check_chunked(const uint64_t *rec_off, const uint32_t *n_bins, const uint64_t *out_off, size_t n_slices, size_t n_states,
+                         const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, const int32_t *status) {
+    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
+    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
+    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->blk_base || !plan->blk_slice ||
+                               !plan->dig_off || !workspace || !status)))
+        return fail(AVR_ERR_INVALID, "null plan pointer");
+    if (workspace_bytes < avr::k1p_layout(n_slices, uint32_t(n_states), plan).total)
+        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac_chunked_workspace_bytes()", workspace_bytes);
+    return AVR_OK;
+}
+
 size_t avr_cabac_chunked_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan) {
     if (!plan || n_states > AVR_MAX_STATES) return 0;
-    return avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan);
+    return avr::k1p_layout(n_slices, uint32_t(n_states), plan).total;
 }
 
 int avr_cabac_encode_chunked_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                                     size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
                                     void *workspace, size_t workspace_bytes, uint8_t *out, const uint64_t *out_off,
                                     uint32_t *out_len, int32_t *status, uint8_t *final_states) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
-    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->blk_base || !plan->blk_slice ||
-                               !plan->dig_off || !workspace || !status)))
-        return fail(AVR_ERR_INVALID, "null plan pointer");
-    if (workspace_bytes < avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan))
-        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac_chunked_workspace_bytes()", workspace_bytes);
+    if (int rc = check_chunked(rec_off, n_bins, out_off, n_slices, n_states, plan, workspace, workspace_bytes, status)) return rc;
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), init_states,
-                            uint32_t(n_states), plan, workspace, out, out_off, out_len, status, final_states));
+    AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
+                            avr::K1pIo{init_states, out, out_off, out_len, status, final_states}));
     return AVR_OK;
 }
 
 size_t avr_cabac8_chunked_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan) {
     if (!plan || n_states > AVR_MAX_STATES8) return 0;
-    return avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan);
+    return avr::k1p_layout(n_slices, uint32_t(n_states), plan).total;
 }
 
 int avr_cabac8_encode_chunked_device(int device, void *stream, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
@@ -1151,23 +1157,11 @@ int avr_cabac8_encode_chunked_device(int device, void *stream, const uint8_t *re
     if (n_slices && (!recs8 || !out || !out_len || (n_states && !init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
     if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->dig_off || !workspace || !status)))
         return fail(AVR_ERR_INVALID, "null plan pointer");
-    if (workspace_bytes < avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan))
+    if (workspace_bytes < avr::k1p_layout(n_slices, uint32_t(n_states), plan).total)
         return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac8_chunked_workspace_bytes()", workspace_bytes);
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k1p8(static_cast<hipStream_t>(stream), recs8, rec_off, n_bins, uint32_t(n_slices), init_states,
-                             uint32_t(n_states), plan, workspace, out, out_off, out_len, status, final_states));
-    return AVR_OK;
-}
-
-static int check_chunked(const uint64_t *rec_off, const uint32_t *n_bins, const uint64_t *out_off, size_t n_slices, size_t n_states,
-                         const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, const int32_t *status) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
-    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->blk_base || !plan->blk_slice ||
-                               !plan->dig_off || !workspace || !status)))
-        return fail(AVR_ERR_INVALID, "null plan pointer");
-    if (workspace_bytes < avr::k1p_workspace_bytes(n_slices, uint32_t(n_states), plan))
-        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac_chunked_workspace_bytes()", workspace_bytes);
+    AVR_HIP(avr::launch_k1p8(static_cast<hipStream_t>(stream), recs8, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
+                             avr::K1pIo{init_states, out, out_off, out_len, status, final_states}));
     return AVR_OK;
 }
 
@@ -1181,8 +1175,8 @@ int avr_cabac_encode_chunked_device_hinted(int device, void *stream, const uint1
     counts[0] = counts[1] = 0;
     if (n_slices == 0) return AVR_OK;
     const avr::DenseHint hint{std::min<uint32_t>(rows_hint, uint32_t(n_states)), counts, counts + 1};
-    AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), init_states,
-                            uint32_t(n_states), plan, workspace, out, out_off, out_len, status, final_states, &hint));
+    AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
+                            avr::K1pIo{init_states, out, out_off, out_len, status, final_states}, &hint));
     return AVR_OK;
 }
 
@@ -1193,8 +1187,8 @@ int avr_cabac_encode_chunked_second_pass_device(int device, void *stream, const 
     if (int rc = check_chunked(rec_off, n_bins, out_off, n_slices, n_states, plan, workspace, workspace_bytes, status)) return rc;
     if (int rc = select_device(device)) return rc;
     if (n_slices == 0) return AVR_OK;
-    AVR_HIP(avr::launch_k1p_retry(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), init_states,
-                                  uint32_t(n_states), plan, workspace, out, out_off, out_len, status, final_states));
+    AVR_HIP(avr::launch_k1p_retry(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
+                                  avr::K1pIo{init_states, out, out_off, out_len, status, final_states}));
     return AVR_OK;
 }
 
@@ -1217,45 +1211,30 @@ extern "C++" {
 // The streams the parts of avr_cabac_encode_chunked_device_parts run on, with their events: one set per (device, caller's stream), made on
 // first use and kept (work on the caller's stream is ordered, so consecutive calls share it); released by avr::forget_part_streams.
 namespace {
-struct PartStreams { int dev; hipStream_t main; hipStream_t side[AVR_MAX_PARTS - 1]; hipEvent_t fork, done[AVR_MAX_PARTS - 1]; };
-std::vector<PartStreams *> g_parts;
-std::mutex g_parts_mu;
+struct PartStreams { hipStream_t side[AVR_MAX_PARTS - 1]; hipEvent_t fork, done[AVR_MAX_PARTS - 1]; };
+avr::StreamPool<PartStreams> g_parts;
 hipError_t part_streams(hipStream_t s, PartStreams **out) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(g_parts_mu);
-    for (PartStreams *x : g_parts)
-        if (x->dev == dev && x->main == s) { *out = x; return hipSuccess; }
-    PartStreams *x = new PartStreams{};
-    x->dev = dev; x->main = s;
-    e = hipEventCreateWithFlags(&x->fork, hipEventDisableTiming);
-    for (int i = 0; i < AVR_MAX_PARTS - 1 && e == hipSuccess; i++) {
-        e = hipStreamCreateWithFlags(&x->side[i], hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&x->done[i], hipEventDisableTiming);
-    }
-    if (e != hipSuccess) { delete x; return e; }                 // (what was made of it is left to the process's end: an out-of-resources path)
-    g_parts.push_back(x);
-    *out = x;
-    return hipSuccess;
+    return g_parts.get(s, out, [](PartStreams &x) {              // (what was made of one that fails is left to the process's end: an out-of-resources path)
+        hipError_t e = hipEventCreateWithFlags(&x.fork, hipEventDisableTiming);
+        for (int i = 0; i < AVR_MAX_PARTS - 1 && e == hipSuccess; i++) {
+            e = hipStreamCreateWithFlags(&x.side[i], hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&x.done[i], hipEventDisableTiming);
+        }
+        return e;
+    });
 }
 }  // namespace
 namespace avr {
 void forget_part_streams(hipStream_t s) {
-    std::lock_guard<std::mutex> lock(g_parts_mu);
-    for (size_t i = 0; i < g_parts.size();) {
-        PartStreams *x = g_parts[i];
-        if (x->main != s) { i++; continue; }
+    g_parts.forget(s, [](PartStreams &x) {
         for (int k = 0; k < AVR_MAX_PARTS - 1; k++) {
-            (void)hipStreamSynchronize(x->side[k]);
-            avr::forget_stream(x->side[k]);                      // the library's own per-stream scratch of that stream
-            (void)hipEventDestroy(x->done[k]);
-            (void)hipStreamDestroy(x->side[k]);
+            (void)hipStreamSynchronize(x.side[k]);
+            avr::forget_stream(x.side[k]);                       // the library's own per-stream scratch of that stream
+            (void)hipEventDestroy(x.done[k]);
+            (void)hipStreamDestroy(x.side[k]);
         }
-        (void)hipEventDestroy(x->fork);
-        delete x;
-        g_parts.erase(g_parts.begin() + long(i));
-    }
+        (void)hipEventDestroy(x.fork);
+    });
 }
 }  // namespace avr
 }  // extern "C++"
@@ -1282,8 +1261,8 @@ int avr_cabac_encode_chunked_device_parts(int device, void *stream, const uint16
         q.counts[0] = q.counts[1] = 0;
         if (q.n_slices) {
             const avr::DenseHint hint{std::min<uint32_t>(q.rows_hint, uint32_t(n_states)), q.counts, q.counts + 1, uint32_t(n_parts)};
-            AVR_HIP(avr::launch_k1p(s, recs, q.rec_off, q.n_bins, uint32_t(q.n_slices), q.init_states, uint32_t(n_states), q.plan,
-                                    q.workspace, out, q.out_off, q.out_len, q.status, q.final_states, &hint));
+            AVR_HIP(avr::launch_k1p(s, recs, q.rec_off, q.n_bins, uint32_t(q.n_slices), uint32_t(n_states), q.plan, q.workspace,
+                                    avr::K1pIo{q.init_states, out, q.out_off, q.out_len, q.status, q.final_states}, &hint));
         }
         if (i) AVR_HIP(hipEventRecord(ps->done[i - 1], s));
     }
@@ -1293,7 +1272,7 @@ int avr_cabac_encode_chunked_device_parts(int device, void *stream, const uint16
 
 size_t avr_range_chunked_workspace_bytes(size_t n_slices, const avr_chunk_plan *plan, uint64_t out_total) {
     if (!plan) return 0;
-    return avr::k2p_workspace_bytes(n_slices, plan->total_chunks, out_total);
+    return avr::k2p_layout(n_slices, plan->total_chunks, out_total).total;
 }
 
 int avr_range_encode_chunked_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
@@ -1302,7 +1281,7 @@ int avr_range_encode_chunked_device(int device, void *stream, const uint16_t *re
     if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
     if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice || !workspace || !status || !out || !out_len)))
         return fail(AVR_ERR_INVALID, "null plan / workspace / output pointer");
-    if (workspace_bytes < avr::k2p_workspace_bytes(n_slices, plan->total_chunks, out_total))
+    if (workspace_bytes < avr::k2p_layout(n_slices, plan->total_chunks, out_total).total)
         return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_range_chunked_workspace_bytes()", workspace_bytes);
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_k2p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), plan->chunk_base,
@@ -1312,7 +1291,7 @@ int avr_range_encode_chunked_device(int device, void *stream, const uint16_t *re
 
 size_t avr_range_resolve_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan) {
     if (!plan) return 0;
-    return avr::est_workspace_bytes(n_slices, n_groups, plan->total_chunks);
+    return avr::est_layout(n_slices, n_groups, plan->total_chunks).total;
 }
 
 int avr_range_resolve_device(int device, void *stream, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins,
@@ -1325,7 +1304,7 @@ int avr_range_resolve_device(int device, void *stream, const uint16_t *keys, con
     if (n_slices && (!group_first || !recs_out || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
     if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice))) return fail(AVR_ERR_INVALID, "null plan pointer");
     if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
-    if (workspace_bytes < avr::est_workspace_bytes(n_slices, n_groups, plan->total_chunks))
+    if (workspace_bytes < avr::est_layout(n_slices, n_groups, plan->total_chunks).total)
         return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than avr_range_resolve_workspace_bytes()", workspace_bytes);
     if (n_slices && recs_out == keys) return fail(AVR_ERR_INVALID, "recs_out must not alias keys");
     if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(recs_out)) & 15)
@@ -1349,7 +1328,7 @@ static int check_plan(const avr_chunk_plan *plan, size_t n_slices, bool need_blo
 
 size_t avr_cabac_resolve_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan) {
     if (!plan || n_states > AVR_MAX_STATES) return 0;
-    return avr::k1p_resolve_workspace_bytes(n_slices, uint32_t(n_states), plan);
+    return avr::resolve_layout(n_slices, uint32_t(n_states), plan).total;
 }
 
 int avr_cabac_resolve_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
@@ -1359,7 +1338,7 @@ int avr_cabac_resolve_device(int device, void *stream, const uint16_t *recs, con
     if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
     if (int rc = check_plan(plan, n_slices, true)) return rc;
     if (n_slices && (!workspace || !status)) return fail(AVR_ERR_INVALID, "null workspace / status");
-    if (workspace_bytes < avr::k1p_resolve_workspace_bytes(n_slices, uint32_t(n_states), plan))
+    if (workspace_bytes < avr::resolve_layout(n_slices, uint32_t(n_states), plan).total)
         return fail(AVR_ERR_CAPACITY, "workspace smaller than avr_cabac_resolve_workspace_bytes()");
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_k1p_resolve(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), init_states,
@@ -1368,7 +1347,7 @@ int avr_cabac_resolve_device(int device, void *stream, const uint16_t *recs, con
 }
 
 size_t avr_cabac_resolved_workspace_bytes(size_t n_slices, const avr_chunk_plan *plan) {
-    return plan ? avr::k1p_code_workspace_bytes(n_slices, plan) : 0;
+    return plan ? avr::code_layout(n_slices, plan).total : 0;
 }
 
 int avr_cabac_encode_resolved_device(int device, void *stream, const uint8_t *codes, const uint32_t *n_bins, size_t n_slices,
@@ -1377,7 +1356,7 @@ int avr_cabac_encode_resolved_device(int device, void *stream, const uint8_t *co
     if (int rc = check_common(codes, n_bins, out_off, n_slices)) return rc;
     if (int rc = check_plan(plan, n_slices, false)) return rc;
     if (n_slices && (!workspace || !status)) return fail(AVR_ERR_INVALID, "null workspace / status");
-    if (workspace_bytes < avr::k1p_code_workspace_bytes(n_slices, plan))
+    if (workspace_bytes < avr::code_layout(n_slices, plan).total)
         return fail(AVR_ERR_CAPACITY, "workspace smaller than avr_cabac_resolved_workspace_bytes()");
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_k1p_code(static_cast<hipStream_t>(stream), codes, n_bins, uint32_t(n_slices), plan, workspace, out, out_off,

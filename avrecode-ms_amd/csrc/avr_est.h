@@ -31,6 +31,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "avr_layout.h"                                // kKeysPad, kWindow, n_rows and the workspace: EstLayout
+
 #if defined(__HIPCC__)
 #define AVR_EST_HD __host__ __device__ inline
 #else
@@ -41,11 +43,9 @@ namespace avr {
 namespace est {
 
 constexpr uint32_t kKeys = 1026;                       // context ids 0..1023, bypass, terminate: h264_model's flat_[]
-constexpr uint32_t kKeysPad = 1028;                    // a table's stride in the workspace
 constexpr uint32_t kLimit = 0x60;                      // recode.cpp:1046: halve when pos + neg exceeds this
 constexpr uint32_t kFresh = 1u | (1u << 8);            // {1, 1}; a table entry is pos | neg << 8
 constexpr uint32_t kChunk = 1024;                      // bins per chunk (AVR_CHUNK_BINS)
-constexpr uint32_t kWindow = 16;                       // chunks per window
 constexpr uint32_t kNoBad = 0xffffffffu;
 
 AVR_EST_HD bool key_ok(uint32_t rec) { return (rec >> 1) < kKeys; }          // bits 12..15 clear and key <= AVR_SEL_TERMINATE
@@ -166,12 +166,9 @@ AVR_EST_HD void window_block_heads(uint32_t w, uint32_t W, const Row rows[2], Bl
     if (rows[1].c0 < rows[1].c1) heads[1] = BlockHead{true, rows[1].g, 0, RowSeq{w, (rows[1].b - 1) / W - w + 1}};
 }
 
-// workspace: slice -> group, first bad slice per group, per row a 32-bit table (counts, then functions) and a 16-bit one
-// (totals, then {pos, neg} at the row's start)
-AVR_EST_HD uint64_t align256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
-AVR_EST_HD uint64_t n_rows(uint64_t total_chunks, uint32_t W) { return 2 * ((total_chunks + W - 1) / W); }
-AVR_EST_HD uint64_t workspace_bytes(uint64_t n_slices, uint64_t n_groups, uint64_t total_chunks) {
-    return align256(4 * n_slices) + align256(4 * n_groups) + n_rows(total_chunks, kWindow) * (kKeysPad * 6);
+// the workspace is avr_layout.h's EstLayout; its size for the emulator (tests/est_emul.cpp)
+inline uint64_t workspace_bytes(uint64_t n_slices, uint64_t n_groups, uint64_t total_chunks) {
+    return est_layout(n_slices, n_groups, total_chunks).total;
 }
 
 }  // namespace est

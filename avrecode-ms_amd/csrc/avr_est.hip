@@ -1,4 +1,6 @@
 // The estimator resolver (avr_est.h): key records -> K2 range records, on the device.  Kernels and their launcher.
+#include <hip/hip_runtime.h>
+
 #include <algorithm>
 
 #include "avr_est.h"
@@ -311,10 +313,6 @@ __global__ __launch_bounds__(256) void k_est_status(EstParams p) {
 
 }  // namespace
 
-size_t est_workspace_bytes(size_t n_slices, size_t n_groups, uint32_t total_chunks) {
-    return size_t(est::workspace_bytes(n_slices, n_groups, total_chunks));
-}
-
 hipError_t launch_est_resolve(hipStream_t s, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
                               const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in, uint8_t *est_out,
                               const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, void *workspace,
@@ -325,14 +323,12 @@ hipError_t launch_est_resolve(hipStream_t s, const uint16_t *keys, const uint64_
     p.est_in = reinterpret_cast<const uint16_t *>(est_in);
     p.est_out = reinterpret_cast<uint16_t *>(est_out);
     p.chunk_base = chunk_base; p.chunk_slice = chunk_slice;
+    const EstLayout L = est_layout(n_slices, n_groups, total_chunks);
     uint8_t *ws = static_cast<uint8_t *>(workspace);
-    p.slice_group = reinterpret_cast<uint32_t *>(ws);
-    ws += est::align256(4 * uint64_t(n_slices));
-    p.group_bad = reinterpret_cast<uint32_t *>(ws);
-    ws += est::align256(4 * uint64_t(n_groups));
-    const uint64_t rows = est::n_rows(total_chunks, est::kWindow);
-    p.row32 = reinterpret_cast<uint32_t *>(ws);
-    p.row16 = reinterpret_cast<uint16_t *>(ws + rows * est::kKeysPad * 4);
+    p.slice_group = reinterpret_cast<uint32_t *>(ws + L.slice_group);
+    p.group_bad = reinterpret_cast<uint32_t *>(ws + L.group_bad);
+    p.row32 = reinterpret_cast<uint32_t *>(ws + L.row32);
+    p.row16 = reinterpret_cast<uint16_t *>(ws + L.row16);
     p.recs_out = recs_out; p.status = status;
     p.n_slices = n_slices; p.n_groups = n_groups; p.total_chunks = total_chunks;
     const uint32_t n_windows = (total_chunks + est::kWindow - 1) / est::kWindow;

@@ -4,7 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <list>
+#include <mutex>
+
 #include "../../include/avrecode_ms_amd.h"
+#include "avr_layout.h"
 
 // No-op records: what the packer and the generators pad a slice's last chunk (and a tile's
 // shorter lanes) with, so the encode kernels never test a record index against n_bins.
@@ -77,6 +81,38 @@ inline bool no_hint() { return test_hooks().no_hint || env().no_hint; }
 //     the context chains are cut into as many segments as keep ALL of them in one round of workgroups (0 = 1).
 struct DenseHint { uint32_t rows; uint32_t *host_count; uint32_t *host_retry; uint32_t sharing = 0; };
 
+// Something the library keeps per (device, stream): made on first use, under the pool's mutex, and kept -- work on one stream is
+// ordered, so consecutive calls may share it -- until forget() releases what is kept for a stream that is going away.
+template <class T>
+class StreamPool {
+    struct Slot { int dev; hipStream_t s; T x; };
+    std::list<Slot> slots_;                                      // a list: the T a call got stays where it is while others are added
+    std::mutex mu_;
+public:
+    // the T of (current device, s); a new one is filled by make(T &), and is not kept if that fails
+    template <class Make>
+    hipError_t get(hipStream_t s, T **out, Make make) {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        std::lock_guard<std::mutex> lock(mu_);
+        for (Slot &x : slots_)
+            if (x.dev == dev && x.s == s) { *out = &x.x; return hipSuccess; }
+        T fresh{};
+        if ((e = make(fresh)) != hipSuccess) return e;
+        slots_.push_back(Slot{dev, s, fresh});
+        *out = &slots_.back().x;
+        return hipSuccess;
+    }
+    // every T kept for s, on whatever device: destroy(T &), then gone
+    template <class Destroy>
+    void forget(hipStream_t s, Destroy destroy) {
+        std::lock_guard<std::mutex> lock(mu_);
+        for (auto it = slots_.begin(); it != slots_.end();)
+            if (it->s == s) { destroy(it->x); it = slots_.erase(it); } else ++it;
+    }
+};
+
 // what the library keeps per (device, stream) -- the renumbering's scratch, K2p's second stream and events -- released: call before the stream is destroyed
 void forget_stream(hipStream_t s);
 void forget_part_streams(hipStream_t s);                      // avr_api.cpp: the streams of avr_cabac_encode_chunked_device_parts kept for s
@@ -126,25 +162,19 @@ hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_s
 hipError_t launch_compact(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
                           const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense);
 
-size_t k1p_workspace_bytes(size_t n_slices, uint32_t n_states, const avr_chunk_plan *pl);
-hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                      uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                      void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                      uint8_t *final_states, const DenseHint *hint = nullptr);
-hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                            uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                            void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                            uint8_t *final_states);
+// workspace of the three whole-path launchers below: k1p_layout(n_slices, n_states, pl).total bytes (avr_layout.h, as every workspace here)
+// the caller's arrays of a K1p job, which travel through the launchers together
+struct K1pIo { const uint8_t *init_states; uint8_t *out; const uint64_t *out_off; uint32_t *out_len; int32_t *status; uint8_t *final_states; };
+hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                      uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io, const DenseHint *hint = nullptr);
+hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                            uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io);
 // the same from one-byte records (rec_off in bytes, multiples of 16; n_states <= AVR_MAX_STATES8): no census, no wait; workspace as above
-hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
-                       uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                       uint8_t *final_states);
-size_t k1p_resolve_workspace_bytes(size_t n_slices, uint32_t n_states, const avr_chunk_plan *pl);
+hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                       uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io);
 hipError_t launch_k1p_resolve(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                               uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
                               void *workspace, uint8_t *codes, int32_t *status, uint8_t *final_states);
-size_t k1p_code_workspace_bytes(size_t n_slices, const avr_chunk_plan *pl);
 hipError_t launch_k1p_code(hipStream_t s, const uint8_t *codes, const uint32_t *n_bins, uint32_t n_slices,
                            const avr_chunk_plan *pl, void *workspace, uint8_t *out, const uint64_t *out_off,
                            uint32_t *out_len, int32_t *status);
@@ -152,12 +182,10 @@ hipError_t launch_cabac_encode_codes(hipStream_t s, const uint8_t *codes, const 
                                      const uint32_t *order, uint32_t n_slices, uint8_t *out, const uint64_t *out_off,
                                      uint32_t *out_len, int32_t *status, int32_t want_status = AVR_SLICE_OK);
 // K2 for few, long slices (avr_k2p.hip): range recurrence per slice, coding per chunk into byte sums, carries + finish
-size_t k2p_workspace_bytes(size_t n_slices, uint32_t total_chunks, uint64_t out_total);
 hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
                       const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, uint64_t out_total,
                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);
 // the compress direction's estimators (avr_est.hip): key records -> K2 range records, per group of slices; never waits
-size_t est_workspace_bytes(size_t n_slices, size_t n_groups, uint32_t total_chunks);
 hipError_t launch_est_resolve(hipStream_t s, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
                               const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in, uint8_t *est_out,
                               const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, void *workspace,

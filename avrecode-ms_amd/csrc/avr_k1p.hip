@@ -69,7 +69,6 @@ struct TileCodes {
     __device__ __forceinline__ U4 load16(uint32_t i) const { return *reinterpret_cast<const U4 *>(base + at(i)); }
     __device__ __forceinline__ uint32_t byte(uint32_t i) const { return base[at(i) + (i & 15u)]; }
 };
-__host__ __device__ inline uint64_t tile_codes_bytes(uint32_t total_chunks) { return (uint64_t(total_chunks) + 63) / 64 * 64 * 1024; }
 
 // ------------------------------------------------------------------ phase A
 //
@@ -178,7 +177,6 @@ __global__ __launch_bounds__(1024) void k_k1p_densemap(const uint32_t *used, uin
 
 // State after n = 0 .. 8 bins, per state and bin pattern (first bin in the low bit; cabac_code.h:43-47):
 //   tn[(128 << n) - 128 + (st << n | bits)],  bits < 2^n                           (kTnBytes in all)
-constexpr uint32_t kTnBytes = 128 * 511;
 __global__ __launch_bounds__(256) void k_k1p_tn(uint8_t *tn) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= kTnBytes) return;
@@ -571,20 +569,13 @@ __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint3
 //                     between with more than kSegBits bins whose walks did not meet (nothing forbids it) is simply walked again,
 //                     chunk by chunk, by the lanes that need its exit state.
 // Batches of short slices (a segment would be a chunk or two) keep k_k1p_ctxchain, the start-to-end walk.
-constexpr uint32_t kMaxChainSegs = 16, kSegWaves = 16;           // 16 waves share the 64 KiB look-up table: two such workgroups per CU
+constexpr uint32_t kSegWaves = 16;                               // 16 waves share the 64 KiB look-up table: two such workgroups per CU (kMaxChainSegs: avr_layout.h)
 // How many segments (r4): as many as keep every wave of the launch resident at once -- the chip holds 8 192 of these waves (two workgroups
 // of 16 a CU), a launch takes as long as its longest lane's walk, and a second round of workgroups would double that.  Lanes are dealt
 // 64 (slice, context) pairs to a wave across slice boundaries (round 3 gave a slice's 86 contexts two waves of 43 lanes): 688 full waves a
 // segment for config 2 instead of 1 024, which is what lets its chains be cut in 11 instead of 8.
 constexpr uint32_t kChainWaveSlots = 8192;
-constexpr uint32_t kSegBits = 128;                               // bins a segment's bit string holds
-struct alignas(16) SegSummary {
-    uint64_t bits[2];         // the segment's bins of this context, first bin in bit 0 of bits[0] (valid when n_bins <= kSegBits)
-    uint32_t n_bins;
-    uint8_t exit_state;       // state after the segment when the walks met
-    uint8_t met;              // 1: the walks met (exit_state valid, chunks from met_chunk on are noted)
-    uint16_t met_chunk;       // first chunk of the segment (relative to its start) whose entry state is noted; segment length if none
-};
+// (kSegBits and SegSummary, what a segment leaves behind: avr_layout.h, which sizes the workspace by it)
 
 // One chunk's step of a context's chain for NS states at once: the context's bins of the chunk are bits [pos, end) of the chunk's
 // bit string (window w: 128 bits from dword pos / 32), taken eight per look-up.  Same structure as k_k1p_ctxchain's step.
@@ -1511,31 +1502,33 @@ __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_
 }
 
 // ------------------------------------------------------------------ launcher
+//
+// Where everything lies in the workspaces is avr_layout.h's business: ResolveLayout (phase A), CodeLayout (phases B-D) and
+// K1pLayout (the whole path: code buffer, then the two).  The launchers take every pointer from those structs.
 
-namespace {
-inline uint64_t up256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
+// What kind of input a job has, and the one place a Plan is made from the caller's pointers.
+enum class Records { kTwoByte, kOneByte, kNone };                // kNone: resolved codes only (phases B-D)
+static Plan make_plan(Records kind, const void *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_states,
+                      const avr_chunk_plan *pl) {
+    Plan p{};
+    if (kind == Records::kTwoByte) p.recs = static_cast<const uint16_t *>(recs);
+    if (kind == Records::kOneByte) p.recs8 = static_cast<const uint8_t *>(recs);
+    p.rec_off = rec_off; p.n_bins = n_bins;
+    p.res_off = pl->res_off; p.dig_off = pl->dig_off;
+    p.chunk_base = pl->chunk_base; p.chunk_slice = pl->chunk_slice; p.blk_base = pl->blk_base; p.blk_slice = pl->blk_slice;
+    p.n_states = kind == Records::kOneByte ? n_states : 0;       // one-byte selectors are dense already; two-byte: known after the census
+    p.ns_full = n_states;
+    return p;
 }
 
-// Phase A: records + initial states -> resolved codes `res` (slice i at res + res_off[i]).
-// `w` is workspace (per-chunk bit strings, end positions and entry states, tables), laid out for the
-// caller's context count; the kernels index it by the dense count, which is known after the census
-// (the one host round trip of the path: four bytes, to size the later launches).
-struct ResolveLayout {
-    uint64_t lbits, lend, est, stretch, meta, summ, total;
+// What one launch_resolve differs from another in.
+struct ResolveMode {
+    const DenseHint *hint = nullptr;         // the caller's guess of the dense count (DenseHint), or none: ask the device and wait
+    uint32_t census_stride = 1;              // the census samples one cache line in so many (1: every record is counted)
+    bool second_pass = false;                // the slices the first pass set aside, once more: final_states are not initialised again
+    uint32_t *retry_count = nullptr;         // (first pass of a sampled census, no hint) the number of slices set aside goes here, and the call waits for it
+    bool tile_codes = false;                 // `res` is the path's own wave-interleaved buffer (TileCodes), not the caller's slice-major one
 };
-static inline ResolveLayout resolve_layout(size_t n_slices, uint32_t ns, const avr_chunk_plan *pl) {
-    ResolveLayout L;
-    uint64_t at = 0;
-    auto take = [&](uint64_t bytes) { const uint64_t o = at; at += up256(bytes); return o; };
-    L.lbits = take(uint64_t(pl->total_chunks + 64) * 128);       // + 64 chunks: the chains read a few chunks ahead, unconditionally
-    L.lend = take(uint64_t(pl->total_chunks + 64) * ns * 2 + 256) + 128;     // a pad in front: k_k1p_ctxchain reads lend[-1]
-    L.est = take(uint64_t(pl->total_chunks) * ((ns + 3) / 4) * 4 + 16);
-    L.stretch = take(uint64_t(pl->total_chunks) * sizeof(Stretch));
-    L.meta = take(256 + 2048 + 2048 + kTnBytes);                 // used[32] + n_dense, table[1024], index[1024], tn
-    L.summ = take(uint64_t(n_slices) * ns * kMaxChainSegs * sizeof(SegSummary));    // the segmented chains' summaries
-    L.total = at;
-    return L;
-}
 
 // k_k1p_tn's table is a constant: made once per device (on the stream of the first call that needs it, which every
 // later call is ordered behind only by its own use of the device: the event makes that explicit) and kept.
@@ -1560,11 +1553,14 @@ static hipError_t tn_table(hipStream_t s, const uint8_t **out) {
     return hipStreamWaitEvent(s, x.ready, 0);
 }
 
-static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const uint8_t *init_states,
-                                 const avr_chunk_plan *pl, uint8_t *w, uint8_t *res, int32_t *status, uint8_t *final_states,
-                                 uint32_t max_stretch, const Stretch **stretch_out, const DenseHint *hint = nullptr,
-                                 uint32_t stride = 1, bool second_pass = false, uint32_t *retry_count = nullptr,
-                                 bool tile_codes = false, bool r8 = false) {
+// Phase A: records + initial states -> resolved codes `res` (slice i at res + res_off[i], or wave-interleaved: mode.tile_codes).
+// `w` is a ResolveLayout for the caller's context count; the kernels index it by the dense count, which is known after the
+// census (the one host round trip of the path: four bytes, to size the later launches).
+static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const avr_chunk_plan *pl, uint8_t *w, uint8_t *res,
+                                 const K1pIo &io, uint32_t max_stretch, const Stretch **stretch_out, const ResolveMode &mode) {
+    const uint8_t *init_states = io.init_states; int32_t *status = io.status; uint8_t *final_states = io.final_states;
+    const DenseHint *hint = mode.hint;
+    const bool r8 = p.recs8 != nullptr;
     const uint32_t ns = p.ns_full;
     const ResolveLayout L = resolve_layout(n_slices, ns, pl);
     uint32_t *lbits = reinterpret_cast<uint32_t *>(w + L.lbits);
@@ -1580,7 +1576,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
     p.index = index;
     hipError_t e;
     if ((e = hipMemsetAsync(used, 0, 256, s)) != hipSuccess) return e;
-    if (final_states && ns && !second_pass &&
+    if (final_states && ns && !mode.second_pass &&
         (e = hipMemcpyAsync(final_states, init_states, size_t(n_slices) * ns, hipMemcpyDeviceToDevice, s)) != hipSuccess)
         return e;                                                // contexts without bins keep their state
     uint32_t n_states = 0;
@@ -1591,7 +1587,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         p.index = nullptr;
         if ((e = tn_table(s, &tn)) != hipSuccess) return e;
     } else {
-        hipLaunchKernelGGL(k_k1p_census, dim3((pl->total_blocks + kCensusBlocks - 1) / kCensusBlocks), dim3(256), 0, s, p, pl->total_blocks, status, used, stride);
+        hipLaunchKernelGGL(k_k1p_census, dim3((pl->total_blocks + kCensusBlocks - 1) / kCensusBlocks), dim3(256), 0, s, p, pl->total_blocks, status, used, mode.census_stride);
         hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
         if ((e = tn_table(s, &tn)) != hipSuccess) return e;
         if (hint && hint->rows) {                                    // sized by the caller's guess, checked by the caller afterwards (DenseHint)
@@ -1637,11 +1633,11 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         // How many slices k_k1p_local set aside for the second pass.  Read here, not at the end of the pass: the kernels that
         // follow are launched while the device is still busy with this one's successors only for a moment, where a wait
         // after the last kernel would leave the device idle until the caller's next launch.
-        if (stride > 1 && !second_pass) {
+        if (mode.census_stride > 1 && !mode.second_pass) {
             if (hint && hint->rows && hint->host_retry) {        // the caller looks when it waits (DenseHint)
                 if ((e = hipMemcpyAsync(hint->host_retry, n_retry, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-            } else if (retry_count) {
-                if ((e = hipMemcpyAsync(retry_count, n_retry, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+            } else if (mode.retry_count) {
+                if ((e = hipMemcpyAsync(mode.retry_count, n_retry, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
                 if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
             }
         }
@@ -1684,7 +1680,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
     const uint32_t per_wave = ((n_states + 8) / 4) * 256;
     const uint32_t replay_waves = per_wave * 4 <= 48 * 1024 ? 4 : per_wave * 2 <= 48 * 1024 ? 2 : 1;
     const uint32_t replay_lds = replay_waves * per_wave;
-    auto replay = r8 ? k_k1p_replay<true, true> : tile_codes ? k_k1p_replay<true, false> : k_k1p_replay<false, false>;   // (r8: tile codes only)
+    auto replay = r8 ? k_k1p_replay<true, true> : mode.tile_codes ? k_k1p_replay<true, false> : k_k1p_replay<false, false>;   // (r8: tile codes only)
     if (replay_lds > 48 * 1024) {
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(replay), hipFuncAttributeMaxDynamicSharedMemorySize, int(replay_lds));
         if (e != hipSuccess) return e;
@@ -1694,29 +1690,30 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
     return hipGetLastError();
 }
 
-// Phases B-D: resolved codes -> bytes.  `w` is workspace for stretches, entries, totals, digit sums.
+// Phases B-D: resolved codes -> bytes.  `w` is a CodeLayout.
 // `have` != nullptr: the stretch summaries (phase B1) have been made already, by k_k1p_replay.
 static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, const avr_chunk_plan *pl, uint8_t *w,
-                              const uint8_t *res, uint32_t max_stretch, uint8_t *out, const uint64_t *out_off,
-                              uint32_t *out_len, int32_t *status, const Stretch *have = nullptr, bool tile_codes = false) {
-    Stretch *st_own = reinterpret_cast<Stretch *>(w);        w += up256(uint64_t(pl->total_chunks) * sizeof(Stretch));
+                              const uint8_t *res, uint32_t max_stretch, const K1pIo &io, const Stretch *have = nullptr,
+                              bool tile_codes = false) {
+    const CodeLayout L = code_layout(n_slices, pl);
+    Stretch *st_own = reinterpret_cast<Stretch *>(w + L.stretch);
     const Stretch *st = have ? have : st_own;
-    Entry *en = reinterpret_cast<Entry *>(w);                w += up256(uint64_t(pl->total_chunks) * sizeof(Entry));
-    SliceTotals *tot = reinterpret_cast<SliceTotals *>(w);   w += up256(n_slices * sizeof(SliceTotals));
-    uint32_t *S = reinterpret_cast<uint32_t *>(w);               w += up256(pl->dig_total * 4 + 16);
+    Entry *en = reinterpret_cast<Entry *>(w + L.entry);
+    SliceTotals *tot = reinterpret_cast<SliceTotals *>(w + L.totals);
+    uint32_t *S = reinterpret_cast<uint32_t *>(w + L.sums);
     const uint32_t chunk_blocks = (pl->total_chunks + 255) / 256;
     if (!have) {
         // codes from the caller, slice-major: B1 reads them lane by lane once and leaves a wave-interleaved copy for phase C
-        uint8_t *tile = w;
-        hipLaunchKernelGGL(k_k1p_b1, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, status, st_own, max_stretch, tile);
+        uint8_t *tile = w + L.tile;
+        hipLaunchKernelGGL(k_k1p_b1, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, io.status, st_own, max_stretch, tile);
         res = tile;
         tile_codes = true;
     }
-    hipLaunchKernelGGL(k_k1p_b2, dim3(n_slices), dim3(256), 0, s, p, status, st, en, tot, S);
+    hipLaunchKernelGGL(k_k1p_b2, dim3(n_slices), dim3(256), 0, s, p, io.status, st, en, tot, S);
     if (tile_codes) hipLaunchKernelGGL(k_k1p_c<true>, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
     else hipLaunchKernelGGL(k_k1p_c<false>, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
     const uint32_t force_retry_every = test_hooks().k1p_force_retry_every;   // test build only, see k_k1p_d
-    hipLaunchKernelGGL(k_k1p_d, dim3(n_slices), dim3(256), 0, s, p, tot, S, out, out_off, out_len, status, force_retry_every);
+    hipLaunchKernelGGL(k_k1p_d, dim3(n_slices), dim3(256), 0, s, p, tot, S, io.out, io.out_off, io.out_len, io.status, force_retry_every);
     return hipGetLastError();
 }
 
@@ -1734,145 +1731,119 @@ hipError_t launch_cabac_encode_codes(hipStream_t s, const uint8_t *codes, const 
     return hipGetLastError();
 }
 
-static inline uint64_t resolve_ws_bytes(size_t n_slices, uint32_t n_states, const avr_chunk_plan *pl) {
-    return resolve_layout(n_slices, n_states, pl).total;
-}
-
-size_t k1p_code_workspace_bytes(size_t n_slices, const avr_chunk_plan *pl);
-// the code buffer between the two stages of launch_k1p: interleaved by tiles of 64 chunks (TileCodes)
-static inline uint64_t codes_bytes(const avr_chunk_plan *pl) {
-    const uint64_t tiled = tile_codes_bytes(pl->total_chunks), linear = pl->res_total + 32;
-    return tiled > linear ? tiled : linear;
-}
-size_t k1p_workspace_bytes(size_t n_slices, uint32_t n_states, const avr_chunk_plan *pl) {
-    return size_t(up256(codes_bytes(pl)) + resolve_ws_bytes(n_slices, n_states, pl)) + k1p_code_workspace_bytes(n_slices, pl);
-}
-
 constexpr uint32_t kK1pCensusStride = 16;
 
 static uint32_t census_stride() {
     return test_hooks().census_stride ? test_hooks().census_stride : kK1pCensusStride;
 }
 
-// One pass of the whole path over the slices whose status is AVR_SLICE_OK.
-static hipError_t k1p_pass(hipStream_t s, const Plan &p, uint32_t n_slices, const uint8_t *init_states, uint32_t n_states,
-                           const avr_chunk_plan *pl, uint8_t *w, uint8_t *res, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
-                           int32_t *status, uint8_t *final_states, const DenseHint *hint, uint32_t stride, bool second_pass,
-                           uint32_t *retry_count) {
+// A job of the whole path (launch_k1p, launch_k1p_retry, launch_k1p8): its plan, and its K1pLayout in the caller's workspace.
+// The codes between the two stages stay inside the call: wave-interleaved (TileCodes).
+struct K1pJob { Plan p; uint32_t n_slices; const avr_chunk_plan *pl; uint8_t *codes, *resolve_ws, *code_ws; };
+static K1pJob k1p_job(Records kind, const void *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                      uint32_t n_states, const avr_chunk_plan *pl, void *workspace) {
+    const K1pLayout L = k1p_layout(n_slices, n_states, pl);
+    uint8_t *w = static_cast<uint8_t *>(workspace);
+    return K1pJob{make_plan(kind, recs, rec_off, n_bins, n_states, pl), n_slices, pl, w + L.codes, w + L.resolve, w + L.code};
+}
+
+// Both stages of a job over the slices whose status is AVR_SLICE_OK; what comes after them is the caller's.
+static hipError_t k1p_stages(hipStream_t s, const K1pJob &j, const K1pIo &io, ResolveMode mode) {
     const Stretch *st = nullptr;
-    // the codes between the two stages stay inside this call: wave-interleaved (TileCodes)
-    hipError_t e = launch_resolve(s, p, n_slices, init_states, pl, w, res, status, final_states, kMaxStretch, &st, hint, stride, second_pass,
-                                  retry_count, true);
+    mode.tile_codes = true;
+    hipError_t e = launch_resolve(s, j.p, j.n_slices, j.pl, j.resolve_ws, j.codes, io, kMaxStretch, &st, mode);
     if (e != hipSuccess) return e;
-    w += resolve_ws_bytes(n_slices, n_states, pl);
-    e = launch_code(s, p, n_slices, pl, w, res, kMaxStretch, out, out_off, out_len, status, st, true);
+    return launch_code(s, j.p, j.n_slices, j.pl, j.code_ws, j.codes, kMaxStretch, io, st, true);
+}
+
+// One pass of the whole path from two-byte records.
+static hipError_t k1p_pass(hipStream_t s, const K1pJob &j, const K1pIo &io, const ResolveMode &mode) {
+    const hipError_t e = k1p_stages(s, j, io, mode);
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;    // (test hook: the hand-overs stay visible, uncoded)
     // slices the scheme declined (status AVR_SLICE_RETRY_SERIAL) are coded by the serial kernel
-    return launch_cabac_encode(false, s, p.recs, p.rec_off, p.n_bins, nullptr, n_slices, init_states, n_states, out, out_off,
-                               out_len, status, nullptr, AVR_SLICE_RETRY_SERIAL);
+    return launch_cabac_encode(false, s, j.p.recs, j.p.rec_off, j.p.n_bins, nullptr, j.n_slices, io.init_states, j.p.ns_full, io.out,
+                               io.out_off, io.out_len, io.status, nullptr, AVR_SLICE_RETRY_SERIAL);
 }
 
 // The second pass: the slices k_k1p_local set aside (a bin in a context the sampled census missed) once more, with every
 // record counted; the finished ones are parked under AVR_SLICE_DONE meanwhile, which every kernel of the path skips.
-static hipError_t k1p_second_pass(hipStream_t s, const Plan &p, uint32_t n_slices, const uint8_t *init_states, uint32_t n_states,
-                                  const avr_chunk_plan *pl, uint8_t *w, uint8_t *res, uint8_t *out, const uint64_t *out_off,
-                                  uint32_t *out_len, int32_t *status, uint8_t *final_states, bool code) {
+// `pass`: what to run on them.
+template <class Pass>
+static hipError_t k1p_second_pass(hipStream_t s, uint32_t n_slices, int32_t *status, Pass pass) {
     const dim3 grid((n_slices + 255) / 256), block(256);
     hipLaunchKernelGGL(k_k1p_swap, grid, block, 0, s, status, n_slices, AVR_SLICE_OK, AVR_SLICE_DONE, AVR_SLICE_RETRY_CENSUS, AVR_SLICE_OK);
-    hipError_t e = code ? k1p_pass(s, p, n_slices, init_states, n_states, pl, w, res, out, out_off, out_len, status, final_states, nullptr, 1,
-                                   true, nullptr)
-                        : launch_resolve(s, p, n_slices, init_states, pl, w, res, status, final_states, kMaxStretch, nullptr, nullptr, 1, true);
+    ResolveMode mode;
+    mode.second_pass = true;
+    const hipError_t e = pass(mode);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_k1p_swap, grid, block, 0, s, status, n_slices, AVR_SLICE_DONE, AVR_SLICE_OK, AVR_SLICE_DONE, AVR_SLICE_OK);
     return hipGetLastError();
 }
 
-hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                      uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                      void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                      uint8_t *final_states, const DenseHint *hint) {
+hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                      uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io, const DenseHint *hint) {
     if (n_slices == 0) return hipSuccess;
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    uint8_t *res = w;                                        w += up256(codes_bytes(pl));
-    const Plan p{recs, rec_off, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
-                 pl->dig_off, 0, n_states, nullptr, nullptr};
-    const uint32_t stride = census_stride();
+    const K1pJob j = k1p_job(Records::kTwoByte, recs, rec_off, n_bins, n_slices, n_states, pl, workspace);
+    auto pass = [&](const ResolveMode &mode) { return k1p_pass(s, j, io, mode); };
     uint32_t retry = 0;
     if (hint && hint->host_retry) *hint->host_retry = 0;
-    hipError_t e = k1p_pass(s, p, n_slices, init_states, n_states, pl, w, res, out, out_off, out_len, status, final_states, hint, stride, false,
-                            &retry);
+    ResolveMode mode;
+    mode.hint = hint;
+    mode.census_stride = census_stride();
+    mode.retry_count = &retry;
+    const hipError_t e = pass(mode);
     if (e != hipSuccess || !retry) return e;
-    return k1p_second_pass(s, p, n_slices, init_states, n_states, pl, w, res, out, out_off, out_len, status, final_states, true);
+    return k1p_second_pass(s, n_slices, io.status, pass);
 }
 
-hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                            uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                            void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                            uint8_t *final_states) {
+hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                            uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io) {
     if (n_slices == 0) return hipSuccess;
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    uint8_t *res = w;                                        w += up256(codes_bytes(pl));
-    const Plan p{recs, rec_off, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
-                 pl->dig_off, 0, n_states, nullptr, nullptr};
-    return k1p_second_pass(s, p, n_slices, init_states, n_states, pl, w, res, out, out_off, out_len, status, final_states, true);
+    const K1pJob j = k1p_job(Records::kTwoByte, recs, rec_off, n_bins, n_slices, n_states, pl, workspace);
+    return k1p_second_pass(s, n_slices, io.status, [&](const ResolveMode &mode) { return k1p_pass(s, j, io, mode); });
 }
 
-// The two stages on their own: phase A into a caller-owned code buffer ...
-size_t k1p_resolve_workspace_bytes(size_t n_slices, uint32_t n_states, const avr_chunk_plan *pl) {
-    return size_t(resolve_ws_bytes(n_slices, n_states, pl));
-}
+// The two stages on their own: phase A into a caller-owned code buffer (workspace: a ResolveLayout) ...
 hipError_t launch_k1p_resolve(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                               uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
                               void *workspace, uint8_t *codes, int32_t *status, uint8_t *final_states) {
     if (n_slices == 0) return hipSuccess;
-    const Plan p{recs, rec_off, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
-                 pl->dig_off, 0, n_states, nullptr, nullptr};
+    const Plan p = make_plan(Records::kTwoByte, recs, rec_off, n_bins, n_states, pl);
+    const K1pIo io{init_states, nullptr, nullptr, nullptr, status, final_states};       // no bytes come out of phase A
     uint8_t *w = static_cast<uint8_t *>(workspace);
-    const uint32_t stride = census_stride();
+    auto resolve = [&](const ResolveMode &mode) { return launch_resolve(s, p, n_slices, pl, w, codes, io, kMaxStretch, nullptr, mode); };
     uint32_t retry = 0;
-    hipError_t e = launch_resolve(s, p, n_slices, init_states, pl, w, codes, status, final_states, kMaxStretch, nullptr, nullptr, stride, false,
-                                  &retry);
+    ResolveMode mode;
+    mode.census_stride = census_stride();
+    mode.retry_count = &retry;
+    const hipError_t e = resolve(mode);
     if (e != hipSuccess || !retry) return e;
-    return k1p_second_pass(s, p, n_slices, init_states, n_states, pl, w, codes, nullptr, nullptr, nullptr, status, final_states, false);
+    return k1p_second_pass(s, n_slices, status, resolve);
 }
 // The one-byte form (AVR_KIND_CABAC8, avr_cabac8_encode_chunked_device): the same phases on p.recs8, without the census, the
 // renumbering, the second pass and the host round trip (the selectors are dense ids below n_states <= AVR_MAX_STATES8 already):
 // everything is enqueued, nothing waits.  The slices phase D hands over are coded by the serial coder from the resolved codes this
 // call made (k_cabac_encode_codes on the wave-interleaved buffer): same bytes as from the records, and no two-byte copy of them.
-hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
-                       uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                       uint8_t *final_states) {
+hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
+                       uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io) {
     if (n_slices == 0) return hipSuccess;
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    uint8_t *res = w;                                        w += up256(codes_bytes(pl));
-    const Plan p{nullptr, rec_off, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
-                 pl->dig_off, n_states, n_states, nullptr, nullptr, recs8};
-    const Stretch *st = nullptr;
-    hipError_t e = launch_resolve(s, p, n_slices, init_states, pl, w, res, status, final_states, kMaxStretch, &st, nullptr, 1, false,
-                                  nullptr, true, true);
-    if (e != hipSuccess) return e;
-    w += resolve_ws_bytes(n_slices, n_states, pl);
-    e = launch_code(s, p, n_slices, pl, w, res, kMaxStretch, out, out_off, out_len, status, st, true);
+    const K1pJob j = k1p_job(Records::kOneByte, recs8, rec_off, n_bins, n_slices, n_states, pl, workspace);
+    const hipError_t e = k1p_stages(s, j, io, ResolveMode{});
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
-    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((n_slices + 63) / 64), dim3(64), 0, s, res, nullptr, pl->chunk_base, n_bins,
-                       nullptr, n_slices, out, out_off, out_len, status, int32_t(AVR_SLICE_RETRY_SERIAL));
+    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((n_slices + 63) / 64), dim3(64), 0, s, j.codes, nullptr, pl->chunk_base, n_bins,
+                       nullptr, n_slices, io.out, io.out_off, io.out_len, io.status, int32_t(AVR_SLICE_RETRY_SERIAL));
     return hipGetLastError();
 }
 
 // ... and phases B-D from resolved codes (no stretch is declined for its length here: a stretch without an
-// LPS is simply walked to its end by one lane); a slice phase D hands back is coded by k_cabac_encode_codes
-size_t k1p_code_workspace_bytes(size_t n_slices, const avr_chunk_plan *pl) {
-    return size_t(up256(uint64_t(pl->total_chunks) * sizeof(Stretch)) + up256(uint64_t(pl->total_chunks) * sizeof(Entry)) +
-                  up256(n_slices * sizeof(SliceTotals)) + up256(pl->dig_total * 4 + 16) + up256(tile_codes_bytes(pl->total_chunks)));
-}
+// LPS is simply walked to its end by one lane); a slice phase D hands back is coded by k_cabac_encode_codes (workspace: a CodeLayout)
 hipError_t launch_k1p_code(hipStream_t s, const uint8_t *codes, const uint32_t *n_bins, uint32_t n_slices,
                            const avr_chunk_plan *pl, void *workspace, uint8_t *out, const uint64_t *out_off,
                            uint32_t *out_len, int32_t *status) {
     if (n_slices == 0) return hipSuccess;
-    const Plan p{nullptr, nullptr, n_bins, pl->res_off, pl->chunk_base, pl->chunk_slice, pl->blk_base, pl->blk_slice,
-                 pl->dig_off, 0, 0, nullptr, nullptr};
-    hipError_t e = launch_code(s, p, n_slices, pl, static_cast<uint8_t *>(workspace), codes, 0xffffffffu, out, out_off, out_len, status);
+    const Plan p = make_plan(Records::kNone, nullptr, nullptr, n_bins, 0, pl);
+    const K1pIo io{nullptr, out, out_off, out_len, status, nullptr};
+    hipError_t e = launch_code(s, p, n_slices, pl, static_cast<uint8_t *>(workspace), codes, 0xffffffffu, io);
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
     return launch_cabac_encode_codes(s, codes, pl->res_off, n_bins, nullptr, n_slices, out, out_off, out_len, status,
                                      AVR_SLICE_RETRY_SERIAL);

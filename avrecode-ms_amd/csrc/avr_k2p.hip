@@ -18,9 +18,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <mutex>
-#include <vector>
-
 #include "avr_div.h"
 #include "avr_internal.h"
 #include "avr_k2p.h"
@@ -597,70 +594,47 @@ __global__ __launch_bounds__(64) void k_k2p_finish(K2Plan p, const uint64_t *fin
     }
 }
 
-inline uint64_t up256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
-
 }  // namespace
-
-// workspace: ck_range, ck_pos per chunk; fin_range, fin_pos per slice; 32-bit sums per output byte position
-size_t k2p_workspace_bytes(size_t n_slices, uint32_t total_chunks, uint64_t out_total) {
-    return size_t(up256(uint64_t(total_chunks) * 8) + up256(uint64_t(total_chunks) * 4) + up256(n_slices * 8) + up256(n_slices * 4) + 4096 +
-                  up256(out_total * 4 + 64));
-}
 
 // The second stream pass 2 runs on while pass 1 walks on, with its events: one set per (device, caller's stream), made on
 // first use and kept (work on the caller's stream is ordered, so consecutive calls may share it).
 namespace {
 constexpr uint32_t kMaxSegments = 8;
-struct Side { int dev; hipStream_t main, side; hipEvent_t seg[kMaxSegments], join; };
-std::vector<Side *> g_side_pool;
-std::mutex g_side_mu;
+struct Side { hipStream_t side; hipEvent_t seg[kMaxSegments], join; };
+StreamPool<Side> g_side_pool;
 hipError_t side_stream(hipStream_t s, Side **out) {
-    std::vector<Side *> &pool = g_side_pool;
-    std::mutex &mu = g_side_mu;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mu);
-    for (Side *x : pool)
-        if (x->dev == dev && x->main == s) { *out = x; return hipSuccess; }
-    Side *x = new Side{dev, s, nullptr, {}, nullptr};
-    if ((e = hipStreamCreateWithFlags(&x->side, hipStreamNonBlocking)) != hipSuccess) { delete x; return e; }
-    for (uint32_t k = 0; k < kMaxSegments && e == hipSuccess; k++) e = hipEventCreateWithFlags(&x->seg[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&x->join, hipEventDisableTiming);
-    if (e != hipSuccess) { delete x; return e; }
-    pool.push_back(x);
-    *out = x;
-    return hipSuccess;
+    return g_side_pool.get(s, out, [](Side &x) {
+        hipError_t e = hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking);
+        for (uint32_t k = 0; k < kMaxSegments && e == hipSuccess; k++) e = hipEventCreateWithFlags(&x.seg[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&x.join, hipEventDisableTiming);
+        return e;
+    });
 }
 }  // namespace
 
 // The caller's stream is going away (avr_batch_destroy): what was kept for it -- the second stream and its events -- goes with it.
 void forget_side_stream(hipStream_t s) {
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    for (size_t i = 0; i < g_side_pool.size();) {
-        Side *x = g_side_pool[i];
-        if (x->main != s) { i++; continue; }
-        (void)hipStreamSynchronize(x->side);
-        for (uint32_t k = 0; k < kMaxSegments; k++) (void)hipEventDestroy(x->seg[k]);
-        (void)hipEventDestroy(x->join);
-        (void)hipStreamDestroy(x->side);
-        delete x;
-        g_side_pool.erase(g_side_pool.begin() + long(i));
-    }
+    g_side_pool.forget(s, [](Side &x) {
+        (void)hipStreamSynchronize(x.side);
+        for (uint32_t k = 0; k < kMaxSegments; k++) (void)hipEventDestroy(x.seg[k]);
+        (void)hipEventDestroy(x.join);
+        (void)hipStreamDestroy(x.side);
+    });
 }
 
 hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
                       const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, uint64_t out_total,
                       void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status) {
     if (n_slices == 0) return hipSuccess;
-    (void)out_total;
+    // the workspace is avr_layout.h's K2pLayout
+    const K2pLayout L = k2p_layout(n_slices, total_chunks, out_total);
     uint8_t *w = static_cast<uint8_t *>(workspace);
-    uint64_t *ck_range = reinterpret_cast<uint64_t *>(w);    w += up256(uint64_t(total_chunks) * 8);
-    uint32_t *ck_pos = reinterpret_cast<uint32_t *>(w);      w += up256(uint64_t(total_chunks) * 4);
-    uint64_t *fin_range = reinterpret_cast<uint64_t *>(w);   w += up256(uint64_t(n_slices) * 8);
-    uint32_t *fin_pos = reinterpret_cast<uint32_t *>(w);     w += up256(uint64_t(n_slices) * 4);
-    uint32_t *long_chunks = reinterpret_cast<uint32_t *>(w); w += 4096;     // the hybrid pass 1's threshold, count and list of long slices (at most 1 022)
-    uint32_t *S = reinterpret_cast<uint32_t *>(w);
+    uint64_t *ck_range = reinterpret_cast<uint64_t *>(w + L.ck_range);
+    uint32_t *ck_pos = reinterpret_cast<uint32_t *>(w + L.ck_pos);
+    uint64_t *fin_range = reinterpret_cast<uint64_t *>(w + L.fin_range);
+    uint32_t *fin_pos = reinterpret_cast<uint32_t *>(w + L.fin_pos);
+    uint32_t *long_chunks = reinterpret_cast<uint32_t *>(w + L.long_chunks);    // the hybrid pass 1's threshold, count and list of long slices
+    uint32_t *S = reinterpret_cast<uint32_t *>(w + L.sums);
     const K2Plan p{recs, rec_off, n_bins, chunk_base, chunk_slice, out_off};
     const dim3 slice_grid((n_slices + 63) / 64), chunk_grid((total_chunks + 255) / 256);
     // Segments: an eighth of the average slice each, the last one open-ended (it takes whatever the longer slices have left).

@@ -962,37 +962,13 @@ __global__ __launch_bounds__(64) void k_synth_slices(
 // (One thread per stream: the census of a call and the kernel that reads its table are separate launches with a 4-byte wait between
 // them, so a second host thread enqueueing on the SAME stream in that window would overwrite the table -- as include/avrecode_ms_amd.h
 // says of every device-resident entry point, a stream is used by one thread at a time.)
-namespace {
-struct ScratchSlot { int dev; hipStream_t s; uint8_t *p; };
-std::vector<ScratchSlot> g_scratch;
-std::mutex g_scratch_mu;
-}  // namespace
-static hipError_t stream_scratch(hipStream_t s, uint8_t **out) {
-    using Slot = ScratchSlot;
-    std::vector<Slot> &slots = g_scratch;
-    std::mutex &mu = g_scratch_mu;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mu);
-    for (const Slot &x : slots)
-        if (x.dev == dev && x.s == s) { *out = x.p; return hipSuccess; }
-    uint8_t *p = nullptr;
-    if ((e = hipMalloc(reinterpret_cast<void **>(&p), 256 + 4096)) != hipSuccess) return e;
-    slots.push_back(Slot{dev, s, p});
-    *out = p;
-    return hipSuccess;
-}
+static StreamPool<uint8_t *> g_scratch;
 
 void forget_side_stream(hipStream_t s);                          // avr_k2p.hip
 // A stream is about to be destroyed (avr_batch_destroy): the resources kept per (device, stream) go with it, so that a process that
 // makes and destroys batches (one per file, say) does not collect them.
 void forget_stream(hipStream_t s) {
-    {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        for (size_t i = 0; i < g_scratch.size();)
-            if (g_scratch[i].s == s) { (void)hipFree(g_scratch[i].p); g_scratch.erase(g_scratch.begin() + long(i)); } else i++;
-    }
+    g_scratch.forget(s, [](uint8_t *&p) { (void)hipFree(p); });
     forget_side_stream(s);
 }
 
@@ -1008,13 +984,14 @@ hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, cons
     if (n_slices == 0) return hipSuccess;
     hipError_t err;
     uint32_t n_rows = n_states;
-    uint8_t *scratch = nullptr;                                  // used[32] + n_dense | table[1024] | index[1024]
+    uint8_t **scratch = nullptr;                                 // -> used[32] + n_dense | table[1024] | index[1024]
     const uint16_t *table = nullptr, *index = nullptr;
     bool retry = false;                                          // the census was a sample: a second launch takes what it missed
     if (dense && want_status == AVR_SLICE_OK && n_states > 8 && !no_dense()) {
-        if ((err = stream_scratch(s, &scratch)) != hipSuccess) return err;
-        uint32_t *used = reinterpret_cast<uint32_t *>(scratch);
-        uint16_t *t = reinterpret_cast<uint16_t *>(scratch + 256);
+        err = g_scratch.get(s, &scratch, [](uint8_t *&p) { return hipMalloc(reinterpret_cast<void **>(&p), 256 + 4096); });
+        if (err != hipSuccess) return err;
+        uint32_t *used = reinterpret_cast<uint32_t *>(*scratch);
+        uint16_t *t = reinterpret_cast<uint16_t *>(*scratch + 256);
         if ((err = hipMemsetAsync(used, 0, 256, s)) != hipSuccess) return err;
         const dim3 cgrid(((n_slices + 63) / 64 + kCensusTiles - 1) / kCensusTiles);
         const uint32_t stride = test_hooks().census_stride ? test_hooks().census_stride : kCensusStride;
