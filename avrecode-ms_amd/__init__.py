@@ -40,7 +40,7 @@ NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
 _SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_verify.hip", "avr_api.cpp"]
-_DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_synth.h", "avr_tables.h",
+_DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
                     "avr_verify.h"]
 
 

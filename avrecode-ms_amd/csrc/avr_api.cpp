@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "avr_internal.h"
+#include "avr_plan.h"
 #include "avr_synth.h"
 #include "avr_tables.h"
 
@@ -150,14 +151,14 @@ struct avr_batch {
     PinBuf<uint8_t> h_est_in, h_est_out;
     bool any_est_in = false, est_out_fetched = false;
     DevBuf<uint16_t> d_keys;
-    DevBuf<uint32_t> d_group_first, d_est_chunk_base, d_est_chunk_slice;
+    DevBuf<uint32_t> d_group_first;
     DevBuf<uint8_t> d_est_in, d_est_out, d_est_ws;
 
     // submit / wait: nothing the device reads may be pageable or local to a call
     PinBuf<uint8_t> h_plan;                 // the plan arrays of the run in flight
     size_t plan_used = 0;
     PinBuf<uint32_t> h_ndense;              // [0]: contexts the batch uses, read back behind the kernels
-    std::vector<uint64_t> out_off;          // n+1, bytes in d_out
+    avr::HostPlan hp;                       // of the run in flight: the output regions (out_off: n+1, bytes in d_out), the path's plan arrays
     bool in_flight = false;
     uint32_t dense_hint = 0;                // context rows the previous run of this object needed (0: no run yet)
     uint32_t hint_used = 0;                 // what the run in flight was sized by (0: it asked the device and waited)
@@ -184,6 +185,30 @@ static int stage_h2d(avr_batch *b, T *dst, const T *src, size_t n) {
     AVR_HIP(hipMemcpyAsync(dst, b->h_plan.p + at, bytes, hipMemcpyHostToDevice, b->stream));
     return AVR_OK;
 }
+// What an array of n elements takes of the arena (h_plan) at most: stage_h2d starts each at a multiple of 64.  A run reserves the
+// sum over the arrays it stages, so an array added to a run is added to its sum; avr_batch_wait's dense_off, staged when the run's
+// arrays are consumed, is no larger than the rec_off every run stages.
+template <class T>
+static constexpr size_t staged(size_t n) { return n * sizeof(T) + 64; }
+static size_t staged_plan(const avr::HostPlan &h) { return h.staged_bytes() + 6 * 64; }
+
+// The arrays of the run's plan (b->hp) on their way to the device, each into room of its own there; *plan: the device's view of them.
+// An array the path does not read is empty and stays where it is.  res_total: of res_off, whoever staged it.
+static int stage_plan(avr_batch *b, uint64_t res_total, avr_chunk_plan *plan) {
+    const avr::HostPlan &h = b->hp;
+    auto put = [b](auto &d, const auto &v) { const int rc = d.reserve(v.size()); return rc || v.empty() ? rc : stage_h2d(b, d.p, v.data(), v.size()); };
+    int rc;
+    if ((rc = put(b->d_res_off, h.res_off)) || (rc = put(b->d_dig_off, h.dig_off)) || (rc = put(b->d_chunk_base, h.chunk_base)) ||
+        (rc = put(b->d_blk_base, h.blk_base)) || (rc = put(b->d_chunk_slice, h.chunk_slice)) || (rc = put(b->d_blk_slice, h.blk_slice)))
+        return rc;
+    const bool blocks = !h.blk_base.empty();
+    *plan = {b->d_res_off.p, b->d_chunk_base.p, b->d_chunk_slice.p, blocks ? b->d_blk_base.p : nullptr, blocks ? b->d_blk_slice.p : nullptr,
+             b->d_dig_off.p, res_total, avr::plan_total(h.dig_off), avr::plan_total(h.chunk_base), avr::plan_total(h.blk_base)};
+    return AVR_OK;
+}
+// few, long slices: the intra-slice parallel kernels; many short ones: one lane per slice (avr::want_chunked, or as AVR_K1_PATH says)
+static bool pick_chunked(const avr_batch *b) { return avr::k1_path() ? avr::k1_path() == 2 : avr::want_chunked(b->n_bins.size(), b->total_bins); }
+
 namespace avr {
 // the three environment switches of the library (avr_internal.h), read once
 const Env &env() {
@@ -282,8 +307,8 @@ void avr_batch_destroy(avr_batch *b) {
     b->d_out.release(); b->d_dense.release();
     b->d_res_off.release(); b->d_dig_off.release(); b->d_chunk_base.release(); b->d_chunk_slice.release();
     b->d_blk_base.release(); b->d_blk_slice.release(); b->d_workspace.release();
-    b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release(); b->d_est_chunk_base.release();
-    b->d_est_chunk_slice.release(); b->d_est_in.release(); b->d_est_out.release(); b->d_est_ws.release();
+    b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release();
+    b->d_est_in.release(); b->d_est_out.release(); b->d_est_ws.release();
     b->d_first_bad.release(); b->h_first_bad.release();
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->vev) if (e) (void)hipEventDestroy(e);
@@ -364,7 +389,7 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
     if (kind == AVR_KIND_CABAC_CODES) {
         // Resolved codes live in the same pinned buffer as records would, as bytes: slice i at byte code_off[i] (the
         // res_off of the chunk plan: 16-byte aligned, padded with a group of its own)
-        const uint64_t padded = ((uint64_t(n) + 15) & ~uint64_t(15)) + 16;
+        const uint64_t padded = avr::slice_work_bytes(n);
         if (off + padded > (b->max_bins + 16 * b->max_slices) * sizeof(uint16_t))
             return fail(AVR_ERR_CAPACITY, "batch code buffer full (%zu slices)", b->n_bins.size());
         uint8_t *dst = reinterpret_cast<uint8_t *>(b->h_recs.p) + off;
@@ -445,49 +470,30 @@ static int enqueue_lengths(avr_batch *b, uint32_t n32);
 // A batch of resolved codes: H2D of one byte per bin, K1p phases B-D (or the one-lane-per-slice coder), lengths back.
 static int submit_codes(avr_batch *b, uint32_t n32) {
     const size_t n = n32;
-    std::vector<uint64_t> &out_off = b->out_off;
-    std::vector<uint64_t> dig_off(n + 1, 0);
-    std::vector<uint32_t> chunk_base(n + 1, 0), chunk_slice;
-    out_off.assign(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t nb = b->n_bins[i];
-        out_off[i + 1] = out_off[i] + ((nb + 16 + 7) & ~uint64_t(7));
-        dig_off[i + 1] = dig_off[i] + nb / 2 + 8;
-        const uint32_t nc = uint32_t(std::max<uint64_t>(1, (nb + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS));
-        chunk_base[i + 1] = chunk_base[i] + nc;
-        chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
-    }
-    // few, long slices: the intra-slice parallel kernels; many short ones: one lane per slice (same rule as for records)
-    bool chunked = n <= 32768 && b->total_bins / n >= 8192;
-    if (avr::k1_path()) chunked = avr::k1_path() == 2;
+    avr::fill_plan(b->hp, b->n_bins.data(), n, avr::PlanFor::Codes);
+    const bool chunked = pick_chunked(b);                        // (same rule as for records)
     std::vector<uint32_t> order;
     if (!chunked) {
         std::vector<uint64_t> tile_off;
         plan_tiles(b->n_bins, order, tile_off);                  // longest first: the lanes of a wave finish together
     }
-    const uint64_t total_codes = b->rec_off.back(), total_out = out_off.back();
+    const uint64_t total_codes = b->rec_off.back(), total_out = b->hp.out_off.back();
+    const size_t arena = staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) * 2 + staged_plan(b->hp);       // rec_off, out_off, n_bins, order; the plan
     int rc;
-    if ((rc = b->d_recs.reserve((total_codes + 64) / 2 + 1)) || (rc = b->d_res_off.reserve(n + 1)) || (rc = b->d_dig_off.reserve(n + 1)) ||
-        (rc = b->d_chunk_base.reserve(n + 1)) || (rc = b->d_chunk_slice.reserve(chunk_slice.size())) ||
+    if ((rc = b->d_recs.reserve((total_codes + 64) / 2 + 1)) || (rc = b->d_res_off.reserve(n + 1)) ||
         (rc = b->d_out_off.reserve(n + 1)) || (rc = b->d_dense_off.reserve(n + 1)) || (rc = b->d_n_bins.reserve(n)) ||
         (rc = b->d_order.reserve(n)) || (rc = b->d_out_len.reserve(n)) || (rc = b->d_status.reserve(n)) || (rc = b->d_out.reserve(total_out)) ||
-        (rc = b->h_out_len.reserve(n)) || (rc = b->h_status.reserve(n)) ||
-        (rc = b->h_plan.reserve(64 * 8 + (n + 1) * 36 + chunk_slice.size() * 4)))
+        (rc = b->h_out_len.reserve(n)) || (rc = b->h_status.reserve(n)) || (rc = b->h_plan.reserve(arena)))
         return rc;
-    avr_chunk_plan plan{b->d_res_off.p, b->d_chunk_base.p, b->d_chunk_slice.p, nullptr, nullptr, b->d_dig_off.p,
-                        total_codes, dig_off.back(), chunk_base.back(), 0};
-    const size_t ws = avr::code_layout(n, &plan).total;
-    if ((rc = b->d_workspace.reserve(ws + 256))) return rc;
     hipStream_t s = b->stream;
     b->plan_used = 0;
     b->hint_used = 0;
     AVR_HIP(hipEventRecord(b->ev[0], s));
     AVR_HIP(hipMemcpyAsync(b->d_recs.p, b->h_recs.p, total_codes, hipMemcpyHostToDevice, s));
     AVR_STAGE(b->d_res_off.p, b->rec_off.data(), n + 1);
-    AVR_STAGE(b->d_dig_off.p, dig_off.data(), n + 1);
-    AVR_STAGE(b->d_chunk_base.p, chunk_base.data(), n + 1);
-    AVR_STAGE(b->d_chunk_slice.p, chunk_slice.data(), chunk_slice.size());
-    AVR_STAGE(b->d_out_off.p, out_off.data(), n + 1);
+    avr_chunk_plan plan;                                         // the codes lie as the caller's records would: res_off is rec_off
+    if ((rc = stage_plan(b, total_codes, &plan)) || (rc = b->d_workspace.reserve(avr::code_layout(n, &plan).total + 256))) return rc;
+    AVR_STAGE(b->d_out_off.p, b->hp.out_off.data(), n + 1);
     AVR_STAGE(b->d_n_bins.p, b->n_bins.data(), n);
     if (!chunked) AVR_STAGE(b->d_order.p, order.data(), n);
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
@@ -495,9 +501,8 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     AVR_HIP(hipEventRecord(b->ev[2], s));
     const uint8_t *d_codes = reinterpret_cast<const uint8_t *>(b->d_recs.p);
     if (chunked) {
-        uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
-        AVR_HIP(avr::launch_k1p_code(s, d_codes, b->d_n_bins.p, n32, &plan, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p,
-                                     b->d_status.p));
+        AVR_HIP(avr::launch_k1p_code(s, d_codes, b->d_n_bins.p, n32, &plan, avr::align256(b->d_workspace.p), b->d_out.p,
+                                     b->d_out_off.p, b->d_out_len.p, b->d_status.p));
     } else {
         AVR_HIP(avr::launch_cabac_encode_codes(s, d_codes, b->d_res_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
                                                b->d_out_off.p, b->d_out_len.p, b->d_status.p));
@@ -512,33 +517,24 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
 // padding), the groups' tables after the run left in d_est_out.  Enqueues and returns.
 static int resolve_keys(avr_batch *b, uint32_t n32) {
     const size_t n = n32, n_groups = b->group_first.size();
-    std::vector<uint32_t> chunk_base(n + 1, 0), chunk_slice, group_first(b->group_first);
+    std::vector<uint32_t> group_first(b->group_first);
     group_first.push_back(n32);
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t nc = uint32_t(std::max<uint64_t>(1, (uint64_t(b->n_bins[i]) + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS));
-        chunk_base[i + 1] = chunk_base[i] + nc;
-        chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
-    }
-    const size_t ws = avr::est_layout(n, n_groups, chunk_base.back()).total;
+    const uint32_t total_chunks = b->hp.chunk_base.back();
     int rc;
-    if ((rc = b->d_est_chunk_base.reserve(n + 1)) || (rc = b->d_est_chunk_slice.reserve(chunk_slice.size())) ||
-        (rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(ws + 256)) ||
+    if ((rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(avr::est_layout(n, n_groups, total_chunks).total + 256)) ||
         (rc = b->d_est_out.reserve(n_groups * kEstTable)) || (b->any_est_in && (rc = b->d_est_in.reserve(n_groups * kEstTable))))
         return rc;
     hipStream_t s = b->stream;
-    AVR_STAGE(b->d_est_chunk_base.p, chunk_base.data(), n + 1);
-    AVR_STAGE(b->d_est_chunk_slice.p, chunk_slice.data(), chunk_slice.size());
     AVR_STAGE(b->d_group_first.p, group_first.data(), n_groups + 1);
     if (b->any_est_in) {                                         // through pinned memory: the copy must not read pageable memory after the call
         if ((rc = b->h_est_in.reserve(n_groups * kEstTable))) return rc;
         memcpy(b->h_est_in.p, b->est_in.data(), n_groups * kEstTable);
         AVR_HIP(hipMemcpyAsync(b->d_est_in.p, b->h_est_in.p, n_groups * kEstTable, hipMemcpyHostToDevice, s));
     }
-    uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_est_ws.p) + 255) & ~uintptr_t(255));
     b->est_out_fetched = false;
     AVR_HIP(avr::launch_est_resolve(s, b->d_keys.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p, uint32_t(n_groups),
-                                    b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, b->d_est_chunk_base.p,
-                                    b->d_est_chunk_slice.p, chunk_base.back(), wsp, b->d_recs.p, b->d_status.p));
+                                    b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, b->d_chunk_base.p,
+                                    b->d_chunk_slice.p, total_chunks, avr::align256(b->d_est_ws.p), b->d_recs.p, b->d_status.p));
     return AVR_OK;
 }
 
@@ -569,18 +565,14 @@ static int submit_impl(avr_batch *b, bool use_hint) {
 
     std::vector<uint32_t> order;
     std::vector<uint64_t> tile_off;
-    std::vector<uint64_t> &out_off = b->out_off;
-    out_off.assign(n + 1, 0);
     plan_tiles(b->n_bins, order, tile_off, b->recs8 ? 16 : 8);  // one-byte records: one-byte tiles (the chunked path has no tiles)
-    // worst case is 8 bits per bin for either coder ("output sizing") + stop bytes
-    for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + ((uint64_t(b->n_bins[i]) + 16 + 7) & ~uint64_t(7));
-    const uint64_t total_recs = b->rec_off.back(), total_chunks = tile_off.back(), total_out = out_off.back();
-    const size_t n_tiles = tile_off.size() - 1;
-    // One lane per slice needs tens of thousands of slices to fill the chip; a batch of few, long
-    // slices (a clip with one slice per frame) goes through the intra-slice parallel kernels.
-    bool chunked = n <= 32768 && b->total_bins / n >= 8192;
-    if (avr::k1_path()) chunked = avr::k1_path() == 2;
+    const bool chunked = pick_chunked(b);
     b->last_path = chunked;
+    // the chunk arrays once, whichever of the resolver and K2p reads them
+    avr::fill_plan(b->hp, b->n_bins.data(), n,
+                   chunked && cabac ? avr::PlanFor::K1p : chunked || b->keys ? avr::PlanFor::Chunks : avr::PlanFor::Serial);
+    const uint64_t total_recs = b->rec_off.back(), total_chunks = tile_off.back(), total_out = b->hp.out_off.back();
+    const size_t n_tiles = tile_off.size() - 1;
 
     int rc;
     if ((b->recs8 ? (rc = b->d_recs8.reserve(total_recs + 16)) : (rc = b->d_recs.reserve(total_recs))) || (!chunked && (rc = b->d_tiles.reserve(total_chunks))) ||
@@ -593,10 +585,9 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if (cabac && ((rc = b->d_states.reserve(n * std::max<size_t>(ns, 1))) || (rc = b->d_final.reserve(n * std::max<size_t>(ns, 1))) ||
                   (rc = b->h_final.reserve(n * std::max<size_t>(ns, 1)))))
         return rc;
-    const size_t n_chunks_max = size_t(b->total_bins / AVR_CHUNK_BINS) + n + 1, n_blks_max = size_t(b->total_bins / AVR_SORT_BLOCK_BINS) + n + 1;
-    const size_t n_groups = b->group_first.size();
-    if ((rc = b->h_plan.reserve(64 * 16 + (n + 1) * 64 + (n_tiles + 1) * 8 + (chunked ? (n_chunks_max + n_blks_max) * 4 : 0) +
-                                (b->keys ? (n_chunks_max + n + n_groups + 3) * 4 + 256 : 0)))) return rc;
+    // rec_off, out_off, n_bins; tile_off, order; group_first; the plan's arrays
+    if ((rc = b->h_plan.reserve(staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) + (chunked ? 0 : staged<uint64_t>(n_tiles + 1) + staged<uint32_t>(n)) +
+                                (b->keys ? staged<uint32_t>(b->group_first.size() + 1) : 0) + staged_plan(b->hp)))) return rc;
     if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
     b->verified = b->verify && !cabac;
     if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
@@ -614,7 +605,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if (b->recs8) AVR_HIP(hipMemcpyAsync(b->d_recs8.p, b->h_recs.p, total_recs, hipMemcpyHostToDevice, s));        // one byte a record
     else AVR_HIP(hipMemcpyAsync(b->keys ? b->d_keys.p : b->d_recs.p, b->h_recs.p, total_recs * sizeof(uint16_t), hipMemcpyHostToDevice, s));
     AVR_STAGE(b->d_rec_off.p, b->rec_off.data(), n + 1);
-    AVR_STAGE(b->d_out_off.p, out_off.data(), n + 1);
+    AVR_STAGE(b->d_out_off.p, b->hp.out_off.data(), n + 1);
     AVR_STAGE(b->d_n_bins.p, b->n_bins.data(), n);
     if (!chunked) {
         AVR_STAGE(b->d_tile_off.p, tile_off.data(), n_tiles + 1);
@@ -626,56 +617,21 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     // Both K1 paths renumber a two-byte batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
     // their census pass, the one-lane-per-slice kernel through launch_cabac_encode): records and states go in as they are.
     // One-byte records name dense ids below n_states already: neither one-byte path counts or renumbers.
+    avr_chunk_plan plan;
+    if ((rc = stage_plan(b, avr::plan_total(b->hp.res_off), &plan))) return rc;
+    if (chunked && (rc = b->d_workspace.reserve((cabac ? avr::k1p_layout(n, uint32_t(ns), &plan).total
+                                                       : avr::k2p_layout(n, plan.total_chunks, total_out).total) + 256))) return rc;
     if (b->keys && (rc = resolve_keys(b, n32))) return rc;       // key records: d_keys -> d_recs, inside slot [1] of the timings
+    uint8_t *wsp = avr::align256(b->d_workspace.p);
     if (chunked && !cabac) {
         // K2 for few, long slices: the range recurrence per slice, everything else per chunk (avr_k2p.hip)
-        std::vector<uint32_t> chunk_base(n + 1, 0), chunk_slice;
-        for (size_t i = 0; i < n; i++) {
-            const uint32_t nc = uint32_t(std::max<uint64_t>(1, (uint64_t(b->n_bins[i]) + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS));
-            chunk_base[i + 1] = chunk_base[i] + nc;
-            chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
-        }
-        const size_t ws = avr::k2p_layout(n, chunk_base.back(), total_out).total;
-        if ((rc = b->d_chunk_base.reserve(n + 1)) || (rc = b->d_chunk_slice.reserve(chunk_slice.size())) || (rc = b->d_workspace.reserve(ws + 256)))
-            return rc;
-        AVR_STAGE(b->d_chunk_base.p, chunk_base.data(), n + 1);
-        AVR_STAGE(b->d_chunk_slice.p, chunk_slice.data(), chunk_slice.size());
         AVR_HIP(hipEventRecord(b->ev[2], s));
-        uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
         AVR_HIP(avr::launch_k2p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_chunk_base.p, b->d_chunk_slice.p,
-                                chunk_base.back(), total_out, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p));
+                                plan.total_chunks, total_out, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p));
         if (b->verified && (rc = enqueue_verify(b, n32, false))) return rc;      // over the slice-major records K2p read
     } else if (chunked) {
-        std::vector<uint64_t> res_off(n + 1, 0), dig_off(n + 1, 0);
-        std::vector<uint32_t> chunk_base(n + 1, 0), blk_base(n + 1, 0), chunk_slice, blk_slice;
-        for (size_t i = 0; i < n; i++) {
-            const uint64_t nb = b->n_bins[i];
-            res_off[i + 1] = res_off[i] + ((nb + 15) & ~uint64_t(15)) + 16;
-            dig_off[i + 1] = dig_off[i] + nb / 2 + 8;
-            const uint32_t nc = uint32_t(std::max<uint64_t>(1, (nb + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS));
-            const uint32_t nk = uint32_t(std::max<uint64_t>(1, (nb + AVR_SORT_BLOCK_BINS - 1) / AVR_SORT_BLOCK_BINS));
-            chunk_base[i + 1] = chunk_base[i] + nc;
-            blk_base[i + 1] = blk_base[i] + nk;
-            chunk_slice.insert(chunk_slice.end(), nc, uint32_t(i));
-            blk_slice.insert(blk_slice.end(), nk, uint32_t(i));
-        }
-        if ((rc = b->d_res_off.reserve(n + 1)) || (rc = b->d_dig_off.reserve(n + 1)) || (rc = b->d_chunk_base.reserve(n + 1)) ||
-            (rc = b->d_blk_base.reserve(n + 1)) || (rc = b->d_chunk_slice.reserve(chunk_slice.size())) ||
-            (rc = b->d_blk_slice.reserve(blk_slice.size())))
-            return rc;
-        avr_chunk_plan plan{b->d_res_off.p, b->d_chunk_base.p, b->d_chunk_slice.p, b->d_blk_base.p, b->d_blk_slice.p, b->d_dig_off.p,
-                            res_off.back(), dig_off.back(), chunk_base.back(), blk_base.back()};
-        const size_t ws = avr::k1p_layout(n, uint32_t(ns), &plan).total;
-        if ((rc = b->d_workspace.reserve(ws + 256))) return rc;
         b->plan = plan;
-        AVR_STAGE(b->d_res_off.p, res_off.data(), n + 1);
-        AVR_STAGE(b->d_dig_off.p, dig_off.data(), n + 1);
-        AVR_STAGE(b->d_chunk_base.p, chunk_base.data(), n + 1);
-        AVR_STAGE(b->d_blk_base.p, blk_base.data(), n + 1);
-        AVR_STAGE(b->d_chunk_slice.p, chunk_slice.data(), chunk_slice.size());
-        AVR_STAGE(b->d_blk_slice.p, blk_slice.data(), blk_slice.size());
         AVR_HIP(hipEventRecord(b->ev[2], s));
-        uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
         if (b->recs8)                                            // one-byte records: no census, no guess to check, nothing waits
             AVR_HIP(avr::launch_k1p8(s, b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
                                      avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
@@ -759,8 +715,7 @@ int avr_batch_wait(avr_batch *b) {
             b->info[3] = 1;
         }
         if (b->last_path == 1 && b->h_ndense.p[1]) {             // slices with a context the sampled census missed: their second pass
-            uint8_t *wsp = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(b->d_workspace.p) + 255) & ~uintptr_t(255));
-            AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(b->n_states), &b->plan, wsp,
+            AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(b->n_states), &b->plan, avr::align256(b->d_workspace.p),
                                           avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
             if ((rc = enqueue_lengths(b, n32))) return rc;
             AVR_HIP(hipStreamSynchronize(s));
@@ -771,7 +726,7 @@ int avr_batch_wait(avr_batch *b) {
         if (seen) b->dense_hint = std::min<uint32_t>(uint32_t(b->n_states), seen + 8);   // a little room: the next batch of a stream rarely needs more
     }
     for (size_t i = 0; i < n; i++) {
-        const uint64_t cap = b->out_off[i + 1] - b->out_off[i];
+        const uint64_t cap = b->hp.out_off[i + 1] - b->hp.out_off[i];
         b->dense_off[i + 1] = b->dense_off[i] + std::min<uint64_t>(b->h_out_len.p[i], cap);
     }
     const uint64_t dense_total = b->dense_off.back();

@@ -38,6 +38,33 @@ def plan_tiles(n_bins, records_per_chunk=8):
     return order.to(torch.int32), tile_off
 
 
+def chunk_plan_arrays(n_bins):
+    """The arrays of an avr_chunk_plan for per-slice bin counts (int tensor, any device; no native library needed): a dict of the
+    six tensors, on n_bins' device, and the four totals.  res_off / dig_off (int64), chunk_base / blk_base (int32): exclusive prefix
+    sums with the total appended; chunk_slice / blk_slice (int32): the slice of every chunk / census block.
+    Same rules as fill_plan() in csrc/avr_plan.h (tests/test_plan.py holds the two to each other)."""
+    import torch
+    from . import CHUNK_BINS, SORT_BLOCK_BINS
+    nb = n_bins.to(torch.int64)
+    zero = torch.zeros(1, dtype=torch.int64, device=nb.device)
+    ar = torch.arange(nb.numel(), device=nb.device)
+    n_chunks = torch.clamp((nb + CHUNK_BINS - 1) // CHUNK_BINS, min=1)
+    n_blocks = torch.clamp((nb + SORT_BLOCK_BINS - 1) // SORT_BLOCK_BINS, min=1)
+    res_off = torch.cat([zero, torch.cumsum((nb + 15) // 16 * 16 + 16, 0)])
+    dig_off = torch.cat([zero, torch.cumsum(nb // 2 + 8, 0)])
+    chunk_base = torch.cat([zero, torch.cumsum(n_chunks, 0)]).to(torch.int32)
+    blk_base = torch.cat([zero, torch.cumsum(n_blocks, 0)]).to(torch.int32)
+    t = dict(res_off=res_off, chunk_base=chunk_base, blk_base=blk_base, dig_off=dig_off,
+             chunk_slice=torch.repeat_interleave(ar, n_chunks).to(torch.int32),
+             blk_slice=torch.repeat_interleave(ar, n_blocks).to(torch.int32))
+    return t, (int(res_off[-1]), int(dig_off[-1]), int(chunk_base[-1]), int(blk_base[-1]))
+
+
+def _aligned(t):
+    """t's address rounded up to 256 bytes, as the C ABI wants a workspace (the workspaces here are allocated 256 bytes larger)."""
+    return (t.data_ptr() + 255) // 256 * 256
+
+
 def encode_tiles(kind, tiles, tile_off, n_bins, order, out, out_off, out_len, status,
                  init_states=None, n_states=0, final_states=None, device_index=0):
     """Enqueue K1 (kind 0) or K2 (kind 1) on torch's current stream."""
@@ -204,7 +231,7 @@ class DeviceWorkload:
         _check(L.avr_range_resolve_device(
             self.device_index, _stream_ptr(torch), self.key_flat.data_ptr(), self.rec_off.data_ptr(), self.n_bins.data_ptr(),
             self.n_slices, self.group_first.data_ptr(), self.n_groups, self.est_in.data_ptr() if self.est_in is not None else None,
-            self.est_out.data_ptr(), ctypes.byref(p["plan"]), (p["ws_est"].data_ptr() + 255) // 256 * 256, p["ws_est_bytes"],
+            self.est_out.data_ptr(), ctypes.byref(p["plan"]), _aligned(p["ws_est"]), p["ws_est_bytes"],
             self.rec_flat.data_ptr(), self.status.data_ptr()))
         return self.rec_flat
 
@@ -330,7 +357,7 @@ class DeviceWorkload:
             a = p["first"]
             arr[i] = ChunkedPart(
                 rec_off.data_ptr() + 8 * a, self.n_bins.data_ptr() + 4 * a, p["n"], self.init_states.data_ptr() + ns * a,
-                ctypes.addressof(p["plan"]), (p["ws"].data_ptr() + 255) // 256 * 256, p["ws_bytes"],
+                ctypes.addressof(p["plan"]), _aligned(p["ws"]), p["ws_bytes"],
                 self.out_off.data_ptr() + 8 * a, self.out_len.data_ptr() + 4 * a, self.status.data_ptr() + 4 * a,
                 (self.final_states.data_ptr() + ns * a) if self.final_states is not None else None,
                 rows_hint, self._part_counts.data_ptr() + 8 * i)
@@ -378,7 +405,7 @@ class DeviceWorkload:
         if self._hinted_path == "chunked" and left:
             recs, rec_off = self._slice_major()
             p = self._chunk_plan()
-            ws_ptr = (p["ws"].data_ptr() + 255) // 256 * 256
+            ws_ptr = _aligned(p["ws"])
             _check(lib().avr_cabac_encode_chunked_second_pass_device(
                 self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(),
                 self.n_slices, self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), ws_ptr, p["ws_bytes"],
@@ -466,27 +493,15 @@ class DeviceWorkload:
     def _plan_of(self, a, b):
         """Plan arrays and workspace of the intra-slice parallel path for slices [a, b), numbered from 0."""
         import torch
-        from . import CHUNK_BINS, SORT_BLOCK_BINS, ChunkPlan
-        dev = self.n_bins.device
-        nb = self.n_bins[a:b].to(torch.int64)
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        ar = torch.arange(b - a, device=dev)
-        res_off = torch.cat([zero, torch.cumsum((nb + 15) // 16 * 16 + 16, 0)])
-        n_chunks = torch.clamp((nb + CHUNK_BINS - 1) // CHUNK_BINS, min=1)
-        n_blocks = torch.clamp((nb + SORT_BLOCK_BINS - 1) // SORT_BLOCK_BINS, min=1)
-        chunk_base = torch.cat([zero, torch.cumsum(n_chunks, 0)]).to(torch.int32)
-        blk_base = torch.cat([zero, torch.cumsum(n_blocks, 0)]).to(torch.int32)
-        dig_off = torch.cat([zero, torch.cumsum(nb // 2 + 8, 0)])
-        t = dict(res_off=res_off, chunk_base=chunk_base, blk_base=blk_base, dig_off=dig_off,
-                 chunk_slice=torch.repeat_interleave(ar, n_chunks).to(torch.int32),
-                 blk_slice=torch.repeat_interleave(ar, n_blocks).to(torch.int32))
+        from . import ChunkPlan
+        t, totals = chunk_plan_arrays(self.n_bins[a:b])
         plan = ChunkPlan(t["res_off"].data_ptr(), t["chunk_base"].data_ptr(), t["chunk_slice"].data_ptr(),
-                         t["blk_base"].data_ptr(), t["blk_slice"].data_ptr(), t["dig_off"].data_ptr(),
-                         int(res_off[-1]), int(dig_off[-1]), int(chunk_base[-1]), int(blk_base[-1]))
+                         t["blk_base"].data_ptr(), t["blk_slice"].data_ptr(), t["dig_off"].data_ptr(), *totals)
         p = dict(tensors=t, plan=plan, first=a, n=b - a)
-        if self.kind == KIND_CABAC:
-            ws_bytes = lib().avr_cabac_chunked_workspace_bytes(b - a, self.n_states, ctypes.byref(plan))
-            p.update(ws_bytes=ws_bytes, ws=torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev))
+        if self.kind in (KIND_CABAC, KIND_CABAC8):      # (K2 sizes its own workspace, see encode_chunked)
+            ws_of = lib().avr_cabac8_chunked_workspace_bytes if self.kind == KIND_CABAC8 else lib().avr_cabac_chunked_workspace_bytes
+            ws_bytes = ws_of(b - a, self.n_states, ctypes.byref(plan))
+            p.update(ws_bytes=ws_bytes, ws=torch.empty(ws_bytes + 256, dtype=torch.uint8, device=self.n_bins.device))
         return p
 
     def set_parts(self, n_parts, weights=None):
@@ -496,10 +511,9 @@ class DeviceWorkload:
         config 2 1.43 -> 1.37 ms in two parts, 1.49 in three; config 4 - 2 %), one part below that (128 slices of config 2: 0.67 ms in
         one, 0.70 in two)."""
         import torch
-        from . import CHUNK_BINS, MAX_PARTS
-        nb = self.n_bins.to(torch.int64)
-        chunks = torch.clamp((nb + CHUNK_BINS - 1) // CHUNK_BINS, min=1)
-        total = int(chunks.sum())
+        from . import MAX_PARTS
+        chunk_base = chunk_plan_arrays(self.n_bins)[0]["chunk_base"]
+        total = int(chunk_base[-1])
         if n_parts == 0:
             waves = (total + 63) // 64
             n_parts = 2 if (waves >= 2048 and self.n_slices >= 64) else 1
@@ -507,7 +521,7 @@ class DeviceWorkload:
         self._parts = None
         self.n_parts = n_parts
         if n_parts > 1 and self.kind == KIND_CABAC and self._counts is not None:
-            csum = torch.cumsum(chunks, 0).cpu().numpy()
+            csum = chunk_base[1:].cpu().numpy()
             import numpy as np
             share = np.cumsum(np.asarray(weights if weights else [1.0] * n_parts, dtype=np.float64))
             share = share / share[-1]                            # (weights: the parts' shares of the chunks, for experiments; default equal)
@@ -520,30 +534,8 @@ class DeviceWorkload:
 
     def _chunk_plan(self):
         """Plan arrays and workspace of the intra-slice parallel path (built once, reused)."""
-        import torch
-        from . import CHUNK_BINS, SORT_BLOCK_BINS, ChunkPlan
         if getattr(self, "_plan", None) is None:
-            dev = self.n_bins.device
-            nb = self.n_bins.to(torch.int64)
-            zero = torch.zeros(1, dtype=torch.int64, device=dev)
-            ar = torch.arange(self.n_slices, device=dev)
-            res_off = torch.cat([zero, torch.cumsum((nb + 15) // 16 * 16 + 16, 0)])
-            n_chunks = torch.clamp((nb + CHUNK_BINS - 1) // CHUNK_BINS, min=1)
-            n_blocks = torch.clamp((nb + SORT_BLOCK_BINS - 1) // SORT_BLOCK_BINS, min=1)
-            chunk_base = torch.cat([zero, torch.cumsum(n_chunks, 0)]).to(torch.int32)
-            blk_base = torch.cat([zero, torch.cumsum(n_blocks, 0)]).to(torch.int32)
-            dig_off = torch.cat([zero, torch.cumsum(nb // 2 + 8, 0)])
-            t = dict(res_off=res_off, chunk_base=chunk_base, blk_base=blk_base, dig_off=dig_off,
-                     chunk_slice=torch.repeat_interleave(ar, n_chunks).to(torch.int32),
-                     blk_slice=torch.repeat_interleave(ar, n_blocks).to(torch.int32))
-            plan = ChunkPlan(t["res_off"].data_ptr(), t["chunk_base"].data_ptr(), t["chunk_slice"].data_ptr(),
-                             t["blk_base"].data_ptr(), t["blk_slice"].data_ptr(), t["dig_off"].data_ptr(),
-                             int(res_off[-1]), int(dig_off[-1]), int(chunk_base[-1]), int(blk_base[-1]))
-            self._plan = dict(tensors=t, plan=plan)
-            if self.kind in (KIND_CABAC, KIND_CABAC8):      # (K2 sizes its own workspace, see encode_chunked)
-                ws_of = lib().avr_cabac8_chunked_workspace_bytes if self.kind == KIND_CABAC8 else lib().avr_cabac_chunked_workspace_bytes
-                ws_bytes = ws_of(self.n_slices, self.n_states, ctypes.byref(plan))
-                self._plan.update(ws_bytes=ws_bytes, ws=torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev))
+            self._plan = self._plan_of(0, self.n_slices)
         return self._plan
 
     def encode_chunked(self):
@@ -555,7 +547,7 @@ class DeviceWorkload:
         if self.kind == KIND_CABAC8:                         # one-byte records: nothing to guess, nothing waits
             _check(lib().avr_cabac8_encode_chunked_device(
                 self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(),
-                self.n_slices, self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), (p["ws"].data_ptr() + 255) // 256 * 256,
+                self.n_slices, self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), _aligned(p["ws"]),
                 p["ws_bytes"], self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
                 self.final_states.data_ptr()))
             return
@@ -567,13 +559,13 @@ class DeviceWorkload:
                 n = L.avr_range_chunked_workspace_bytes(self.n_slices, ctypes.byref(p["plan"]), out_total)
                 p["ws_k2"] = torch.empty(n + 256, dtype=torch.uint8, device=self.n_bins.device)
                 p["ws_k2_bytes"] = n
-            ws_ptr = (p["ws_k2"].data_ptr() + 255) // 256 * 256
+            ws_ptr = _aligned(p["ws_k2"])
             _check(L.avr_range_encode_chunked_device(
                 self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(), self.n_slices,
                 ctypes.byref(p["plan"]), ws_ptr, p["ws_k2_bytes"], self.out.data_ptr(), self.out_off.data_ptr(), out_total,
                 self.out_len.data_ptr(), self.status.data_ptr()))
             return
-        ws_ptr = (p["ws"].data_ptr() + 255) // 256 * 256
+        ws_ptr = _aligned(p["ws"])
         if self._counts is not None and getattr(self, "_parts", None):
             self._hinted_path = "parts"
             if getattr(self, "_status_before", None) is None:
@@ -610,12 +602,11 @@ class DeviceWorkload:
             p["ws1"] = torch.empty(n + 256, dtype=torch.uint8, device=self.n_bins.device)
             p["ws1_bytes"] = n
             p["codes"] = torch.empty(p["plan"].res_total + 32 + 256, dtype=torch.uint8, device=self.n_bins.device)
-        al = lambda t: (t.data_ptr() + 255) // 256 * 256
         _check(L.avr_cabac_resolve_device(
             self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(), self.n_slices,
-            self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), al(p["ws1"]), p["ws1_bytes"], al(p["codes"]),
+            self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), _aligned(p["ws1"]), p["ws1_bytes"], _aligned(p["codes"]),
             self.status.data_ptr(), self.final_states.data_ptr() if self.final_states is not None else None))
-        off = al(p["codes"]) - p["codes"].data_ptr()
+        off = _aligned(p["codes"]) - p["codes"].data_ptr()
         return p["codes"][off:off + p["plan"].res_total + 32]
 
     def encode_resolved(self, codes):
@@ -629,7 +620,7 @@ class DeviceWorkload:
             p["ws2_bytes"] = n
         _check(L.avr_cabac_encode_resolved_device(
             self.device_index, _stream_ptr(torch), codes.data_ptr(), self.n_bins.data_ptr(), self.n_slices,
-            ctypes.byref(p["plan"]), (p["ws2"].data_ptr() + 255) // 256 * 256, p["ws2_bytes"], self.out.data_ptr(),
+            ctypes.byref(p["plan"]), _aligned(p["ws2"]), p["ws2_bytes"], self.out.data_ptr(),
             self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr()))
 
     def encode_codes_serial(self, codes):
