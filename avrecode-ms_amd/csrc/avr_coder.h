@@ -234,4 +234,13 @@ struct ChunkSource {
     }
 };
 
+// ------------------------------------------------------------------ output regions
+
+// What a lane may write of its slice's region [begin, end) of `out`: the byte counters are 32 bits wide, the caller's offsets 64 and a
+// region any size -- so the gap saturates instead of wrapping (a region of exactly 2^32 bytes is not one of 0).
+__host__ __device__ inline uint32_t region_capacity(uint64_t begin, uint64_t end) {
+    const uint64_t gap = end - begin;
+    return gap < 0xffffffffull ? uint32_t(gap) : 0xffffffffu;
+}
+
 }  // namespace avr

@@ -1355,7 +1355,7 @@ __global__ __launch_bounds__(256) void k_k1p_d(Plan p, const SliceTotals *tot, c
     if (T.bad || (force_retry_every && s % force_retry_every == 0)) { if (t == 0) status[s] = AVR_SLICE_RETRY_SERIAL; return; }
     const uint32_t *Ss = S + p.dig_off[s];
     uint8_t *o = out + out_off[s];
-    const uint32_t cap = uint32_t(out_off[s + 1] - out_off[s]);
+    const uint32_t cap = region_capacity(out_off[s], out_off[s + 1]);
     const uint32_t nd = ref_digits(T.t_total);
     if (t == 0) {
         const uint32_t low = uint32_t((uint64_t(Ss[nd]) << 15) + (Ss[nd + 1] >> 1));
@@ -1464,7 +1464,7 @@ __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_
     auto load16 = [&](uint32_t i) { return TILE ? tiled.load16(i) : *reinterpret_cast<const U4 *>(res + i); };
     auto byte = [&](uint32_t i) { return TILE ? tiled.byte(i) : uint32_t(res[i]); };
     const uint64_t o0 = out_off[slice];
-    const uint32_t cap = uint32_t(out_off[slice + 1] - o0);
+    const uint32_t cap = region_capacity(o0, out_off[slice + 1]);
     CabacEncoder e;
     e.init(0x7F800000u, out + o0, cap);                          // cabac_code.h:30
     auto bin = [&](uint32_t c) {

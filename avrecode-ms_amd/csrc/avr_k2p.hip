@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "avr_coder.h"
 #include "avr_div.h"
 #include "avr_internal.h"
 #include "avr_k2p.h"
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(64) void k_k2p_finish(K2Plan p, const uint64_t *fin
     const uint32_t P = fin_pos[s];
     const uint32_t *Ss = S + p.out_off[s];
     uint8_t *o = out + p.out_off[s];
-    const uint32_t cap = uint32_t(p.out_off[s + 1] - p.out_off[s]);
+    const uint32_t cap = region_capacity(p.out_off[s], p.out_off[s + 1]);
     uint32_t tile_carry = 0;                                     // into the last position of the tile being done (same in every lane)
     // Tiles from the last position.  A tile is aligned to its END: entry e of the tile (position lo + e - pad) sits in segment
     // e / kFinSeg, and segment 63 ends at the tile's last position; a short first tile leaves its low segments empty (zeros).

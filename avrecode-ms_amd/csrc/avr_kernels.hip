@@ -441,7 +441,7 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
     typename std::conditional<FORM == 3, CabacLaneNS, typename std::conditional<FORM == 1 || FORM == 4 || FORM == 5, CabacLaneN,
         typename std::conditional<FORM == 2, CabacLaneS, CabacLane>::type>::type>::type L;
     const uint64_t o0 = in_range ? out_off[slice] : 0;
-    const uint32_t cap = in_range ? uint32_t(out_off[slice + 1] - o0) : 0;
+    const uint32_t cap = in_range ? region_capacity(o0, out_off[slice + 1]) : 0;
     if constexpr (FORM == 1 || FORM == 4 || FORM == 5) L.init(out + o0, cap);
     else if constexpr (FORM == 2 || FORM == 3) L.init(out + o0, cap, lds + (blockDim.x >> 6) * rows4 * 64 + wv * 1024 + lane);
     else L.e.init(0x7F800000u, out + o0, cap);                   // cabac_code.h:30
@@ -629,7 +629,7 @@ __global__ __launch_bounds__(64) void k_range_encode(
 
     RangeEncoder64 e;
     const uint64_t o0 = out_off[slice];
-    const uint32_t cap = uint32_t(out_off[slice + 1] - o0);
+    const uint32_t cap = region_capacity(o0, out_off[slice + 1]);
     e.init(uint64_t(1) << 63, out + o0, cap);                    // arithmetic_code.h:96-97
 
     const ChunkSource<TILED> src(recs, off, g, slice);

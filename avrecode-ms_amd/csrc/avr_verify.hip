@@ -48,7 +48,7 @@ __global__ __launch_bounds__(64) void k_range_verify(
     uint32_t bad = AVR_VERIFY_NONE;
     if (status[slice] == AVR_SLICE_OK) {                         // any other slice is skipped: its status stays, its bytes are not the slice's
         const uint64_t o0 = out_off[slice];
-        const uint32_t cap = uint32_t(out_off[slice + 1] - o0), n = out_len[slice];
+        const uint32_t cap = region_capacity(o0, out_off[slice + 1]), n = out_len[slice];
         const VerifySource<TILED> src(recs, off, g, slice);
         bad = verify::verify_slice(reinterpret_cast<const uint64_t *>(out + o0), n < cap ? n : cap, n_bins[slice], src, inv_d);
         if (bad != AVR_VERIFY_NONE) status[slice] = AVR_SLICE_VERIFY_FAILED;

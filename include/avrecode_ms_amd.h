@@ -276,6 +276,9 @@ int avr_multi_load(avr_multi *m, uint64_t *bins_per_device);
  * be handed from one batch to another as it stands.  A call writes nothing outside [workspace, workspace + workspace_bytes) and the documented
  * extents of its output arrays: out[out_off[i] .. out_off[i] + out_len[i]) of every slice (nothing else of `out`, not a byte past out_off[n_slices]),
  * n_slices entries of out_len and status, n_slices * n_states final states, res_total + 32 bytes of codes, tile_off[n_tiles] * 16 bytes of tiles.
+ * A region [out_off[i], out_off[i + 1]) may be any size, gaps of 2^32 bytes and more included; a slice uses at most 2^32 - 1 bytes of it.
+ * A slice that a one-lane-per-slice coder gives up on while coding it (AVR_SLICE_OVERFLOW; avr_cabac8_encode_tiles_device: a put_terminate(1)
+ * that is not last) may have had bytes of its own region written before -- nothing outside [out_off[i], out_off[i + 1]).
  * STREAMS: whatever a call runs on streams of its own is joined back: work enqueued on `stream` behind the call sees all of its results
  * and may overwrite its workspace (tests/test_gpu_workspace.py holds the library to all three).
  * ONE THREAD PER STREAM: the library keeps a few kilobytes of scratch (and, for the chunked K2, a second stream with its

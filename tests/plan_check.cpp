@@ -1,7 +1,9 @@
 // The plan rules of csrc/avr_plan.h, printed: the header compiled alone by g++ (no HIP), driven by tests/test_plan.py.
-// stdin, a line each:   "plan k nb_0 ... nb_(k-1)"   or   "path n_slices total_bins".
+// stdin, a line each:   "plan k nb_0 ... nb_(k-1)"   or   "big k nb_0 ... nb_(k-1)"   or   "path n_slices total_bins".
 // stdout for a plan: the per-slice values (chunks, blocks, work, digits, out), then every array of the K1p plan by name; and a line
 // "lesser" telling whether the lesser paths (Serial, Chunks, Codes) build the same arrays and leave the others empty.
+// stdout for "big" (slices of up to 2^32 - 1 bins: millions of chunks): the same without the per-chunk arrays, of which a line
+// "slices" gives the two sizes and whether every entry is the slice whose range of chunk_base / blk_base holds it.
 // stdout for a path: "path 0" or "path 1" (want_chunked).
 #include <inttypes.h>
 #include <stdio.h>
@@ -31,7 +33,8 @@ int main() {
             continue;
         }
         uint64_t k;
-        if (strcmp(what, "plan") || scanf("%" SCNu64, &k) != 1) return 1;
+        const bool big = !strcmp(what, "big");
+        if ((!big && strcmp(what, "plan")) || scanf("%" SCNu64, &k) != 1) return 1;
         std::vector<uint32_t> nb(k);
         for (auto &x : nb)
             if (scanf("%" SCNu32, &x) != 1) return 1;
@@ -44,7 +47,17 @@ int main() {
         HostPlan p, q;
         fill_plan(p, nb.data(), nb.size(), PlanFor::K1p);
         line("out_off", p.out_off); line("res_off", p.res_off); line("dig_off", p.dig_off); line("chunk_base", p.chunk_base);
-        line("chunk_slice", p.chunk_slice); line("blk_base", p.blk_base); line("blk_slice", p.blk_slice);
+        if (big) {
+            bool in_place = p.chunk_slice.size() == p.chunk_base.back() && p.blk_slice.size() == p.blk_base.back();
+            for (size_t i = 0; in_place && i < nb.size(); i++) {
+                for (uint32_t c = p.chunk_base[i]; c < p.chunk_base[i + 1]; c++) in_place = in_place && p.chunk_slice[c] == i;
+                for (uint32_t b = p.blk_base[i]; b < p.blk_base[i + 1]; b++) in_place = in_place && p.blk_slice[b] == i;
+            }
+            line("blk_base", p.blk_base);
+            printf("slices %zu %zu %d\n", p.chunk_slice.size(), p.blk_slice.size(), int(in_place));
+        } else {
+            line("chunk_slice", p.chunk_slice); line("blk_base", p.blk_base); line("blk_slice", p.blk_slice);
+        }
         printf("totals %" PRIu64 " %" PRIu64 " %" PRIu32 " %" PRIu32 "\n", plan_total(p.res_off), plan_total(p.dig_off), plan_total(p.chunk_base), plan_total(p.blk_base));
         bool same = true;
         q = p;                                                    // refilled from a full plan: what a path does not read must go

@@ -155,6 +155,53 @@ def test_library_still_quotes_the_recorded_sizes(avr, build):
         assert quotes(L, shape) == want, shape
 
 
+# The plan of three slices of 0xfffffff0 bins and an empty one (tests/test_plan.py: test_offsets_and_totals_above_4g), 86 contexts:
+# res_total, dig_total, total_chunks, total_blocks, out_total, and what the library quotes for it -- K1p, K1p's phases B-D, K2p
+FAR_TOTALS = (12884901904, 6442450952, 12582913, 3145729, 12884901904)
+FAR_QUOTES = {"avr_cabac_chunked_workspace_bytes": 57428808960, "avr_cabac_resolved_workspace_bytes": 39208420352,
+              "avr_range_chunked_workspace_bytes": 51690607872}
+
+
+def far_quotes(L, res_total, dig_total, out_total):
+    shape_plan = (res_total, dig_total) + FAR_TOTALS[2:4]
+
+    class Plan(ctypes.Structure):
+        _fields_ = [(name, ctypes.c_void_p) for name in ("res_off", "chunk_base", "chunk_slice", "blk_base", "blk_slice", "dig_off")]
+        _fields_ += [("res_total", ctypes.c_uint64), ("dig_total", ctypes.c_uint64), ("total_chunks", ctypes.c_uint32),
+                     ("total_blocks", ctypes.c_uint32)]
+    plan = ctypes.byref(Plan(None, None, None, None, None, None, *shape_plan))
+    z = ctypes.c_size_t
+    for name in FAR_QUOTES:
+        getattr(L, name).restype = z
+    return {"avr_cabac_chunked_workspace_bytes": L.avr_cabac_chunked_workspace_bytes(z(4), z(86), plan),
+            "avr_cabac_resolved_workspace_bytes": L.avr_cabac_resolved_workspace_bytes(z(4), plan),
+            "avr_range_chunked_workspace_bytes": L.avr_range_chunked_workspace_bytes(z(4), plan, ctypes.c_uint64(out_total))}
+
+
+@pytest.mark.parametrize("build", ["product", "hooks"])
+def test_quotes_of_a_plan_above_4g(avr, build):
+    """Totals that do not fit in 32 bits: the quotes are the recorded numbers, hold what the kernels index (the code buffer of
+    res_total + 32 bytes, four bytes to a digit sum, four to a byte of out_total) and grow by exactly what a total grows by --
+    a quote computed in 32 bits would wrap between one step and the next."""
+    L = ctypes.CDLL(avr.LIB_PATH if build == "product" else avr.HOOKS_LIB_PATH)
+    res_total, dig_total, _, _, out_total = FAR_TOTALS
+    G = 1 << 32
+    q = far_quotes(L, res_total, dig_total, out_total)
+    assert q == FAR_QUOTES and all(v > G for v in q.values())
+    assert q["avr_cabac_chunked_workspace_bytes"] >= res_total + 32 + q["avr_cabac_resolved_workspace_bytes"]
+    assert q["avr_cabac_resolved_workspace_bytes"] >= 4 * dig_total + 16 and q["avr_range_chunked_workspace_bytes"] >= 4 * out_total + 64
+    for step in (256, G - 256, G, 5 * G):                        # (multiples of 256: the regions are rounded to that)
+        more_res = far_quotes(L, res_total + step, dig_total, out_total)
+        more_dig = far_quotes(L, res_total, dig_total + step // 4, out_total)
+        more_out = far_quotes(L, res_total, dig_total, out_total + step // 4)
+        tiled = (FAR_TOTALS[2] + 63) // 64 * 64 * 1024             # the code buffer holds the larger of the tiled and the linear form
+        linear = (res_total + step + 32 + 255) // 256 * 256
+        assert tiled == 12884967424 and more_res["avr_cabac_chunked_workspace_bytes"] == q["avr_cabac_chunked_workspace_bytes"] - tiled + max(tiled, linear)
+        assert more_dig["avr_cabac_chunked_workspace_bytes"] == q["avr_cabac_chunked_workspace_bytes"] + step
+        assert more_dig["avr_cabac_resolved_workspace_bytes"] == q["avr_cabac_resolved_workspace_bytes"] + step
+        assert more_out["avr_range_chunked_workspace_bytes"] == q["avr_range_chunked_workspace_bytes"] + step
+
+
 if __name__ == "__main__":                                       # record: the table above, from the library given
     lib = ctypes.CDLL(sys.argv[1])
     picks = [s for s in grid() if (s[0], s[1], s[2], s[3]) in {

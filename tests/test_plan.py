@@ -53,6 +53,15 @@ def cpp_plan(run, lengths):
     return {line.split()[0]: list(map(int, line.split()[1:])) for line in out[:-1]}
 
 
+def cpp_big_plan(run, lengths):
+    """cpp_plan for slices of millions of chunks: "slices" (the two sizes, and whether every entry is in place) stands for
+    chunk_slice and blk_slice."""
+    out = run("big %d %s\n" % (len(lengths), " ".join(map(str, lengths))))
+    names = ["chunks", "blocks", "work", "digits", "out", "out_off", "res_off", "dig_off", "chunk_base", "blk_base", "slices", "totals", "lesser"]
+    assert [line.split()[0] for line in out[:-1]] == names and out[-1] == ""
+    return {line.split()[0]: list(map(int, line.split()[1:])) for line in out[:-1]}
+
+
 def test_fixed_numbers(plan_check):
     p = cpp_plan(plan_check, FIXED)
     for name, (per_slice, total) in PER_SLICE.items():
@@ -96,3 +105,33 @@ def test_totals_against_the_layout_tests(plan_check):
             p = cpp_plan(plan_check, lengths)
             assert tuple(p["totals"] + [p["out_off"][-1]]) == plan_totals(n_slices, first), (n_slices, first)
             assert chunk_plan_arrays(torch.tensor(lengths, dtype=torch.int32))[1] == plan_totals(n_slices, first)[:4]
+
+
+def test_offsets_and_totals_above_4g(plan_check):
+    """Three slices of 0xfffffff0 bins and an empty one: out_off, res_off and dig_off pass 2^32 (the counts of chunks and blocks do
+    not), in C++ and in Python alike and as the per-slice rules, worked out here in Python integers, say."""
+    import torch
+    from avrecode_ms_amd.device import chunk_plan_arrays
+    big = 0xfffffff0
+    lengths = [big, big, 0, big]
+    G = 1 << 32
+    p = cpp_big_plan(plan_check, lengths)
+    assert p["out"] == [G, G, 16, G] and p["work"] == [G, G, 16, G] and p["digits"] == [G // 2, G // 2, 8, G // 2]
+    assert p["chunks"] == [1 << 22, 1 << 22, 1, 1 << 22] and p["blocks"] == [1 << 20, 1 << 20, 1, 1 << 20]
+    assert p["out_off"] == [0, G, 2 * G, 2 * G + 16, 3 * G + 16] and p["res_off"] == p["out_off"]
+    assert p["dig_off"] == [0, G // 2, G, G + 8, 3 * G // 2 + 8]
+    assert p["chunk_base"] == [0, 1 << 22, 1 << 23, (1 << 23) + 1, 3 * (1 << 22) + 1]
+    assert p["blk_base"] == [0, 1 << 20, 1 << 21, (1 << 21) + 1, 3 * (1 << 20) + 1]
+    assert p["totals"] == [12884901904, 6442450952, 12582913, 3145729] and p["totals"][0] > G and p["totals"][1] > G
+    assert p["slices"] == [12582913, 3145729, 1] and p["lesser"] == [1]
+    rules = {"out_off": lambda x: (x + 16 + 7) // 8 * 8, "res_off": lambda x: (x + 15) // 16 * 16 + 16, "dig_off": lambda x: x // 2 + 8,
+             "chunk_base": lambda x: max(1, (x + 1023) // 1024), "blk_base": lambda x: max(1, (x + 4095) // 4096)}
+    for name, rule in rules.items():
+        assert p[name] == [sum(rule(x) for x in lengths[:i]) for i in range(len(lengths) + 1)], name
+    t, totals = chunk_plan_arrays(torch.tensor(lengths, dtype=torch.int64))
+    for name in ("res_off", "dig_off", "chunk_base", "blk_base"):
+        assert t[name].tolist() == p[name], name
+    assert list(totals) == p["totals"]
+    for name, base in (("chunk_slice", "chunk_base"), ("blk_slice", "blk_base")):
+        assert t[name].dtype == torch.int32
+        assert np.array_equal(t[name].numpy(), np.repeat(np.arange(len(lengths), dtype=np.int32), np.diff(p[base]))), name
