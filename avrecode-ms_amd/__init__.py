@@ -35,13 +35,13 @@ KIND_RANGE_KEYS, EST_KEYS = 4, 1026                           # key records: the
 SEL_BYPASS, SEL_TERMINATE = 1024, 1025
 SEL8_BYPASS, SEL8_TERMINATE, MAX_STATES8 = 126, 127, 126      # one-byte records (KIND_CABAC8)
 SLICE_OK, SLICE_ZERO_PROB, SLICE_OVERFLOW, SLICE_BAD_RECORD = 0, 1, 2, 3
-SLICE_VERIFY_FAILED, VERIFY_NONE = 4, 0xFFFFFFFF             # only ever set by the K2 verifier; "no bad bin"
+SLICE_VERIFY_FAILED, VERIFY_NONE = 4, 0xFFFFFFFF             # only ever set by a verifier; "no bad bin"
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_verify.hip", "avr_api.cpp"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_api.cpp"]
 _DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
-                    "avr_verify.h"]
+                    "avr_verify.h", "avr_cabac_verify.h"]
 
 
 class AvrError(RuntimeError):
@@ -163,6 +163,17 @@ SIGNATURES = {
     "avr_batch_timings": (c_int, [c_void_p, POINTER(c_float)]),
     "avr_batch_run_info": (c_int, [c_void_p, POINTER(ctypes.c_uint32)]),
     "avr_batch_set_verify": (c_int, [c_void_p, c_int]),
+    "avr_batch_set_verify_k1": (c_int, [c_void_p, c_int]),
+    "avr_cabac_verify_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avr_cabac_verify_slices_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avr_cabac8_verify_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avr_cabac8_verify_slices_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avr_cabac_verify_codes_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avr_batch_get_verify": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
     "avr_batch_verify_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "avr_range_verify_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
@@ -288,7 +299,7 @@ def test_hooks(**hooks):
     -DAVR_TEST_HOOKS -- with the named hooks set (csrc/avr_internal.h: k1p_force_retry_every, census_stride,
     chain_lanes, k1_form_ref, k1_path [1 serial, 2 chunked], no_dense, no_hint, k2p_seg_len, local_waves, k2p_wave); all of them keep the bytes exact and
     only force paths that real batches take rarely -- except verify_flip, which corrupts one slice's first byte on the device in front of the verifier (a batch with
-    set_verify on) so that a test sees a failure travel through the batch API, and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
+    set_verify or set_verify_k1 on) so that a test sees a failure travel through the batch API, and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
     AVR_SLICE_RETRY_SERIAL) so that a test can see which ones it coded itself.  The product library has no such switches."""
     global _lib, _hooks_lib
     if _hooks_lib is None:
@@ -477,6 +488,12 @@ class Batch:
         """K2 batches (KIND_RANGE, KIND_RANGE_KEYS): from the next submit on, every coded slice is decoded back on the device against
         its records, behind the encode kernels.  A slice that does not decode comes back with SLICE_VERIFY_FAILED."""
         _check(self._L.avr_batch_set_verify(self._h, 1 if on else 0))
+
+    def set_verify_k1(self, on: bool = True):
+        """From the next submit() on, every coded slice of a K1 batch (add_slice_cabac, add_slice_cabac8, add_codes) is decoded back on
+        the device by the CABAC decoder of the standard against its records, behind the encode kernels, and the decoder's final states
+        are compared with the encoder's.  A slice that does not decode comes back with SLICE_VERIFY_FAILED."""
+        _check(self._L.avr_batch_set_verify_k1(self._h, 1 if on else 0))
 
     def get_verify(self, i: int) -> int:
         """Index of slice i's first bin that decoded to another value, or VERIFY_NONE."""

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "avr_cabac_verify.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
 #include "avr_synth.h"
@@ -165,8 +166,9 @@ struct avr_batch {
     uint32_t info[4] = {0, 0, 0, 0};        // avr_batch_run_info
     avr_chunk_plan plan{};                  // of the chunked run in flight (device arrays of this batch)
 
-    // verification of a K2 run (avr_batch_set_verify): off by default, and then none of this is touched
-    bool verify = false;                    // the setting: the next submit enqueues the verifier behind the encode
+    // verification of a run (K2: avr_batch_set_verify, K1: avr_batch_set_verify_k1): off by default, and then none of this is touched
+    bool verify = false;                    // the setting: the next submit of a K2 batch enqueues the verifier behind the encode
+    bool verify_k1 = false;                 // the same for a K1 batch (avr_cabac_verify.hip)
     bool verified = false;                  // the run in flight / the last run had it
     hipEvent_t vev[3] = {};                 // end of the encode, start and end of the verifier (created when verify is first set)
     float verify_ms = 0;
@@ -466,6 +468,7 @@ int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n) {
 #define AVR_STAGE(dst, src, n) do { if (int rc_ = stage_h2d(b, dst, src, n)) return rc_; } while (0)
 
 static int enqueue_lengths(avr_batch *b, uint32_t n32);
+static int enqueue_verify_k1(avr_batch *b, uint32_t n32, int form, const void *recs, const uint64_t *off, const uint32_t *order, bool again = false);
 
 // A batch of resolved codes: H2D of one byte per bin, K1p phases B-D (or the one-lane-per-slice coder), lengths back.
 static int submit_codes(avr_batch *b, uint32_t n32) {
@@ -485,6 +488,8 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
         (rc = b->d_order.reserve(n)) || (rc = b->d_out_len.reserve(n)) || (rc = b->d_status.reserve(n)) || (rc = b->d_out.reserve(total_out)) ||
         (rc = b->h_out_len.reserve(n)) || (rc = b->h_status.reserve(n)) || (rc = b->h_plan.reserve(arena)))
         return rc;
+    b->verified = b->verify_k1;
+    if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
     hipStream_t s = b->stream;
     b->plan_used = 0;
     b->hint_used = 0;
@@ -508,6 +513,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
                                                b->d_out_off.p, b->d_out_len.p, b->d_status.p));
     }
     b->last_path = chunked;
+    if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kCodes, d_codes, b->d_res_off.p, chunked ? nullptr : b->d_order.p))) return rc;
     return enqueue_lengths(b, n32);
 }
 
@@ -556,6 +562,24 @@ static int enqueue_verify(avr_batch *b, uint32_t n32, bool tiled) {
     return AVR_OK;
 }
 
+// The same behind the encode kernels of a K1 run: the CABAC decoder over whatever that path's encoder read -- `form` (cabac_verify::Form),
+// the records or codes at `recs` / `off`, `order` where the path has one -- with the encoder's final states where the kind has states.
+// again: behind K1p's second pass at avr_batch_wait, over the same bytes (the test build's hook has had its turn).
+static int enqueue_verify_k1(avr_batch *b, uint32_t n32, int form, const void *recs, const uint64_t *off, const uint32_t *order, bool again) {
+    hipStream_t s = b->stream;
+    const bool states = form != avr::cabac_verify::kCodes;
+    AVR_HIP(hipEventRecord(b->vev[0], s));
+#ifdef AVR_TEST_HOOKS
+    if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
+#endif
+    AVR_HIP(hipEventRecord(b->vev[1], s));
+    AVR_HIP(avr::launch_cabac_verify(form, s, recs, off, b->d_n_bins.p, order, n32, states ? b->d_states.p : nullptr, states ? uint32_t(b->n_states) : 0u,
+                                     b->d_out.p, b->d_out_off.p, b->d_out_len.p, states ? b->d_final.p : nullptr, b->d_status.p,
+                                     b->d_first_bad.p));
+    AVR_HIP(hipEventRecord(b->vev[2], s));
+    return AVR_OK;
+}
+
 static int submit_impl(avr_batch *b, bool use_hint) {
     const size_t n = b->n_bins.size();
     const uint32_t n32 = uint32_t(n);
@@ -589,7 +613,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if ((rc = b->h_plan.reserve(staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) + (chunked ? 0 : staged<uint64_t>(n_tiles + 1) + staged<uint32_t>(n)) +
                                 (b->keys ? staged<uint32_t>(b->group_first.size() + 1) : 0) + staged_plan(b->hp)))) return rc;
     if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
-    b->verified = b->verify && !cabac;
+    b->verified = cabac ? b->verify_k1 : b->verify;
     if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
 
     hipStream_t s = b->stream;
@@ -638,6 +662,9 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         else
             AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
                                     avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}, &hint));
+        // over the slice-major records K1p read, in the caller's numbering: the census, the dense map and the chains are checked with the bytes
+        if (b->verified && (rc = b->recs8 ? enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices8, b->d_recs8.p, b->d_rec_off.p, nullptr)
+                                          : enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr))) return rc;
     } else {
         if (b->recs8)                                            // one-byte records validated and transposed in one pass, as they are
             AVR_HIP(avr::launch_pack_tiles8_narrow(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
@@ -656,7 +683,10 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         else
             AVR_HIP(avr::launch_range_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
                                              b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-        if (b->verified && (rc = enqueue_verify(b, n32, true))) return rc;       // over the tiles the encoder read
+        if (b->verified && cabac)                                // over the tiles the encoder read
+            rc = enqueue_verify_k1(b, n32, b->recs8 ? avr::cabac_verify::kTiles8 : avr::cabac_verify::kTiles2, b->d_tiles.p, b->d_tile_off.p, b->d_order.p);
+        else if (b->verified) rc = enqueue_verify(b, n32, true);
+        if (rc) return rc;
     }
     return enqueue_lengths(b, n32);
 }
@@ -683,6 +713,8 @@ int avr_batch_submit(avr_batch *b) {
     b->dense_off.assign(n + 1, 0);
     if (b->verify && b->kind >= 0 && b->kind != AVR_KIND_RANGE)
         return fail(AVR_ERR_INVALID, "verification exists for the compress direction only: not for a K1 batch");
+    if (b->verify_k1 && b->kind == AVR_KIND_RANGE)
+        return fail(AVR_ERR_INVALID, "K1 verification exists for the decompress direction only: not for a K2 batch");
     b->verified = false;
     if (n == 0) { b->in_flight = true; return AVR_OK; }
     const bool use_hint = b->dense_hint > 0 && !avr::no_hint();
@@ -704,6 +736,7 @@ int avr_batch_wait(avr_batch *b) {
     int rc;
     AVR_HIP(hipStreamSynchronize(s));
     b->info[0] = uint32_t(b->last_path); b->info[1] = b->info[2] = b->info[3] = 0;
+    float verify_before = 0;                                     // of the verifier in front of K1p's second pass, where there is one
     if (b->kind == AVR_KIND_CABAC) {
         // The run was sized by a guess of the context count.  The one-lane-per-slice kernel is exact whatever the
         // guess; the intra-slice parallel kernels only if the batch needs no more rows than guessed: else once more,
@@ -715,8 +748,20 @@ int avr_batch_wait(avr_batch *b) {
             b->info[3] = 1;
         }
         if (b->last_path == 1 && b->h_ndense.p[1]) {             // slices with a context the sampled census missed: their second pass
+            if (b->verified) {
+                // The verifier has run in front of this pass, and the pass treats a slice it marked AVR_SLICE_VERIFY_FAILED like one with a bad
+                // record (length 0).  Such a slice goes in as AVR_SLICE_OK -- finished, so the pass leaves it alone -- and the verifier behind
+                // the pass, which decodes every slice again, fails it again at the same bin.  (h_status is the device's, behind a synchronise.)
+                (void)hipEventElapsedTime(&verify_before, b->vev[1], b->vev[2]);
+                bool any = false;
+                for (size_t i = 0; i < n; i++)
+                    if (b->h_status.p[i] == AVR_SLICE_VERIFY_FAILED) { b->h_status.p[i] = AVR_SLICE_OK; any = true; }
+                if (any) AVR_HIP(hipMemcpyAsync(b->d_status.p, b->h_status.p, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            }
             AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(b->n_states), &b->plan, avr::align256(b->d_workspace.p),
                                           avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
+            // the verifier skipped the slices of this pass (their status was not AVR_SLICE_OK yet): once more behind it
+            if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr, true))) return rc;
             if ((rc = enqueue_lengths(b, n32))) return rc;
             AVR_HIP(hipStreamSynchronize(s));
             b->info[3] |= 2;
@@ -742,6 +787,11 @@ int avr_batch_wait(avr_batch *b) {
     if (b->verified) {                                           // the encode's slot ends where the verifier's events begin
         (void)hipEventElapsedTime(&b->ms[2], b->ev[2], b->vev[0]);
         (void)hipEventElapsedTime(&b->verify_ms, b->vev[1], b->vev[2]);
+        // Behind K1p's second pass (rare) vev[0] was recorded again: the span from ev[2] then also holds the first verifier, taken off
+        // here, and what lay between the two runs -- the host's wait, the status and length copies -- which stays in: on that path
+        // ms[2] is an upper bound of the encode, not the encode alone.
+        b->ms[2] -= verify_before;
+        b->verify_ms += verify_before;
     }
     b->ran = true;                                               // only now: the getters hand out h_out / h_status
     return AVR_OK;
@@ -809,6 +859,17 @@ int avr_batch_set_verify(avr_batch *b, int on) {
         for (auto &e : b->vev) AVR_HIP(hipEventCreate(&e));
     }
     b->verify = on != 0;
+    return AVR_OK;
+}
+
+int avr_batch_set_verify_k1(avr_batch *b, int on) {
+    if (!b) return fail(AVR_ERR_INVALID, "null batch");
+    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    if (on && !b->vev[0]) {
+        if (int rc = select_device(b->device)) return rc;
+        for (auto &e : b->vev) AVR_HIP(hipEventCreate(&e));
+    }
+    b->verify_k1 = on != 0;
     return AVR_OK;
 }
 
@@ -1360,6 +1421,61 @@ int avr_range_verify_slices_device(int device, void *stream, const uint16_t *rec
     AVR_HIP(avr::launch_range_verify(false, static_cast<hipStream_t>(stream), recs, rec_off, n_bins, order, uint32_t(n_slices),
                                      out, out_off, out_len, status, first_bad));
     return AVR_OK;
+}
+
+// The K1 verifier's five forms (avr_cabac_verify.hip).  One body: the checks that need no device, then the launch.
+static int cabac_verify_device(int form, int device, void *stream, const void *recs, const uint64_t *off, const uint32_t *n_bins,
+                               const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states, const uint8_t *out,
+                               const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states, int32_t *status,
+                               uint32_t *first_bad, bool need_first_bad) {
+    if (int rc = check_common(off, n_bins, out_off, n_slices)) return rc;
+    const size_t limit = avr::cabac_verify::form_max_states(form);
+    if (n_states > limit) return fail(AVR_ERR_INVALID, "n_states %zu > %zu", n_states, limit);
+    if (n_slices && (!recs || !out || !out_len || !status || (need_first_bad && !first_bad) || (n_states && !init_states)))
+        return fail(AVR_ERR_INVALID, "null device pointer");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_cabac_verify(form, static_cast<hipStream_t>(stream), recs, off, n_bins, order, uint32_t(n_slices), init_states,
+                                     uint32_t(n_states), out, out_off, out_len, final_states, status, first_bad));
+    return AVR_OK;
+}
+
+int avr_cabac_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
+                                  const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                  const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
+                                  int32_t *status, uint32_t *first_bad) {
+    return cabac_verify_device(avr::cabac_verify::kTiles2, device, stream, tiles, tile_off, n_bins, order, n_slices, init_states, n_states,
+                               out, out_off, out_len, final_states, status, first_bad, false);
+}
+
+int avr_cabac_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
+                                   int32_t *status, uint32_t *first_bad) {
+    return cabac_verify_device(avr::cabac_verify::kSlices2, device, stream, recs, rec_off, n_bins, order, n_slices, init_states, n_states,
+                               out, out_off, out_len, final_states, status, first_bad, true);
+}
+
+int avr_cabac8_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
+                                   int32_t *status, uint32_t *first_bad) {
+    return cabac_verify_device(avr::cabac_verify::kTiles8, device, stream, tiles, tile_off, n_bins, order, n_slices, init_states, n_states,
+                               out, out_off, out_len, final_states, status, first_bad, false);
+}
+
+int avr_cabac8_verify_slices_device(int device, void *stream, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
+                                    const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                    const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
+                                    int32_t *status, uint32_t *first_bad) {
+    return cabac_verify_device(avr::cabac_verify::kSlices8, device, stream, recs8, rec_off, n_bins, order, n_slices, init_states, n_states,
+                               out, out_off, out_len, final_states, status, first_bad, true);
+}
+
+int avr_cabac_verify_codes_device(int device, void *stream, const uint8_t *codes, const uint64_t *res_off, const uint32_t *n_bins,
+                                  const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
+                                  const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
+    return cabac_verify_device(avr::cabac_verify::kCodes, device, stream, codes, res_off, n_bins, order, n_slices, nullptr, 0,
+                               out, out_off, out_len, nullptr, status, first_bad, true);
 }
 
 // ------------------------------------------------------------------ dense context ids

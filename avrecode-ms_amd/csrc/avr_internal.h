@@ -133,6 +133,13 @@ hipError_t launch_range_encode(bool tiled, hipStream_t s, const void *recs, cons
 hipError_t launch_range_verify(bool tiled, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
                                const uint32_t *order, uint32_t n_slices, const uint8_t *out, const uint64_t *out_off,
                                const uint32_t *out_len, int32_t *status, uint32_t *first_bad);
+// the K1 verifier (avr_cabac_verify.hip): the CABAC decoder of H.264 9.3.3.2 over every AVR_SLICE_OK slice and its records; `form` is a
+// cabac_verify::Form (avr_cabac_verify.h: 0 / 1 two-byte tiles / slices, 2 / 3 one-byte tiles / slices, 4 codes -- no states);
+// final_states may be null; writes status and first_bad only
+hipError_t launch_cabac_verify(int form, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
+                               const uint32_t *order, uint32_t n_slices, const uint8_t *init_states, uint32_t n_states,
+                               const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
+                               int32_t *status, uint32_t *first_bad);
 #ifdef AVR_TEST_HOOKS
 hipError_t launch_verify_flip(hipStream_t s, uint8_t *out, const uint64_t *out_off, uint32_t slice);
 #endif

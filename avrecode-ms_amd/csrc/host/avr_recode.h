@@ -73,13 +73,15 @@ struct phase_timer {
 
 inline void gpu_check(int rc) { if (rc < 0) throw std::runtime_error(std::string("avr: ") + avr_last_error()); }
 
-// AVR_TIMING=1: the verifier's share of a batch that ran with avr_batch_set_verify, as a phase of its own (device time, between its events)
-inline void report_verify_ms(avr_batch *b) {
+// AVR_TIMING=1: the verifier's share of a batch that ran with avr_batch_set_verify (or, `what` naming it, avr_batch_set_verify_k1), as a
+// phase of its own (device time, between its events)
+inline void report_verify_ms(avr_batch *b, const char *what = "compress: GPU verify (a5)") {
     if (!getenv("AVR_TIMING")) return;
     float ms = 0;
     gpu_check(avr_batch_verify_ms(b, &ms));
-    fprintf(stderr, "[timing] %-28s %8.1f ms\n", "compress: GPU verify (a5)", double(ms));
+    fprintf(stderr, "[timing] %-28s %8.1f ms\n", what, double(ms));
 }
+inline void report_verify_k1_ms(avr_batch *b) { report_verify_ms(b, "decompress: GPU verify (K1)"); }
 
 struct batch_holder {                                    // RAII around the C ABI's avr_batch
     avr_batch *b;
@@ -356,6 +358,9 @@ class decompressor {                                     // recode.cpp:1319-1598
     }
     size_t pending_slices() const { return pending_.size(); }
     size_t pending_bins() const { size_t bins = 0; for (auto &p : pending_) bins += p.codes.size(); return bins; }
+    // run() has every coded slice decoded back on the device, as the CABAC stream it is, against the codes it was made from
+    // (avr_batch_set_verify_k1).  A caller with a batch of its own (add_to / take_from) sets that on its batch.
+    void set_verify(bool on) { verify_ = on; }
     void add_to(avr_batch *b) {
         first_in_batch_ = -1;
         for (auto &p : pending_) {
@@ -369,6 +374,11 @@ class decompressor {                                     // recode.cpp:1319-1598
         for (size_t i = 0; i < pending_.size(); i++) {
             const uint8_t *bytes; size_t len; int status;
             gpu_check(avr_batch_get(b, size_t(first_in_batch_) + i, &bytes, &len, &status));
+            if (status == AVR_SLICE_VERIFY_FAILED) {         // the verifier's (a batch with avr_batch_set_verify_k1): the bytes must not reach the user's file
+                uint32_t bin = AVR_VERIFY_NONE;
+                gpu_check(avr_batch_get_verify(b, size_t(first_in_batch_) + i, &bin));
+                throw std::runtime_error("Verify error: coded slice does not decode to its bins (slice " + std::to_string(i) + ", bin " + std::to_string(bin) + ")");
+            }
             if (status != AVR_SLICE_OK) throw std::runtime_error("avr: slice status " + std::to_string(status));
             len = avr_drop_stop_byte(bytes, len);        // cabac_decoder::finish, recode.cpp:1508-1512
             blocks_[pending_[i].index].out_bytes.assign(reinterpret_cast<const char *>(bytes), len);
@@ -503,13 +513,16 @@ class decompressor {                                     // recode.cpp:1319-1598
         if (pending_.empty()) return;
         batch_holder bh(device_, pending_.size(), pending_bins() + 16 * pending_.size() + 64);
         add_to(bh.b);
+        if (verify_) gpu_check(avr_batch_set_verify_k1(bh.b, 1));
         gpu_check(avr_batch_run(bh.b));
+        if (verify_) report_verify_k1_ms(bh.b);
         take_from(bh.b);
     }
 
     struct pending { int index; std::vector<uint8_t> codes; };
     int first_in_batch_ = -1;
     int device_;
+    bool verify_ = false;
     Recoded in_;
     int read_index_ = 0;                                 // blocks the reader has opened
     std::string feed_;                                   // bytes of the block being read

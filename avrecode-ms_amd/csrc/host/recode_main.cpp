@@ -22,6 +22,10 @@
 // slice is decoded back on the device against its records before its bytes go into a container, with or without
 // AVR_DEVICE_ESTIMATORS=1; a slice that does not decode ends the file with "Verify error: ..." (exit status 1, as with the other
 // coder errors).  The .recode bytes are the same either way.  Read here, not by the library.  Off by default.
+// AVR_VERIFY_K1=1 = the same for the other direction: the K1 batches of decompress, roundtrip and test <dir> run with the K1 verifier on
+// (avr_batch_set_verify_k1): every coded slice is decoded back on the device, as the CABAC stream it is, against the codes it was made
+// from before its bytes go into the H.264 file; a slice that does not decode ends the file with "Verify error: coded slice does not
+// decode to its bins (slice N, bin M)" (exit status 1).  The file's bytes are the same either way.  Off by default.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -57,6 +61,7 @@ bool device_estimators() {
 }
 
 bool verify() { static const bool on = [] { const char *d = getenv("AVR_VERIFY"); return d && atoi(d) != 0; }(); return on; }
+bool verify_k1() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_K1"); return d && atoi(d) != 0; }(); return on; }
 
 std::string slurp(const std::string &path) {
     std::ifstream f(path, std::ios::binary);
@@ -77,6 +82,7 @@ std::string compress_bytes(const std::string &original) {            // compress
 
 std::string decompress_bytes(const std::string &recoded) {           // decompressor::run, recode.cpp:1345-1364
     host::decompressor d(recoded, device());
+    d.set_verify(verify_k1());
     h264::h264_stream_decoder dec;
     dec.residual_hooks = model_hooks();
     return d.run(&dec);
@@ -267,7 +273,7 @@ void perf_test_driver(const std::string &directory_path) {
     const unsigned threads = std::min<unsigned>(hw ? hw : 4, 32);
     shared_batch batch_in, batch_out;
     const bool on_device = device_estimators();                      // read here, once, not in the files' threads
-    const bool verify_on = verify();
+    const bool verify_on = verify(), verify_k1_on = verify_k1();
     for (size_t base = 0; base < files.size(); base += window) {
         const size_t n = std::min(window, files.size() - base);
         std::vector<file_job> jobs(n);
@@ -334,7 +340,9 @@ void perf_test_driver(const std::string &directory_path) {
                 const auto t0 = std::chrono::steady_clock::now();
                 avr_batch *b = batch_out.get(slices, bins + 16 * slices + 64);
                 for (file_job &j : jobs) if (!j.failed) j.d->add_to(b);
+                if (verify_k1_on) host::gpu_check(avr_batch_set_verify_k1(b, 1));
                 host::gpu_check(avr_batch_run(b));
+                if (verify_k1_on) host::report_verify_k1_ms(b);
                 for (file_job &j : jobs) if (!j.failed) { try { j.d->take_from(b); } catch (const std::exception &e) { log_exception(j, e); } }
                 const double ms = ms_since(t0);
                 for (file_job &j : jobs) j.d_gpu_ms = bins ? ms * double(j.d_bins) / double(bins) : 0;

@@ -612,6 +612,7 @@ class DeviceWorkload:
     def encode_resolved(self, codes):
         """Stage 2 of K1p alone: arithmetic coding from resolved codes (same bytes as encode())."""
         import torch
+        self._verify_layout, self._verify_codes = "codes", codes
         p = self._chunk_plan()
         L = lib()
         if "ws2" not in p:
@@ -626,6 +627,7 @@ class DeviceWorkload:
     def encode_codes_serial(self, codes):
         """K1 from resolved codes with one lane per slice (k_cabac_encode_codes): same bytes as encode()."""
         import torch
+        self._verify_layout, self._verify_codes = "codes", codes
         p = self._chunk_plan()
         _check(lib().avr_cabac_encode_codes_device(
             self.device_index, _stream_ptr(torch), codes.data_ptr(), p["tensors"]["res_off"].data_ptr(), self.n_bins.data_ptr(),
@@ -673,6 +675,41 @@ class DeviceWorkload:
                 self.device_index, _stream_ptr(torch), recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(), None,
                 self.n_slices, self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
                 first_bad.data_ptr()))
+        return first_bad
+
+    def verify_k1(self):
+        """K1 only (KIND_CABAC, KIND_CABAC8), behind encode() / encode_chunked() / encode_slice_major() / encode_resolved() /
+        encode_codes_serial() on torch's current stream: every AVR_SLICE_OK slice decoded back on the device by the CABAC decoder of
+        the standard against what that call read -- two-byte or one-byte tiles after encode(), the slice-major records after the two
+        slice-major calls, the codes after the two code calls -- and, where the call left final states, the decoder's states compared
+        with them.  Returns the first_bad tensor (int32; VERIFY_NONE reads as -1, n_bins: only the final states differ) and leaves the
+        statuses in self.status: SLICE_VERIFY_FAILED for a slice that does not decode.  Enqueues and returns.  (A slice that a hinted
+        run has handed to its second pass is skipped until settle() has coded it.)"""
+        import torch
+        if self.kind not in (KIND_CABAC, KIND_CABAC8):
+            raise AvrError("verify_k1: the K1 verifier exists for K1 (KIND_CABAC, KIND_CABAC8) workloads only")
+        layout = getattr(self, "_verify_layout", None)
+        if layout is None:
+            raise AvrError("verify_k1: nothing was encoded yet")
+        L, sp = lib(), _stream_ptr(torch)
+        first_bad = torch.empty(self.n_slices, dtype=torch.int32, device=self.n_bins.device)
+        init = self.init_states.data_ptr() if self.init_states is not None and self.n_states else None
+        final = self.final_states.data_ptr() if self.final_states is not None and self.n_states else None
+        tail = (self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr())
+        if layout == "codes":
+            _check(L.avr_cabac_verify_codes_device(
+                self.device_index, sp, self._verify_codes.data_ptr(), self._chunk_plan()["tensors"]["res_off"].data_ptr(),
+                self.n_bins.data_ptr(), None, self.n_slices, *tail, self.status.data_ptr(), first_bad.data_ptr()))
+        elif layout == "tiles":
+            call = L.avr_cabac8_verify_tiles_device if getattr(self, "narrow_tiles", False) else L.avr_cabac_verify_tiles_device
+            _check(call(self.device_index, sp, self.tiles.data_ptr(), self.tile_off.data_ptr(), self.n_bins.data_ptr(),
+                        self.order.data_ptr(), self.n_slices, init, self.n_states, *tail, final, self.status.data_ptr(),
+                        first_bad.data_ptr()))
+        else:
+            recs, rec_off = self._slice_major()
+            call = L.avr_cabac8_verify_slices_device if self.kind == KIND_CABAC8 else L.avr_cabac_verify_slices_device
+            _check(call(self.device_index, sp, recs.data_ptr(), rec_off.data_ptr(), self.n_bins.data_ptr(), None, self.n_slices,
+                        init, self.n_states, *tail, final, self.status.data_ptr(), first_bad.data_ptr()))
         return first_bad
 
     # ---- accounting (DESIGN.md "algorithmic bytes")

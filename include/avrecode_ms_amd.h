@@ -92,8 +92,10 @@ extern "C" {
 #define AVR_SLICE_ZERO_PROB   1  /* arithmetic_code.h:116-118 "emitted a zero-probability symbol" */
 #define AVR_SLICE_OVERFLOW    2  /* output region too small (never with the batch API's sizing) */
 #define AVR_SLICE_BAD_RECORD  3  /* a record the rule above calls malformed */
-/* Only ever set by the verifier (avr_range_verify_*_device, avr_batch_set_verify), and only on a slice that was AVR_SLICE_OK: the
- * slice's coded bytes do not decode back to the bins of its records.  The slice's bytes and length stay retrievable as they are. */
+/* Only ever set by a verifier (K2: avr_range_verify_*_device, avr_batch_set_verify; K1: avr_cabac_verify_*_device,
+ * avr_cabac8_verify_*_device, avr_batch_set_verify_k1), and only on a slice that was AVR_SLICE_OK: the slice's coded bytes do not
+ * decode back to the bins of its records (K1 also: the decoder's final context states are not the encoder's).  The slice's bytes
+ * and length stay retrievable as they are. */
 #define AVR_SLICE_VERIFY_FAILED 4           /* only ever set by the verifier */
 #define AVR_VERIFY_NONE 0xFFFFFFFFu
 
@@ -236,6 +238,20 @@ int avr_batch_timings(avr_batch *b, float ms[4]);
 int avr_batch_set_verify(avr_batch *b, int on);
 int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad);
 int avr_batch_verify_ms(avr_batch *b, float *ms);
+
+/* Verification of a K1 batch (AVR_KIND_CABAC, AVR_KIND_CABAC8, AVR_KIND_CABAC_CODES) -- the decompress direction, whose product is the
+ * user's H.264 file -- switched on by a call of its own: off by default, and then nothing of a run differs.
+ * avr_batch_set_verify_k1(b, 1): from the next avr_batch_submit on, the K1 verifier (below: avr_cabac_verify_*_device) is enqueued
+ * behind the encode on the batch's stream, over whatever that path's encoder read -- the two-byte or one-byte tiles on the
+ * one-lane-per-slice paths, the slice-major records on K1p, the codes on both code paths -- with the encoder's final states to compare
+ * where the kind has states; avr_batch_submit still does not wait.  When avr_batch_wait runs a batch a second time, or runs K1p's second
+ * pass, the verifier follows again; the last answers are the ones reported.  Everything else is avr_batch_set_verify's: the setting
+ * stays (avr_batch_reset keeps it), AVR_ERR_INVALID while the batch is in flight, AVR_SLICE_VERIFY_FAILED with the bytes as the encoder
+ * left them, avr_batch_get_verify (the first bad bin; n_bins where only the final states differ), avr_batch_timings()[2] the encode
+ * alone and avr_batch_verify_ms the verifier (one exception: where avr_batch_wait ran K1p's second pass, [2] also holds the host's wait
+ * and the copies between the two runs -- an upper bound of the encode).  K1 verification exists for the decompress direction only: with it on, avr_batch_submit
+ * of a K2 batch returns AVR_ERR_INVALID.  avr_batch_set_verify and its rule for K1 batches are unchanged. */
+int avr_batch_set_verify_k1(avr_batch *b, int on);
 
 /* ------------------------------------------------------------------ one batch over several GPUs
  * Slices are independent (one coder object each in the reference, recode.cpp:1270, :1525), so a batch shards
@@ -386,6 +402,62 @@ int avr_range_verify_slices_device(int device, void *stream, const uint16_t *rec
                                    const uint32_t *n_bins, const uint32_t *order /* may be NULL */, size_t n_slices,
                                    const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
                                    int32_t *status, uint32_t *first_bad);
+
+/* K1 verifier: the arithmetic decoder of ITU-T H.264 (9.3.1.2; 9.3.3.2: DecodeDecision, DecodeBypass, DecodeTerminate) over slices
+ * whose records are known, one lane per slice.  A K1 slice's output is a standard CABAC stream and every bin's context is known from the
+ * records, so the decoder is handed the context of each bin, decodes the bin and compares it with the record's.  It is written from
+ * the standard, has no carries, no deferred digits and no finish(), and works the context states out itself by the sequential rule of
+ * Figure 9-3 in the CALLER's numbering (no dense renumbering): it is independent of the encoders -- the one-lane kernels, K1p's
+ * speculative replay, census, dense map, chains and phase D, the one-byte and the code forms -- except for one thing it shares with
+ * them, rangeTabLPS and the state transitions (avr_cabac_lps_range_table / avr_cabac_mlps_state_table hold the same values).
+ * WHAT IT COSTS: one lane per slice is a slice's whole serial chain, so on batches of few, long slices (K1p's shapes) it takes a
+ * multiple of the encode; a chunk-parallel verifier would start from the encoder's own per-chunk states and would not be independent.
+ * Five record forms behind the same walk:
+ *   avr_cabac_verify_tiles_device    two-byte tiles, as avr_cabac_encode_tiles_device reads them; n_states <= AVR_MAX_STATES
+ *   avr_cabac_verify_slices_device   two-byte records, slice-major (rec_off in records, multiples of 8; padding never decoded)
+ *   avr_cabac8_verify_tiles_device   one-byte tiles, the layout of avr_pack_tiles8_narrow_device; n_states <= AVR_MAX_STATES8
+ *   avr_cabac8_verify_slices_device  one-byte records, slice-major (rec_off in bytes, multiples of 16, readable to the next multiple of 16)
+ *   avr_cabac_verify_codes_device    resolved codes (AVR_CODE_*) at res_off[i] (bytes, multiples of 16, readable to the next multiple
+ *                                    of 16): each code is the (symbol, *state) pair itself, so no states are kept -- code < 252 is a
+ *                                    context bin at state code >> 1, 252 / 253 bypass, 254 / 255 a decision at pStateIdx 63 (LPS range 2
+ *                                    in every quarter), which for a slice's last bin is DecodeTerminate
+ * init_states: n_slices * n_states bytes, as the encoder was given; final_states: the encoder's, or NULL.  status is in/out:
+ *   a slice whose status is not AVR_SLICE_OK on entry is skipped: its status stays, first_bad[slice] = AVR_VERIFY_NONE;
+ *   an AVR_SLICE_OK slice has bins 0 .. n_bins - 1 decoded in order from out[out_off[i] .. out_off[i] + min(out_len[i], capacity));
+ *   at the first bin that decodes to another value (or whose selector is no context of the slice, bypass or terminate) the lane stops
+ *   with its chunk: first_bad[slice] = that bin's index, status[slice] = AVR_SLICE_VERIFY_FAILED;
+ *   where every bin decoded right and final_states is given, the decoder's own states are compared with it, all n_states bytes:
+ *   a difference is first_bad[slice] = n_bins (no bin has that index) with AVR_SLICE_VERIFY_FAILED;
+ *   otherwise first_bad[slice] = AVR_VERIFY_NONE and the status stays AVR_SLICE_OK.
+ * Records at an index >= n_bins are never decoded, whatever they hold.  first_bad may be NULL in the tiles calls.  Nothing else is
+ * written: not out, out_len, records, tiles or states.  Bits at or past a slice's length read as zero whatever the region holds there,
+ * and nothing outside a slice's region is read.  The calls enqueue on `stream` and return: they never block, allocate or use a
+ * workspace.  Refused before anything touches a device (AVR_ERR_INVALID): a null pointer with n_slices > 0 (order may be NULL in the
+ * slices and codes calls, init_states when n_states is 0), n_slices >= 2^31, n_states above the form's limit. */
+int avr_cabac_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off,
+                                  const uint32_t *n_bins, const uint32_t *order, size_t n_slices,
+                                  const uint8_t *init_states, size_t n_states,
+                                  const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                  const uint8_t *final_states /* may be NULL */, int32_t *status, uint32_t *first_bad /* may be NULL */);
+int avr_cabac_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off,
+                                   const uint32_t *n_bins, const uint32_t *order /* may be NULL */, size_t n_slices,
+                                   const uint8_t *init_states, size_t n_states,
+                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                   const uint8_t *final_states /* may be NULL */, int32_t *status, uint32_t *first_bad);
+int avr_cabac8_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off,
+                                   const uint32_t *n_bins, const uint32_t *order, size_t n_slices,
+                                   const uint8_t *init_states, size_t n_states,
+                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                   const uint8_t *final_states /* may be NULL */, int32_t *status, uint32_t *first_bad /* may be NULL */);
+int avr_cabac8_verify_slices_device(int device, void *stream, const uint8_t *recs8, const uint64_t *rec_off,
+                                    const uint32_t *n_bins, const uint32_t *order /* may be NULL */, size_t n_slices,
+                                    const uint8_t *init_states, size_t n_states,
+                                    const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                    const uint8_t *final_states /* may be NULL */, int32_t *status, uint32_t *first_bad);
+int avr_cabac_verify_codes_device(int device, void *stream, const uint8_t *codes, const uint64_t *res_off,
+                                  const uint32_t *n_bins, const uint32_t *order /* may be NULL */, size_t n_slices,
+                                  const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                                  int32_t *status, uint32_t *first_bad);
 
 /* K1, intra-slice parallel form ("K1p", avrecode-ms_amd/csrc/avr_k1p.h): the same bytes as
  * avr_cabac_encode_tiles_device, produced by many lanes per slice -- for batches of few, long
