@@ -39,9 +39,9 @@ SLICE_VERIFY_FAILED, VERIFY_NONE = 4, 0xFFFFFFFF             # only ever set by 
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_api.cpp"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_api.cpp"]
 _DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
-                    "avr_verify.h", "avr_cabac_verify.h"]
+                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h"]
 
 
 class AvrError(RuntimeError):
@@ -154,6 +154,11 @@ SIGNATURES = {
     "avr_range_resolve_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
     "avr_range_resolve_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "avr_range_keys_verify_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
+    "avr_range_keys_verify_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "avr_batch_get_verify_est": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_batch_verify_est_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "avr_batch_reserve_slice": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_size_t, POINTER(c_void_p)]),
     "avr_batch_submit": (c_int, [c_void_p]),
     "avr_batch_wait": (c_int, [c_void_p]),
@@ -298,7 +303,8 @@ def test_hooks(**hooks):
     """FOR tests/ ONLY.  Inside the block, lib() is libavrecode_hip_hooks.so -- the same sources built with
     -DAVR_TEST_HOOKS -- with the named hooks set (csrc/avr_internal.h: k1p_force_retry_every, census_stride,
     chain_lanes, k1_form_ref, k1_path [1 serial, 2 chunked], no_dense, no_hint, k2p_seg_len, local_waves, k2p_wave); all of them keep the bytes exact and
-    only force paths that real batches take rarely -- except verify_flip, which corrupts one slice's first byte on the device in front of the verifier (a batch with
+    only force paths that real batches take rarely -- except est_flip / est_flip_bin, which add one to neg of one resolved record of a batch of key records with set_verify on
+    (between the resolver and the encode: only the estimator checker can see it), verify_flip, which corrupts one slice's first byte on the device in front of the verifier (a batch with
     set_verify or set_verify_k1 on) so that a test sees a failure travel through the batch API, and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
     AVR_SLICE_RETRY_SERIAL) so that a test can see which ones it coded itself.  The product library has no such switches."""
     global _lib, _hooks_lib
@@ -505,6 +511,19 @@ class Batch:
         """Milliseconds of the verifier in the last run (0 with verify off); timings()["encode_ms"] is the encode alone."""
         ms = c_float()
         _check(self._L.avr_batch_verify_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def get_verify_est(self, i: int) -> int:
+        """Batches of key records with set_verify on: index of slice i's first bin whose resolved estimator does not follow the model
+        (n_bins: its padding or its group's table afterwards), or VERIFY_NONE -- also for other kinds and with verify off."""
+        v = c_uint32()
+        _check(self._L.avr_batch_get_verify_est(self._h, i, ctypes.byref(v)))
+        return v.value
+
+    def verify_est_ms(self) -> float:
+        """Milliseconds of the estimator checker in the last run (0 where it did not run); not part of verify_ms()."""
+        ms = c_float()
+        _check(self._L.avr_batch_verify_est_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
 

@@ -174,6 +174,12 @@ struct avr_batch {
     float verify_ms = 0;
     DevBuf<uint32_t> d_first_bad;
     PinBuf<uint32_t> h_first_bad;
+    // ... and of a run of key records the estimator checker (avr_est_verify.hip) behind it, with events and answers of its own
+    bool verified_est = false;              // the run in flight / the last run had it
+    hipEvent_t eev[2] = {};                 // start and end of the checker (created with vev)
+    float verify_est_ms = 0;
+    DevBuf<uint32_t> d_first_bad_est;
+    PinBuf<uint32_t> h_first_bad_est;
 };
 
 // One plan array to the device through the batch's pinned arena: the copy is asynchronous for real (a copy from
@@ -255,6 +261,8 @@ int avr_test_hook_set(const char *name, uint32_t value) {
     else if (!strcmp(name, "chain_segments")) h.chain_segments = value;
     else if (!strcmp(name, "chain_force_redo")) h.chain_force_redo = value;
     else if (!strcmp(name, "verify_flip")) h.verify_flip = value;
+    else if (!strcmp(name, "est_flip")) h.est_flip = value;
+    else if (!strcmp(name, "est_flip_bin")) h.est_flip_bin = value;
     else if (!strcmp(name, "reset")) h = avr::TestHooks{};
     else return fail(AVR_ERR_INVALID, "unknown test hook %s", name);
     return AVR_OK;
@@ -306,7 +314,7 @@ void avr_batch_destroy(avr_batch *b) {
     b->d_recs.release(); b->d_recs8.release(); b->d_tiles.release(); b->d_rec_off.release(); b->d_tile_off.release();
     b->d_out_off.release(); b->d_dense_off.release(); b->d_n_bins.release(); b->d_order.release();
     b->d_out_len.release(); b->d_status.release(); b->d_states.release(); b->d_final.release();
-    b->d_out.release(); b->d_dense.release();
+    b->d_out.release(); b->d_dense.release(); b->d_first_bad_est.release(); b->h_first_bad_est.release();
     b->d_res_off.release(); b->d_dig_off.release(); b->d_chunk_base.release(); b->d_chunk_slice.release();
     b->d_blk_base.release(); b->d_blk_slice.release(); b->d_workspace.release();
     b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release();
@@ -314,6 +322,7 @@ void avr_batch_destroy(avr_batch *b) {
     b->d_first_bad.release(); b->h_first_bad.release();
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->vev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : b->eev) if (e) (void)hipEventDestroy(e);
     if (b->stream) { avr::forget_part_streams(b->stream); avr::forget_stream(b->stream); (void)hipStreamDestroy(b->stream); }
     delete b;
 }
@@ -490,6 +499,8 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
         return rc;
     b->verified = b->verify_k1;
     if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
+    b->verified_est = b->verified && b->keys;
+    if (b->verified_est && ((rc = b->d_first_bad_est.reserve(n)) || (rc = b->h_first_bad_est.reserve(n)))) return rc;
     hipStream_t s = b->stream;
     b->plan_used = 0;
     b->hint_used = 0;
@@ -541,6 +552,23 @@ static int resolve_keys(avr_batch *b, uint32_t n32) {
     AVR_HIP(avr::launch_est_resolve(s, b->d_keys.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p, uint32_t(n_groups),
                                     b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, b->d_chunk_base.p,
                                     b->d_chunk_slice.p, total_chunks, avr::align256(b->d_est_ws.p), b->d_recs.p, b->d_status.p));
+#ifdef AVR_TEST_HOOKS
+    if (const uint32_t k = avr::test_hooks().est_flip; k && k <= n32 && b->verified)
+        AVR_HIP(avr::launch_est_flip(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, k - 1, avr::test_hooks().est_flip_bin));
+#endif
+    return AVR_OK;
+}
+
+// The estimator checker behind the K2 verifier of a run of key records, between events of its own: the resolver's records held to the
+// key records and the tables, in the resolver's workspace (it is done with it, and the checker's is no larger).
+static int enqueue_verify_est(avr_batch *b, uint32_t n32) {
+    hipStream_t s = b->stream;
+    AVR_HIP(hipEventRecord(b->eev[0], s));
+    AVR_HIP(avr::launch_est_verify(s, b->d_keys.p, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p,
+                                   uint32_t(b->group_first.size()), b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p,
+                                   b->d_chunk_base.p, b->d_chunk_slice.p, b->hp.chunk_base.back(), avr::align256(b->d_est_ws.p),
+                                   b->d_status.p, b->d_first_bad_est.p));
+    AVR_HIP(hipEventRecord(b->eev[1], s));
     return AVR_OK;
 }
 
@@ -615,6 +643,8 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
     b->verified = cabac ? b->verify_k1 : b->verify;
     if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
+    b->verified_est = b->verified && b->keys;
+    if (b->verified_est && ((rc = b->d_first_bad_est.reserve(n)) || (rc = b->h_first_bad_est.reserve(n)))) return rc;
 
     hipStream_t s = b->stream;
     b->plan_used = 0;
@@ -653,6 +683,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         AVR_HIP(avr::launch_k2p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_chunk_base.p, b->d_chunk_slice.p,
                                 plan.total_chunks, total_out, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p));
         if (b->verified && (rc = enqueue_verify(b, n32, false))) return rc;      // over the slice-major records K2p read
+        if (b->verified_est && (rc = enqueue_verify_est(b, n32))) return rc;
     } else if (chunked) {
         b->plan = plan;
         AVR_HIP(hipEventRecord(b->ev[2], s));
@@ -687,6 +718,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
             rc = enqueue_verify_k1(b, n32, b->recs8 ? avr::cabac_verify::kTiles8 : avr::cabac_verify::kTiles2, b->d_tiles.p, b->d_tile_off.p, b->d_order.p);
         else if (b->verified) rc = enqueue_verify(b, n32, true);
         if (rc) return rc;
+        if (b->verified_est && (rc = enqueue_verify_est(b, n32))) return rc;
     }
     return enqueue_lengths(b, n32);
 }
@@ -701,6 +733,7 @@ static int enqueue_lengths(avr_batch *b, uint32_t n32) {
     AVR_HIP(hipMemcpyAsync(b->h_status.p, b->d_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (with_states) AVR_HIP(hipMemcpyAsync(b->h_final.p, b->d_final.p, n * ns, hipMemcpyDeviceToHost, s));
     if (b->verified) AVR_HIP(hipMemcpyAsync(b->h_first_bad.p, b->d_first_bad.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (b->verified_est) AVR_HIP(hipMemcpyAsync(b->h_first_bad_est.p, b->d_first_bad_est.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return AVR_OK;
 }
 
@@ -715,7 +748,7 @@ int avr_batch_submit(avr_batch *b) {
         return fail(AVR_ERR_INVALID, "verification exists for the compress direction only: not for a K1 batch");
     if (b->verify_k1 && b->kind == AVR_KIND_RANGE)
         return fail(AVR_ERR_INVALID, "K1 verification exists for the decompress direction only: not for a K2 batch");
-    b->verified = false;
+    b->verified = b->verified_est = false;
     if (n == 0) { b->in_flight = true; return AVR_OK; }
     const bool use_hint = b->dense_hint > 0 && !avr::no_hint();
     if (int rc = submit_impl(b, use_hint)) { (void)hipStreamSynchronize(b->stream); return rc; }
@@ -793,6 +826,8 @@ int avr_batch_wait(avr_batch *b) {
         b->ms[2] -= verify_before;
         b->verify_ms += verify_before;
     }
+    b->verify_est_ms = 0;
+    if (b->verified_est) (void)hipEventElapsedTime(&b->verify_est_ms, b->eev[0], b->eev[1]);
     b->ran = true;                                               // only now: the getters hand out h_out / h_status
     return AVR_OK;
 }
@@ -858,6 +893,10 @@ int avr_batch_set_verify(avr_batch *b, int on) {
         if (int rc = select_device(b->device)) return rc;
         for (auto &e : b->vev) AVR_HIP(hipEventCreate(&e));
     }
+    if (on && !b->eev[0]) {
+        if (int rc = select_device(b->device)) return rc;
+        for (auto &e : b->eev) AVR_HIP(hipEventCreate(&e));
+    }
     b->verify = on != 0;
     return AVR_OK;
 }
@@ -883,6 +922,19 @@ int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad) {
 int avr_batch_verify_ms(avr_batch *b, float *ms) {
     if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
     *ms = b->verify_ms;
+    return AVR_OK;
+}
+
+int avr_batch_get_verify_est(avr_batch *b, size_t slice, uint32_t *first_bad) {
+    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
+    if (first_bad) *first_bad = b->verified_est ? b->h_first_bad_est.p[slice] : AVR_VERIFY_NONE;
+    return AVR_OK;
+}
+
+int avr_batch_verify_est_ms(avr_batch *b, float *ms) {
+    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
+    *ms = b->verify_est_ms;
     return AVR_OK;
 }
 
@@ -1332,6 +1384,38 @@ int avr_range_resolve_device(int device, void *stream, const uint16_t *keys, con
     AVR_HIP(avr::launch_est_resolve(static_cast<hipStream_t>(stream), keys, rec_off, n_bins, uint32_t(n_slices), group_first,
                                     uint32_t(n_groups), est_in, est_out, plan->chunk_base, plan->chunk_slice, plan->total_chunks,
                                     workspace, recs_out, status));
+    return AVR_OK;
+}
+
+size_t avr_range_keys_verify_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan) {
+    (void)n_groups;
+    if (!plan) return 0;
+    return avr::est_verify_layout(n_slices, plan->total_chunks).total;
+}
+
+int avr_range_keys_verify_device(int device, void *stream, const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off,
+                                 const uint32_t *n_bins, size_t n_slices, const uint32_t *group_first, size_t n_groups,
+                                 const uint8_t *est_in, const uint8_t *est_out, const avr_chunk_plan *plan, void *workspace,
+                                 size_t workspace_bytes, int32_t *status, uint32_t *first_bad) {
+    if (int rc = check_common(rec_off, n_bins, keys, n_slices)) return rc;
+    if (n_groups > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_groups out of range");
+    if (n_slices && (n_groups == 0 || n_groups > n_slices))
+        return fail(AVR_ERR_INVALID, "n_groups %zu: a batch of %zu slices has between 1 and %zu groups", n_groups, n_slices, n_slices);
+    if (n_slices && (!group_first || !recs || !status || !first_bad)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice))) return fail(AVR_ERR_INVALID, "null plan pointer");
+    if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
+    if (workspace_bytes < avr::est_verify_layout(n_slices, plan->total_chunks).total)
+        return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than avr_range_keys_verify_workspace_bytes()", workspace_bytes);
+    if (n_slices && recs == keys) return fail(AVR_ERR_INVALID, "recs must not alias keys");
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(recs)) & 15)
+        return fail(AVR_ERR_INVALID, "keys / recs not 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(est_in) | reinterpret_cast<uintptr_t>(est_out)) & 1)
+        return fail(AVR_ERR_INVALID, "est_in / est_out not 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AVR_ERR_INVALID, "workspace not 256-byte aligned");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_est_verify(static_cast<hipStream_t>(stream), keys, recs, rec_off, n_bins, uint32_t(n_slices), group_first,
+                                   uint32_t(n_groups), est_in, est_out, plan->chunk_base, plan->chunk_slice, plan->total_chunks,
+                                   workspace, status, first_bad));
     return AVR_OK;
 }
 

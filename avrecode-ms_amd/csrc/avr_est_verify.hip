@@ -1,0 +1,272 @@
+// The estimator checker (avr_est_verify.h): resolved K2 records held to their key records and to each other.  Kernels and launcher.
+// Writes first_bad and status only; reads nothing outside a slice's records and their padding to the next multiple of eight.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "avr_est_verify.h"
+#include "avr_internal.h"
+
+namespace avr {
+namespace {
+
+using namespace estv;
+
+struct EstvParams {
+    const uint16_t *keys, *recs;
+    const uint64_t *rec_off;
+    const uint32_t *n_bins;
+    const uint32_t *group_first;
+    const uint16_t *est_in, *est_out;       // {pos, neg} byte pairs read as pos | neg << 8
+    const uint32_t *chunk_base, *chunk_slice;
+    uint32_t *slice_group;
+    uint16_t *tab, *agg;
+    int32_t *status;
+    uint32_t *first_bad;
+    uint32_t n_slices, n_groups, total_chunks;
+};
+
+// one chunk: its slice, its first bin in the slice, its bins, its records with the slice's padding, its first record
+struct ChunkAt { uint32_t s, start, n, padded; uint64_t base; };
+__device__ inline ChunkAt chunk_at(const EstvParams &p, uint32_t c) {
+    ChunkAt k;
+    k.s = p.chunk_slice[c];
+    const uint32_t nb = p.n_bins[k.s];
+    k.start = (c - p.chunk_base[k.s]) * kChunk;
+    k.n = nb > k.start ? min(kChunk, nb - k.start) : 0u;
+    k.padded = padded_bins(k.start, k.n, nb);
+    k.base = p.rec_off[k.s] + k.start;
+    return k;
+}
+__device__ inline Group group_at(const EstvParams &p, uint32_t c) {
+    Group r;
+    r.g = p.slice_group[p.chunk_slice[c]];
+    r.a = p.chunk_base[p.group_first[r.g]];
+    r.b = p.chunk_base[p.group_first[r.g + 1]];
+    return r;
+}
+__device__ inline uint32_t start_entry(const EstvParams &p, uint32_t g, uint32_t k) {
+    return p.est_in ? p.est_in[size_t(g) * kKeys + k] : kFresh;
+}
+__device__ inline bool takes_part(const EstvParams &p, uint32_t s) { return p.status[s] != kBadRecord; }
+
+// the lanes of the wave that hold this lane's key
+__device__ inline uint64_t same_key(uint32_t key, bool valid) {
+    uint64_t m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 11; b++) {
+        const bool bit = (key >> b) & 1u;
+        const uint64_t bb = __ballot(bit);
+        m &= bit ? bb : ~bb;
+    }
+    return m;
+}
+
+// slice -> group; no finding yet
+__global__ __launch_bounds__(256) void k_estv_prep(EstvParams p) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n_slices) return;
+    uint32_t lo = 0, hi = p.n_groups - 1;                        // the last group that starts at or before slice i
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) / 2;
+        if (p.group_first[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    p.slice_group[i] = lo;
+    p.first_bad[i] = kNone;
+}
+
+// per piece of a crossing group and key: what the key's next bin must carry after the piece (0: not met).  Any order: 16-byte loads,
+// one LDS atomicMax on position << 16 | next per bin.
+__global__ __launch_bounds__(64) void k_estv_last(EstvParams p) {
+    __shared__ uint32_t last[kTabStride];
+    const uint32_t w = blockIdx.x, lane = threadIdx.x;
+    Piece pc[2];
+    span_pieces(w, kSpan, p.total_chunks, [&](uint32_t c) { return group_at(p, c); }, pc);
+    for (int pi = 0; pi < 2; pi++) {
+        if (pc[pi].c0 >= pc[pi].c1) continue;
+        for (uint32_t k = lane; k < kTabStride; k += 64) last[k] = 0;
+        __syncthreads();
+        for (uint32_t c = pc[pi].c0; c < pc[pi].c1; c++) {
+            const ChunkAt ck = chunk_at(p, c);
+            if (!takes_part(p, ck.s)) continue;
+            const uint4 *ksrc = reinterpret_cast<const uint4 *>(p.keys + ck.base);
+            const uint4 *rsrc = reinterpret_cast<const uint4 *>(p.recs + ck.base);
+            const uint32_t at = (c - pc[pi].c0) * kChunk;        // below 2^16: a piece has at most kSpan chunks
+            for (uint32_t v = lane; v * 8 < ck.n; v += 64) {
+                const uint4 kq = ksrc[v], rq = rsrc[v];
+                const uint32_t kw[4] = {kq.x, kq.y, kq.z, kq.w}, rw[4] = {rq.x, rq.y, rq.z, rq.w};
+#pragma unroll
+                for (uint32_t e = 0; e < 8; e++) {
+                    const uint32_t krec = (kw[e / 2] >> (16 * (e & 1))) & 0xffffu, rrec = (rw[e / 2] >> (16 * (e & 1))) & 0xffffu;
+                    if (v * 8 + e < ck.n && key_ok(krec)) atomicMax(&last[krec >> 1], last_entry(at + v * 8 + e, next_of(rrec, krec)));
+                }
+            }
+        }
+        __syncthreads();
+        uint16_t *dst = p.tab + size_t(2 * w + pi) * kTabStride;
+        for (uint32_t k = lane; k < kKeys; k += 64) dst[k] = uint16_t(last[k]);
+        __syncthreads();
+    }
+}
+
+// The walk over a crossing group's pieces, in blocks (avr_est_verify.h): every block's aggregate -- per key the last piece of the
+// block that met it -- into the second table of the block's last slot ...
+__global__ __launch_bounds__(256) void k_estv_agg(EstvParams p) {
+    const uint32_t w = blockIdx.x;
+    Piece pc[2];
+    BlockHead heads[2];
+    span_pieces(w, kSpan, p.total_chunks, [&](uint32_t c) { return group_at(p, c); }, pc);
+    span_block_heads(w, kSpan, pc, heads);
+    const uint16_t *__restrict__ tab = p.tab;
+    uint16_t *__restrict__ agg = p.agg;
+    for (int h = 0; h < 2; h++) {
+        if (!heads[h].any) continue;
+        const PieceSeq seq = heads[h].seq;
+        const uint32_t i0 = heads[h].kb * kPieceBlock, i1 = seq.block_end(heads[h].kb);
+        for (uint32_t k = threadIdx.x; k < kKeys; k += 256) {
+            uint32_t a = 0;
+#pragma unroll 8
+            for (uint32_t i = i0; i < i1; i++) a = then(a, tab[size_t(seq.slot(i)) * kTabStride + k]);
+            agg[size_t(seq.slot(i1 - 1)) * kTabStride + k] = uint16_t(a);
+        }
+    }
+}
+// ... then every piece's table turned, in place, into the table at the piece's START
+__global__ __launch_bounds__(256) void k_estv_start(EstvParams p) {
+    const uint32_t w = blockIdx.x;
+    Piece pc[2];
+    BlockHead heads[2];
+    span_pieces(w, kSpan, p.total_chunks, [&](uint32_t c) { return group_at(p, c); }, pc);
+    span_block_heads(w, kSpan, pc, heads);
+    const uint16_t *__restrict__ agg = p.agg;
+    uint16_t *tab = p.tab;
+    for (int h = 0; h < 2; h++) {
+        if (!heads[h].any) continue;
+        const PieceSeq seq = heads[h].seq;
+        const uint32_t i0 = heads[h].kb * kPieceBlock, i1 = seq.block_end(heads[h].kb);
+        for (uint32_t k = threadIdx.x; k < kKeys; k += 256) {
+            uint32_t cur = start_entry(p, heads[h].g, k);
+#pragma unroll 8
+            for (uint32_t kb = 0; kb < heads[h].kb; kb++) cur = then(cur, agg[size_t(seq.slot(seq.block_end(kb) - 1)) * kTabStride + k]);
+            uint32_t i = i0;
+            for (; i + 8 <= i1; i += 8) {                        // the addresses do not depend on cur: eight loads in flight
+                uint32_t nx[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++) nx[j] = tab[size_t(seq.slot(i + j)) * kTabStride + k];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++) { tab[size_t(seq.slot(i + j)) * kTabStride + k] = uint16_t(cur); cur = then(cur, nx[j]); }
+            }
+            for (; i < i1; i++) {
+                const size_t at = size_t(seq.slot(i)) * kTabStride + k;
+                const uint32_t nx = tab[at];
+                tab[at] = uint16_t(cur);
+                cur = then(cur, nx);
+            }
+        }
+    }
+}
+
+// The check: a span's chunks in stream order, the table of the group at hand in LDS, 64 bins a step.
+__global__ __launch_bounds__(64) void k_estv_check(EstvParams p) {
+    __shared__ uint16_t tab[kTabStride];
+    __shared__ __attribute__((aligned(16))) uint16_t kbuf[kChunk];
+    __shared__ __attribute__((aligned(16))) uint16_t rbuf[kChunk];
+    const uint32_t w = blockIdx.x, lane = threadIdx.x;
+    const uint32_t lo = w * kSpan, hi = min(lo + kSpan, p.total_chunks);
+    for (uint32_t c = lo; c < hi; c++) {
+        const ChunkAt ck = chunk_at(p, c);
+        const Group gr = group_at(p, c);
+        if (c == lo || c == gr.a) {                              // a group's first chunk: its start table; a span's: the piece's
+            __syncthreads();
+            if (c == gr.a) for (uint32_t k = lane; k < kKeys; k += 64) tab[k] = uint16_t(start_entry(p, gr.g, k));
+            else for (uint32_t k = lane; k < kKeys; k += 64) tab[k] = p.tab[size_t(2 * w) * kTabStride + k];
+            __syncthreads();
+        }
+        if (!takes_part(p, ck.s)) continue;                      // (uniform; and so is every later slice of the group)
+        __syncthreads();                                         // the chunk before is done with the buffers
+        for (uint32_t v = lane; v * 8 < ck.n; v += 64)
+            reinterpret_cast<uint4 *>(kbuf)[v] = reinterpret_cast<const uint4 *>(p.keys + ck.base)[v];
+        for (uint32_t v = lane; v * 8 < ck.padded; v += 64)      // (padded: a multiple of eight, as the chunk's start is)
+            reinterpret_cast<uint4 *>(rbuf)[v] = reinterpret_cast<const uint4 *>(p.recs + ck.base)[v];
+        __syncthreads();
+        bool pad_bad = false;
+        for (uint32_t i0 = 0; i0 < ck.padded; i0 += 64) {
+            const uint32_t idx = i0 + lane;
+            const bool in_chunk = idx < ck.n;
+            const uint32_t krec = in_chunk ? kbuf[idx] : 0u, rrec = idx < ck.padded ? rbuf[idx] : 0u;
+            const bool valid = in_chunk && key_ok(krec);
+            const uint32_t key = krec >> 1;
+            const uint64_t mask = same_key(key, valid);
+            const uint32_t nx = next_of(rrec, krec);
+            const int from = valid ? lower_lane(mask, lane) : -1;
+            const uint32_t left = uint32_t(__shfl(int(nx), from < 0 ? int(lane) : from));
+            const uint32_t expected = from >= 0 ? left : valid ? tab[key] : 0u;
+            const bool bad = in_chunk && bin_bad(krec, rrec, expected);
+            pad_bad |= !in_chunk && rrec != 0;                   // condition 4 (rrec is 0 beyond `padded`)
+            __syncthreads();                                     // every lane has read the table
+            if (valid && (mask >> lane) == 1) tab[key] = uint16_t(nx);      // the key's last lane of the step
+            __syncthreads();
+            const uint64_t bads = __ballot(bad);
+            if (bads && lane == uint32_t(__builtin_ctzll(bads))) atomicMin(&p.first_bad[ck.s], ck.start + idx);
+        }
+        if (__ballot(pad_bad) && lane == 0) atomicMin(&p.first_bad[ck.s], p.n_bins[ck.s]);
+        if (c + 1 == gr.b && p.est_out) {                        // condition 5 (this chunk's slice is the group's last, and it takes part)
+            bool diff = false;
+            for (uint32_t k = lane; k < kKeys; k += 64) diff |= tab[k] != p.est_out[size_t(gr.g) * kKeys + k];
+            if (__ballot(diff) && lane == 0) atomicMin(&p.first_bad[ck.s], p.n_bins[ck.s]);
+        }
+    }
+}
+
+// a slice with a finding goes from AVR_SLICE_OK to AVR_SLICE_VERIFY_FAILED; any other status stays
+__global__ __launch_bounds__(256) void k_estv_status(EstvParams p) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < p.n_slices && p.first_bad[i] != kNone && p.status[i] == kOk) p.status[i] = kVerifyFailed;
+}
+
+#ifdef AVR_TEST_HOOKS
+// Test build only (est_flip, avr_internal.h): one added to neg of one resolved record (neg <= 96: the field stays valid and non-zero)
+__global__ void k_est_flip(uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t slice, uint32_t bin) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && bin < n_bins[slice]) recs[rec_off[slice] + bin] += 0x100u;
+}
+#endif
+
+}  // namespace
+
+hipError_t launch_est_verify(hipStream_t s, const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                             uint32_t n_slices, const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in,
+                             const uint8_t *est_out, const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks,
+                             void *workspace, int32_t *status, uint32_t *first_bad) {
+    if (n_slices == 0 || n_groups == 0) return hipSuccess;
+    EstvParams p{};
+    p.keys = keys; p.recs = recs; p.rec_off = rec_off; p.n_bins = n_bins; p.group_first = group_first;
+    p.est_in = reinterpret_cast<const uint16_t *>(est_in);
+    p.est_out = reinterpret_cast<const uint16_t *>(est_out);
+    p.chunk_base = chunk_base; p.chunk_slice = chunk_slice;
+    const EstVerifyLayout L = est_verify_layout(n_slices, total_chunks);
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    p.slice_group = reinterpret_cast<uint32_t *>(ws + L.slice_group);
+    p.tab = reinterpret_cast<uint16_t *>(ws + L.tab);
+    p.agg = reinterpret_cast<uint16_t *>(ws + L.agg);
+    p.status = status; p.first_bad = first_bad;
+    p.n_slices = n_slices; p.n_groups = n_groups; p.total_chunks = total_chunks;
+    const uint32_t n_spans = (total_chunks + kSpan - 1) / kSpan;
+    k_estv_prep<<<(n_slices + 255) / 256, 256, 0, s>>>(p);
+    if (n_spans) {
+        k_estv_last<<<n_spans, 64, 0, s>>>(p);
+        k_estv_agg<<<n_spans, 256, 0, s>>>(p);
+        k_estv_start<<<n_spans, 256, 0, s>>>(p);
+        k_estv_check<<<n_spans, 64, 0, s>>>(p);
+    }
+    k_estv_status<<<(n_slices + 255) / 256, 256, 0, s>>>(p);
+    return hipGetLastError();
+}
+
+#ifdef AVR_TEST_HOOKS
+hipError_t launch_est_flip(hipStream_t s, uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t slice, uint32_t bin) {
+    hipLaunchKernelGGL(k_est_flip, dim3(1), dim3(64), 0, s, recs, rec_off, n_bins, slice, bin);
+    return hipGetLastError();
+}
+#endif
+
+}  // namespace avr

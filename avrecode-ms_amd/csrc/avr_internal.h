@@ -54,6 +54,8 @@ struct TestHooks {
     uint32_t k1_waves;               // one-lane-per-slice K1: waves to a workgroup (0 = the built-in count)
     uint32_t k2p_wave;               // K2p pass 1: 1 = a wave per slice, 2 = a lane per slice, 3 = a lane per slice and a wave each for the longest (0 = by slice count)
     uint32_t verify_flip;            // batch API with verify on: k > 0 complements bit 7 of byte 0 of slice k - 1's output region between the encode and the verifier
+    uint32_t est_flip, est_flip_bin; // batch API with verify on, key records: k > 0 adds one to neg of bin est_flip_bin of slice k - 1's resolved record, between the
+                                     // resolver and the encode: encoder and K2 verifier agree on the wrong pair, only the estimator checker can see it
     uint32_t k1p_keep_retry;         // K1p (every form): the slices that leave the parallel path -- declined by the scheme, handed over by phase D -- keep
                                      // AVR_SLICE_RETRY_SERIAL (no serial kernel after it), so a test sees which slices phase D coded itself
 };
@@ -197,6 +199,15 @@ hipError_t launch_est_resolve(hipStream_t s, const uint16_t *keys, const uint64_
                               const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in, uint8_t *est_out,
                               const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, void *workspace,
                               uint16_t *recs_out, int32_t *status);
+// the estimator checker (avr_est_verify.hip): resolved records held to their key records and to each other (avr_est_verify.h);
+// workspace est_verify_layout(n_slices, total_chunks).total bytes; writes status and first_bad only; never waits
+hipError_t launch_est_verify(hipStream_t s, const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                             uint32_t n_slices, const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in,
+                             const uint8_t *est_out, const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks,
+                             void *workspace, int32_t *status, uint32_t *first_bad);
+#ifdef AVR_TEST_HOOKS
+hipError_t launch_est_flip(hipStream_t s, uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t slice, uint32_t bin);
+#endif
 hipError_t launch_synth_slices(hipStream_t s, int workload, uint32_t scale, uint64_t seed, uint64_t first_slice,
                                int kind, uint32_t n_slices, const uint64_t *rec_off, uint16_t *recs,
                                uint8_t *init_states, uint32_t n_states);

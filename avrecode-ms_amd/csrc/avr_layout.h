@@ -121,4 +121,27 @@ inline EstLayout est_layout(uint64_t n_slices, uint64_t n_groups, uint64_t total
     return L;
 }
 
+// ------------------------------------------------------------------ the estimator checker (avr_est_verify.hip)
+
+namespace estv {
+constexpr uint32_t kTabStride = 1028;                  // a 16-bit table's stride in the workspace
+constexpr uint32_t kSpan = 16;                         // chunks per span (the checker's own: nothing ties it to the resolver's window)
+inline uint64_t n_slots(uint64_t total_chunks, uint32_t S) { return 2 * ((total_chunks + S - 1) / S); }
+}  // namespace estv
+
+// slice -> group, then per piece slot a 16-bit table (what the key's next bin must carry after the piece, then the table at the
+// piece's start) and a second one for the aggregate of the block of pieces that ends there; no larger than EstLayout for the same
+// batch, so the resolver's workspace can be handed on as it stands
+struct EstVerifyLayout { uint64_t slice_group, tab, agg, total; };
+inline EstVerifyLayout est_verify_layout(uint64_t n_slices, uint64_t total_chunks) {
+    EstVerifyLayout L;
+    Cursor c;
+    const uint64_t slots = estv::n_slots(total_chunks, estv::kSpan);
+    L.slice_group = c.take(4 * n_slices);
+    L.tab = c.take_unrounded(slots * estv::kTabStride * 2);
+    L.agg = c.take_unrounded(slots * estv::kTabStride * 2);
+    L.total = c.at;
+    return L;
+}
+
 }  // namespace avr

@@ -80,6 +80,9 @@ inline void report_verify_ms(avr_batch *b, const char *what = "compress: GPU ver
     float ms = 0;
     gpu_check(avr_batch_verify_ms(b, &ms));
     fprintf(stderr, "[timing] %-28s %8.1f ms\n", what, double(ms));
+    float est_ms = 0;                                    // key records: the estimator checker behind it, a line of its own where it ran
+    gpu_check(avr_batch_verify_est_ms(b, &est_ms));
+    if (est_ms > 0) fprintf(stderr, "[timing] %-28s %8.1f ms\n", "compress: GPU verify estimators", double(est_ms));
 }
 inline void report_verify_k1_ms(avr_batch *b) { report_verify_ms(b, "decompress: GPU verify (K1)"); }
 
@@ -197,6 +200,10 @@ class compressor {                                       // recode.cpp:1109-1316
             if (status == AVR_SLICE_VERIFY_FAILED) {         // the verifier's (a batch with avr_batch_set_verify): the bytes must not reach a container
                 uint32_t bin = AVR_VERIFY_NONE;
                 gpu_check(avr_batch_get_verify(b, size_t(first_in_batch_) + i, &bin));
+                uint32_t est_bin = AVR_VERIFY_NONE;          // the decoder is content: the estimator checker's finding, if it has one
+                if (bin == AVR_VERIFY_NONE) gpu_check(avr_batch_get_verify_est(b, size_t(first_in_batch_) + i, &est_bin));
+                if (est_bin != AVR_VERIFY_NONE)
+                    throw std::runtime_error("Verify error: resolved estimators do not follow the model (slice " + std::to_string(i) + ", bin " + std::to_string(est_bin) + ")");
                 throw std::runtime_error("Verify error: recoded block does not decode to its bins (slice " + std::to_string(i) + ", bin " + std::to_string(bin) + ")");
             }
             if (status != AVR_SLICE_OK) throw std::runtime_error("avr: slice status " + std::to_string(status));

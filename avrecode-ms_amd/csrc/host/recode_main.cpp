@@ -21,7 +21,9 @@
 // AVR_VERIFY=1 = the K2 batches of compress, roundtrip and test <dir> run with the verifier on (avr_batch_set_verify): every coded
 // slice is decoded back on the device against its records before its bytes go into a container, with or without
 // AVR_DEVICE_ESTIMATORS=1; a slice that does not decode ends the file with "Verify error: ..." (exit status 1, as with the other
-// coder errors).  The .recode bytes are the same either way.  Read here, not by the library.  Off by default.
+// coder errors).  With AVR_DEVICE_ESTIMATORS=1 the estimator checker runs behind it (the resolved records held to the model's update
+// rule): "Verify error: resolved estimators do not follow the model (slice N, bin M)", and under AVR_TIMING=1 a line of its own,
+// "GPU verify estimators".  The .recode bytes are the same either way.  Read here, not by the library.  Off by default.
 // AVR_VERIFY_K1=1 = the same for the other direction: the K1 batches of decompress, roundtrip and test <dir> run with the K1 verifier on
 // (avr_batch_set_verify_k1): every coded slice is decoded back on the device, as the CABAC stream it is, against the codes it was made
 // from before its bytes go into the H.264 file; a slice that does not decode ends the file with "Verify error: coded slice does not

@@ -235,6 +235,28 @@ class DeviceWorkload:
             self.rec_flat.data_ptr(), self.status.data_ptr()))
         return self.rec_flat
 
+    def verify_keys(self):
+        """avr_range_keys_verify_device behind resolve_keys() / resolve_range() on torch's current stream: the resolved records
+        (self.rec_flat) and self.est_out held to the key records by the model's update rule, record by record -- a check that shares
+        nothing with the resolver.  Returns (self.status, first_bad): first_bad an int32 tensor (VERIFY_NONE reads as -1; n_bins: the
+        slice's padding or its group's table), SLICE_VERIFY_FAILED in the status of a slice with a finding.  Enqueues and returns."""
+        import torch
+        if self.kind != KIND_RANGE_KEYS:
+            raise AvrError("verify_keys: not a workload of key records")
+        p = self._chunk_plan()
+        L = lib()
+        if "ws_estv" not in p:
+            n = L.avr_range_keys_verify_workspace_bytes(self.n_slices, self.n_groups, ctypes.byref(p["plan"]))
+            p["ws_estv"] = torch.empty(n + 256, dtype=torch.uint8, device=self.n_bins.device)
+            p["ws_estv_bytes"] = n
+        first_bad = torch.empty(self.n_slices, dtype=torch.int32, device=self.n_bins.device)
+        _check(L.avr_range_keys_verify_device(
+            self.device_index, _stream_ptr(torch), self.key_flat.data_ptr(), self.rec_flat.data_ptr(), self.rec_off.data_ptr(),
+            self.n_bins.data_ptr(), self.n_slices, self.group_first.data_ptr(), self.n_groups,
+            self.est_in.data_ptr() if self.est_in is not None else None, self.est_out.data_ptr(), ctypes.byref(p["plan"]),
+            _aligned(p["ws_estv"]), p["ws_estv_bytes"], self.status.data_ptr(), first_bad.data_ptr()))
+        return self.status, first_bad
+
     def resolve_range(self):
         """The resolved AVR_KIND_RANGE workload on the device: the estimators resolved (resolve_keys) and the records packed into
         tiles, its status carrying what the resolver found malformed.  encode() / encode_chunked() of the result code it."""

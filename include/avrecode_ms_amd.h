@@ -234,10 +234,20 @@ int avr_batch_timings(avr_batch *b, float ms[4]);
  * avr_batch_get_verify gives the index of its first bad bin -- AVR_VERIFY_NONE for every other slice, and for every slice of a run
  * with verify off.  avr_batch_timings()[2] stays the encode alone: the verifier sits between two events of its own, and
  * avr_batch_verify_ms reports them (0 for a run with verify off).  Verification exists for the compress direction only: with verify
- * on, avr_batch_submit of a K1 batch returns AVR_ERR_INVALID. */
+ * on, avr_batch_submit of a K1 batch returns AVR_ERR_INVALID.
+ *   Key records (AVR_KIND_RANGE_KEYS).  The decoder above reads the resolver's output, estimators included: it shows that the bytes
+ * decode with the estimators the resolver chose, not that those are the model's.  So behind it the ESTIMATOR CHECKER
+ * (avr_range_keys_verify_device, below) holds every resolved record and every group's table afterwards to the key records by the
+ * update rule itself, between two events of its own and with answers of its own: avr_batch_get_verify_est gives the slice's first bin
+ * whose estimator does not follow the model (n_bins: its padding, or its group's table afterwards), AVR_VERIFY_NONE for a slice
+ * without a finding, for batches of other kinds and for runs with verify off; avr_batch_verify_est_ms its time (0 where it did not
+ * run; not part of avr_batch_verify_ms).  A slice failed by either check comes back AVR_SLICE_VERIFY_FAILED; avr_batch_get_verify
+ * stays the decoder's answer, AVR_VERIFY_NONE for a slice that only the checker failed. */
 int avr_batch_set_verify(avr_batch *b, int on);
 int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad);
 int avr_batch_verify_ms(avr_batch *b, float *ms);
+int avr_batch_get_verify_est(avr_batch *b, size_t slice, uint32_t *first_bad);
+int avr_batch_verify_est_ms(avr_batch *b, float *ms);
 
 /* Verification of a K1 batch (AVR_KIND_CABAC, AVR_KIND_CABAC8, AVR_KIND_CABAC_CODES) -- the decompress direction, whose product is the
  * user's H.264 file -- switched on by a call of its own: off by default, and then nothing of a run differs.
@@ -616,6 +626,34 @@ int avr_range_resolve_device(int device, void *stream,
                              const uint8_t *est_in, uint8_t *est_out,
                              const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
                              uint16_t *recs_out, int32_t *status);
+
+/* The estimator checker (avrecode-ms_amd/csrc/avr_est_verify.h): are `recs` the K2 records the model's update rule gives for `keys`?
+ * A check of avr_range_resolve_device's output that shares nothing with it.  step(e, b): pos += b, neg += 1 - b, and both halved
+ * rounding up if pos + neg > 0x60.  Over each group's bins in stream order: (1) bit 0 of a record is bit 0 of its well-formed key
+ * record; (2) a key's first bin in the group carries est_in[group][key], {1, 1} without est_in; (3) every other bin carries step of
+ * the RECORDED pair and the bin of the key's previous bin; (4) the records from n_bins to the slice's next multiple of 8 are
+ * AVR_NOP_RANGE; (5) est_out[group][key], where est_out is given, is step of the key's last recorded pair and bin, or the start entry
+ * of a key the group never met.  The arguments are avr_range_resolve_device's, `recs` being its recs_out and est_out read only.
+ *   workspace     avr_range_keys_verify_workspace_bytes(...) bytes, 256-byte aligned:
+ *                 align256(4 n_slices) + 2 ceil(total_chunks / 16) * 4112
+ *                 -- never more than avr_range_resolve_workspace_bytes for the same batch: the resolver's may be handed on as it stands
+ *   status        in/out.  A slice that comes in as AVR_SLICE_BAD_RECORD takes no part, nor (the resolver's rule, relied on) any later
+ *                 slice of its group: first_bad = AVR_VERIFY_NONE, and (5) is not checked for that group.  Every other slice takes
+ *                 part whatever its status; one with a finding goes from AVR_SLICE_OK to AVR_SLICE_VERIFY_FAILED, any other status stays.
+ *   first_bad     per slice: the smallest bin index that violates (1), (2) or (3); n_bins for (4), and for (5) on the group's last
+ *                 slice, unless a smaller index is noted; else AVR_VERIFY_NONE.  The same from run to run.
+ * Nothing else is written; nothing is read between a slice's padded records and the next rec_off.  The call enqueues on `stream` and
+ * returns: it neither waits nor allocates.  A group inside one span of 16 chunks is checked by one wave; a longer one also gets, per
+ * span and key, the estimator its next bin must carry and from those the table at every span's start.  Refused before anything
+ * touches a device (AVR_ERR_INVALID): a null pointer with n_slices > 0, n_groups of 0 or above n_slices, a null plan, recs == keys,
+ * misaligned keys / recs / est_in / est_out / workspace, a workspace below the quoted size, n_slices >= 2^31. */
+size_t avr_range_keys_verify_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan);
+int avr_range_keys_verify_device(int device, void *stream,
+                                 const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, size_t n_slices,
+                                 const uint32_t *group_first, size_t n_groups,
+                                 const uint8_t *est_in /* may be NULL */, const uint8_t *est_out /* may be NULL */,
+                                 const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
+                                 int32_t *status, uint32_t *first_bad);
 
 /* The two stages of K1p on their own.
  *
