@@ -36,12 +36,13 @@ SEL_BYPASS, SEL_TERMINATE = 1024, 1025
 SEL8_BYPASS, SEL8_TERMINATE, MAX_STATES8 = 126, 127, 126      # one-byte records (KIND_CABAC8)
 SLICE_OK, SLICE_ZERO_PROB, SLICE_OVERFLOW, SLICE_BAD_RECORD = 0, 1, 2, 3
 SLICE_VERIFY_FAILED, VERIFY_NONE = 4, 0xFFFFFFFF             # only ever set by a verifier; "no bad bin"
+EXPECT_NONE = 0xFFFFFFFF                                      # expect_len of a slice without an expectation (the restore check)
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_api.cpp"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_restore.hip", "avr_api.cpp"]
 _DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
-                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h"]
+                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h"]
 
 
 class AvrError(RuntimeError):
@@ -180,6 +181,10 @@ SIGNATURES = {
     "avr_cabac_verify_codes_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avr_batch_get_verify": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_batch_expect": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t]),
+    "avr_batch_get_restore": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_batch_restore_ms": (c_int, [c_void_p, POINTER(c_float)]),
+    "avr_restore_check_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avr_batch_verify_ms": (c_int, [c_void_p, POINTER(c_float)]),
     "avr_range_verify_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -526,6 +531,27 @@ class Batch:
         _check(self._L.avr_batch_verify_est_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    def expect(self, i: int, payload):
+        """K1 batches: slice i (already added) is expected to restore `payload` (bytes) -- its coded bytes through drop_stop_byte and
+        tail_patch with the payload's own length parity and last byte.  A run carries the restore check iff a slice has an
+        expectation; reset() drops them.  A slice that does not restore its payload comes back with SLICE_VERIFY_FAILED."""
+        import numpy as np
+        p = np.frombuffer(bytes(payload), dtype=np.uint8)
+        _check(self._L.avr_batch_expect(self._h, i, p.ctypes.data if p.size else None, p.size))
+
+    def get_restore(self, i: int) -> int:
+        """Index of the first byte at which slice i's restored payload differs from its expectation (the shorter length where one is the
+        beginning of the other), or VERIFY_NONE -- also for a slice without an expectation."""
+        v = c_uint32()
+        _check(self._L.avr_batch_get_restore(self._h, i, ctypes.byref(v)))
+        return v.value
+
+    def restore_ms(self) -> float:
+        """Milliseconds of the restore check in the last run (0 where it did not run); no part of timings() or verify_ms()."""
+        ms = c_float()
+        _check(self._L.avr_batch_restore_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
 
 class MultiBatch:
     """One batch sharded over several GPUs (avr_multi_*): LPT by bin count, a host thread and an avr_batch per device."""
@@ -598,6 +624,6 @@ class MultiBatch:
 from .device import DeviceWorkload, encode_tiles, plan_tiles, synth_config  # noqa: E402  (torch-backed helpers)
 
 __all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS",
-           "SEL_BYPASS", "SEL_TERMINATE", "SLICE_VERIFY_FAILED", "VERIFY_NONE",
+           "SEL_BYPASS", "SEL_TERMINATE", "SLICE_VERIFY_FAILED", "VERIFY_NONE", "EXPECT_NONE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
            "make_cabac_records", "make_range_records", "plan_tiles", "synth_config", "tail_patch"]

@@ -180,6 +180,19 @@ struct avr_batch {
     float verify_est_ms = 0;
     DevBuf<uint32_t> d_first_bad_est;
     PinBuf<uint32_t> h_first_bad_est;
+
+    // the restore check of a K1 run (avr_batch_expect): a batch without expectations touches none of this
+    std::vector<uint64_t> expect_off;       // per slice: where its expectation lies in h_expect (bytes, multiples of 8)
+    std::vector<uint32_t> expect_len;       // per slice: its length, AVR_EXPECT_NONE for a slice without one
+    size_t n_expect = 0, expect_used = 0;   // slices that have one; bytes of h_expect in use (a multiple of 8)
+    PinBuf<uint8_t> h_expect;               // the expectations as they came, each padded to 8
+    bool restored = false;                  // the run in flight / the last run had the check
+    hipEvent_t rev[2] = {};                 // end of what ran before the check (the encode, or the K1 verifier), end of the check (created with the first expectation)
+    float restore_ms = 0;
+    DevBuf<uint8_t> d_expect;
+    DevBuf<uint64_t> d_expect_off;
+    DevBuf<uint32_t> d_expect_len, d_first_diff;
+    PinBuf<uint32_t> h_first_diff;
 };
 
 // One plan array to the device through the batch's pinned arena: the copy is asynchronous for real (a copy from
@@ -320,6 +333,9 @@ void avr_batch_destroy(avr_batch *b) {
     b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release();
     b->d_est_in.release(); b->d_est_out.release(); b->d_est_ws.release();
     b->d_first_bad.release(); b->h_first_bad.release();
+    b->h_expect.release(); b->d_expect.release(); b->d_expect_off.release(); b->d_expect_len.release();
+    b->d_first_diff.release(); b->h_first_diff.release();
+    for (auto &e : b->rev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->vev) if (e) (void)hipEventDestroy(e);
     for (auto &e : b->eev) if (e) (void)hipEventDestroy(e);
@@ -335,6 +351,7 @@ int avr_batch_reset(avr_batch *b) {
     b->rec_off.assign(1, 0);
     b->n_bins.clear();
     b->dense_off.clear();
+    b->expect_off.clear(); b->expect_len.clear(); b->n_expect = 0; b->expect_used = 0;    // the expectations go with the slices
     return AVR_OK;
 }
 
@@ -478,6 +495,11 @@ int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n) {
 
 static int enqueue_lengths(avr_batch *b, uint32_t n32);
 static int enqueue_verify_k1(avr_batch *b, uint32_t n32, int form, const void *recs, const uint64_t *off, const uint32_t *order, bool again = false);
+static int reserve_restore(avr_batch *b, size_t n);
+static int stage_restore(avr_batch *b, size_t n);
+static int enqueue_restore(avr_batch *b, uint32_t n32);
+// what the expectations' offsets and lengths take of the arena
+static size_t staged_restore(const avr_batch *b, size_t n) { return b->n_expect ? staged<uint64_t>(n) + staged<uint32_t>(n) : 0; }
 
 // A batch of resolved codes: H2D of one byte per bin, K1p phases B-D (or the one-lane-per-slice coder), lengths back.
 static int submit_codes(avr_batch *b, uint32_t n32) {
@@ -490,7 +512,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
         plan_tiles(b->n_bins, order, tile_off);                  // longest first: the lanes of a wave finish together
     }
     const uint64_t total_codes = b->rec_off.back(), total_out = b->hp.out_off.back();
-    const size_t arena = staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) * 2 + staged_plan(b->hp);       // rec_off, out_off, n_bins, order; the plan
+    const size_t arena = staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) * 2 + staged_plan(b->hp) + staged_restore(b, n);    // rec_off, out_off, n_bins, order; the plan
     int rc;
     if ((rc = b->d_recs.reserve((total_codes + 64) / 2 + 1)) || (rc = b->d_res_off.reserve(n + 1)) ||
         (rc = b->d_out_off.reserve(n + 1)) || (rc = b->d_dense_off.reserve(n + 1)) || (rc = b->d_n_bins.reserve(n)) ||
@@ -501,6 +523,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
     b->verified_est = b->verified && b->keys;
     if (b->verified_est && ((rc = b->d_first_bad_est.reserve(n)) || (rc = b->h_first_bad_est.reserve(n)))) return rc;
+    if ((rc = reserve_restore(b, n))) return rc;
     hipStream_t s = b->stream;
     b->plan_used = 0;
     b->hint_used = 0;
@@ -512,6 +535,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     AVR_STAGE(b->d_out_off.p, b->hp.out_off.data(), n + 1);
     AVR_STAGE(b->d_n_bins.p, b->n_bins.data(), n);
     if (!chunked) AVR_STAGE(b->d_order.p, order.data(), n);
+    if (b->restored && (rc = stage_restore(b, n))) return rc;
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipEventRecord(b->ev[2], s));
@@ -525,6 +549,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     }
     b->last_path = chunked;
     if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kCodes, d_codes, b->d_res_off.p, chunked ? nullptr : b->d_order.p))) return rc;
+    if (b->restored && (rc = enqueue_restore(b, n32))) return rc;
     return enqueue_lengths(b, n32);
 }
 
@@ -639,12 +664,13 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         return rc;
     // rec_off, out_off, n_bins; tile_off, order; group_first; the plan's arrays
     if ((rc = b->h_plan.reserve(staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) + (chunked ? 0 : staged<uint64_t>(n_tiles + 1) + staged<uint32_t>(n)) +
-                                (b->keys ? staged<uint32_t>(b->group_first.size() + 1) : 0) + staged_plan(b->hp)))) return rc;
+                                (b->keys ? staged<uint32_t>(b->group_first.size() + 1) : 0) + staged_plan(b->hp) + staged_restore(b, n)))) return rc;
     if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
     b->verified = cabac ? b->verify_k1 : b->verify;
     if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
     b->verified_est = b->verified && b->keys;
     if (b->verified_est && ((rc = b->d_first_bad_est.reserve(n)) || (rc = b->h_first_bad_est.reserve(n)))) return rc;
+    if ((rc = reserve_restore(b, n))) return rc;
 
     hipStream_t s = b->stream;
     b->plan_used = 0;
@@ -666,6 +692,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         AVR_STAGE(b->d_order.p, order.data(), n);
     }
     if (cabac && ns) AVR_HIP(hipMemcpyAsync(b->d_states.p, b->h_states.p, n * ns, hipMemcpyHostToDevice, s));
+    if (b->restored && (rc = stage_restore(b, n))) return rc;
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
     // Both K1 paths renumber a two-byte batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
@@ -720,7 +747,39 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         if (rc) return rc;
         if (b->verified_est && (rc = enqueue_verify_est(b, n32))) return rc;
     }
+    if (b->restored && (rc = enqueue_restore(b, n32))) return rc;    // (K1 only: a K2 batch takes no expectations)
     return enqueue_lengths(b, n32);
+}
+
+// The restore check of a K1 run.  reserve_restore: decides whether the run has it (iff a slice has an expectation) and makes room;
+// stage_restore: the expectations with their offsets and lengths on their way to the device, among the run's other H2D copies;
+// enqueue_restore: the check behind the encode of whichever path ran -- behind the K1 verifier where that is on -- between its two events.
+static int reserve_restore(avr_batch *b, size_t n) {
+    b->restored = b->n_expect > 0;
+    if (!b->restored) return AVR_OK;
+    b->expect_off.resize(n, 0);
+    b->expect_len.resize(n, AVR_EXPECT_NONE);
+    int rc;
+    if ((rc = b->d_expect.reserve(b->expect_used + 8)) || (rc = b->d_expect_off.reserve(n)) || (rc = b->d_expect_len.reserve(n)) ||
+        (rc = b->d_first_diff.reserve(n)) || (rc = b->h_first_diff.reserve(n)))
+        return rc;
+    return AVR_OK;
+}
+
+static int stage_restore(avr_batch *b, size_t n) {
+    if (b->expect_used) AVR_HIP(hipMemcpyAsync(b->d_expect.p, b->h_expect.p, b->expect_used, hipMemcpyHostToDevice, b->stream));
+    AVR_STAGE(b->d_expect_off.p, b->expect_off.data(), n);
+    AVR_STAGE(b->d_expect_len.p, b->expect_len.data(), n);
+    return AVR_OK;
+}
+
+static int enqueue_restore(avr_batch *b, uint32_t n32) {
+    hipStream_t s = b->stream;
+    AVR_HIP(hipEventRecord(b->rev[0], s));
+    AVR_HIP(avr::launch_restore_check(s, b->d_out.p, b->d_out_off.p, b->d_out_len.p, n32, b->d_expect.p, b->d_expect_off.p, b->d_expect_len.p,
+                                      b->d_status.p, b->d_first_diff.p));
+    AVR_HIP(hipEventRecord(b->rev[1], s));
+    return AVR_OK;
 }
 
 // lengths, statuses and final states on their way to the host behind the kernels
@@ -734,6 +793,7 @@ static int enqueue_lengths(avr_batch *b, uint32_t n32) {
     if (with_states) AVR_HIP(hipMemcpyAsync(b->h_final.p, b->d_final.p, n * ns, hipMemcpyDeviceToHost, s));
     if (b->verified) AVR_HIP(hipMemcpyAsync(b->h_first_bad.p, b->d_first_bad.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (b->verified_est) AVR_HIP(hipMemcpyAsync(b->h_first_bad_est.p, b->d_first_bad_est.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (b->restored) AVR_HIP(hipMemcpyAsync(b->h_first_diff.p, b->d_first_diff.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return AVR_OK;
 }
 
@@ -748,7 +808,7 @@ int avr_batch_submit(avr_batch *b) {
         return fail(AVR_ERR_INVALID, "verification exists for the compress direction only: not for a K1 batch");
     if (b->verify_k1 && b->kind == AVR_KIND_RANGE)
         return fail(AVR_ERR_INVALID, "K1 verification exists for the decompress direction only: not for a K2 batch");
-    b->verified = b->verified_est = false;
+    b->verified = b->verified_est = b->restored = false;
     if (n == 0) { b->in_flight = true; return AVR_OK; }
     const bool use_hint = b->dense_hint > 0 && !avr::no_hint();
     if (int rc = submit_impl(b, use_hint)) { (void)hipStreamSynchronize(b->stream); return rc; }
@@ -769,7 +829,7 @@ int avr_batch_wait(avr_batch *b) {
     int rc;
     AVR_HIP(hipStreamSynchronize(s));
     b->info[0] = uint32_t(b->last_path); b->info[1] = b->info[2] = b->info[3] = 0;
-    float verify_before = 0;                                     // of the verifier in front of K1p's second pass, where there is one
+    float verify_before = 0, restore_before = 0;                 // of the verifier and the restore check in front of K1p's second pass, where there is one
     if (b->kind == AVR_KIND_CABAC) {
         // The run was sized by a guess of the context count.  The one-lane-per-slice kernel is exact whatever the
         // guess; the intra-slice parallel kernels only if the batch needs no more rows than guessed: else once more,
@@ -781,11 +841,13 @@ int avr_batch_wait(avr_batch *b) {
             b->info[3] = 1;
         }
         if (b->last_path == 1 && b->h_ndense.p[1]) {             // slices with a context the sampled census missed: their second pass
-            if (b->verified) {
+            if (b->verified || b->restored) {
                 // The verifier has run in front of this pass, and the pass treats a slice it marked AVR_SLICE_VERIFY_FAILED like one with a bad
                 // record (length 0).  Such a slice goes in as AVR_SLICE_OK -- finished, so the pass leaves it alone -- and the verifier behind
                 // the pass, which decodes every slice again, fails it again at the same bin.  (h_status is the device's, behind a synchronise.)
-                (void)hipEventElapsedTime(&verify_before, b->vev[1], b->vev[2]);
+                // The same holds for the restore check and its findings.
+                if (b->verified) (void)hipEventElapsedTime(&verify_before, b->vev[1], b->vev[2]);
+                if (b->restored) (void)hipEventElapsedTime(&restore_before, b->rev[0], b->rev[1]);
                 bool any = false;
                 for (size_t i = 0; i < n; i++)
                     if (b->h_status.p[i] == AVR_SLICE_VERIFY_FAILED) { b->h_status.p[i] = AVR_SLICE_OK; any = true; }
@@ -795,6 +857,7 @@ int avr_batch_wait(avr_batch *b) {
                                           avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
             // the verifier skipped the slices of this pass (their status was not AVR_SLICE_OK yet): once more behind it
             if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr, true))) return rc;
+            if (b->restored && (rc = enqueue_restore(b, n32))) return rc;        // ... and the restore check, for the same reason
             if ((rc = enqueue_lengths(b, n32))) return rc;
             AVR_HIP(hipStreamSynchronize(s));
             b->info[3] |= 2;
@@ -823,8 +886,17 @@ int avr_batch_wait(avr_batch *b) {
         // Behind K1p's second pass (rare) vev[0] was recorded again: the span from ev[2] then also holds the first verifier, taken off
         // here, and what lay between the two runs -- the host's wait, the status and length copies -- which stays in: on that path
         // ms[2] is an upper bound of the encode, not the encode alone.
-        b->ms[2] -= verify_before;
+        b->ms[2] -= verify_before + restore_before;
         b->verify_ms += verify_before;
+    }
+    b->restore_ms = 0;
+    if (b->restored) {                                           // without a verifier in front of it the check's first event ends the encode's slot
+        if (!b->verified) {
+            (void)hipEventElapsedTime(&b->ms[2], b->ev[2], b->rev[0]);
+            b->ms[2] -= restore_before;                          // (behind K1p's second pass: as above, an upper bound of the encode)
+        }
+        (void)hipEventElapsedTime(&b->restore_ms, b->rev[0], b->rev[1]);
+        b->restore_ms += restore_before;
     }
     b->verify_est_ms = 0;
     if (b->verified_est) (void)hipEventElapsedTime(&b->verify_est_ms, b->eev[0], b->eev[1]);
@@ -935,6 +1007,53 @@ int avr_batch_get_verify_est(avr_batch *b, size_t slice, uint32_t *first_bad) {
 int avr_batch_verify_est_ms(avr_batch *b, float *ms) {
     if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
     *ms = b->verify_est_ms;
+    return AVR_OK;
+}
+
+int avr_batch_expect(avr_batch *b, size_t slice, const uint8_t *bytes, size_t len) {
+    if (!b) return fail(AVR_ERR_INVALID, "null batch");
+    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
+    if (b->kind == AVR_KIND_RANGE) return fail(AVR_ERR_INVALID, "the restore check exists for K1 batches only: not for a K2 batch");
+    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu has not been added", slice);
+    if (len >= 0xffffffffull) return fail(AVR_ERR_INVALID, "expectation too long");
+    if (!bytes && len) return fail(AVR_ERR_INVALID, "null bytes");
+    if (slice < b->expect_len.size() && b->expect_len[slice] != AVR_EXPECT_NONE)
+        return fail(AVR_ERR_INVALID, "slice %zu has an expectation already", slice);
+    if (!b->rev[0]) {
+        if (int rc = select_device(b->device)) return rc;
+        for (auto &e : b->rev) AVR_HIP(hipEventCreate(&e));
+    }
+    const size_t padded = (len + 7) & ~size_t(7), need = b->expect_used + padded;
+    if (need > b->h_expect.cap) {                                // grown with what it holds (PinBuf::reserve keeps nothing)
+        PinBuf<uint8_t> grown;
+        if (int rc = grown.reserve(std::max(need, 2 * b->h_expect.cap))) return rc;
+        if (b->expect_used) memcpy(grown.p, b->h_expect.p, b->expect_used);
+        b->h_expect.release();
+        b->h_expect = grown;
+    }
+    uint8_t *dst = b->h_expect.p + b->expect_used;
+    if (len) memcpy(dst, bytes, len);
+    memset(dst + len, 0, padded - len);
+    b->expect_off.resize(b->n_bins.size(), 0);
+    b->expect_len.resize(b->n_bins.size(), AVR_EXPECT_NONE);
+    b->expect_off[slice] = b->expect_used;
+    b->expect_len[slice] = uint32_t(len);
+    b->expect_used = need;
+    b->n_expect++;
+    return AVR_OK;
+}
+
+int avr_batch_get_restore(avr_batch *b, size_t slice, uint32_t *first_diff) {
+    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
+    if (first_diff) *first_diff = b->restored ? b->h_first_diff.p[slice] : AVR_VERIFY_NONE;
+    return AVR_OK;
+}
+
+int avr_batch_restore_ms(avr_batch *b, float *ms) {
+    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
+    *ms = b->restore_ms;
     return AVR_OK;
 }
 
@@ -1560,6 +1679,20 @@ int avr_cabac_verify_codes_device(int device, void *stream, const uint8_t *codes
                                   const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
     return cabac_verify_device(avr::cabac_verify::kCodes, device, stream, codes, res_off, n_bins, order, n_slices, nullptr, 0,
                                out, out_off, out_len, nullptr, status, first_bad, true);
+}
+
+// The restore check (avr_restore.hip): the checks that need no device, then the launch.
+int avr_restore_check_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, size_t n_slices,
+                             const uint8_t *expect, const uint64_t *expect_off, const uint32_t *expect_len, int32_t *status,
+                             uint32_t *first_diff) {
+    if (n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_slices %zu out of range", n_slices);
+    if (n_slices && (!out || !out_off || !out_len || !expect || !expect_off || !expect_len || !status || !first_diff))
+        return fail(AVR_ERR_INVALID, "null device pointer");
+    if (reinterpret_cast<uintptr_t>(expect) & 7) return fail(AVR_ERR_INVALID, "expect is not 8-byte aligned");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_restore_check(static_cast<hipStream_t>(stream), out, out_off, out_len, uint32_t(n_slices), expect, expect_off,
+                                      expect_len, status, first_diff));
+    return AVR_OK;
 }
 
 // ------------------------------------------------------------------ dense context ids

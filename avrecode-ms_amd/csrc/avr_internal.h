@@ -142,6 +142,11 @@ hipError_t launch_cabac_verify(int form, hipStream_t s, const void *recs, const 
                                const uint32_t *order, uint32_t n_slices, const uint8_t *init_states, uint32_t n_states,
                                const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
                                int32_t *status, uint32_t *first_bad);
+// the restore check (avr_restore.hip): every slice that is AVR_SLICE_OK or AVR_SLICE_VERIFY_FAILED and has an expectation, its coded
+// bytes through the decompressor's epilogue rule against the expected payload, a wave per slice; writes status and first_diff only
+hipError_t launch_restore_check(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, uint32_t n_slices,
+                                const uint8_t *expect, const uint64_t *expect_off, const uint32_t *expect_len, int32_t *status,
+                                uint32_t *first_diff);
 #ifdef AVR_TEST_HOOKS
 hipError_t launch_verify_flip(hipStream_t s, uint8_t *out, const uint64_t *out_off, uint32_t slice);
 #endif

@@ -85,6 +85,13 @@ inline void report_verify_ms(avr_batch *b, const char *what = "compress: GPU ver
     if (est_ms > 0) fprintf(stderr, "[timing] %-28s %8.1f ms\n", "compress: GPU verify estimators", double(est_ms));
 }
 inline void report_verify_k1_ms(avr_batch *b) { report_verify_ms(b, "decompress: GPU verify (K1)"); }
+// AVR_TIMING=1: the restore check's own share of the batch it ran in (device time, between its events)
+inline void report_restore_ms(avr_batch *b) {
+    if (!getenv("AVR_TIMING")) return;
+    float ms = 0;
+    gpu_check(avr_batch_restore_ms(b, &ms));
+    fprintf(stderr, "[timing] %-28s %8.1f ms\n", "compress: restore check kernel", double(ms));
+}
 
 struct batch_holder {                                    // RAII around the C ABI's avr_batch
     avr_batch *b;
@@ -160,6 +167,7 @@ class compressor {                                       // recode.cpp:1109-1316
     std::string run(stream_decoder *d) {                 // :1122-1132
         prepare(d);
         { phase_timer t("compress: GPU batch (K2)"); code_pending(); }
+        if (restore_check_) { phase_timer t("compress: GPU restore check (K1)"); check_restore_pending(); }
         return finish();
     }
     // run() in three steps, so that a caller with several files (recode test <dir>, test.cpp:113-148) can code the slices of all of
@@ -179,6 +187,45 @@ class compressor {                                       // recode.cpp:1109-1316
     // The file's own batch (run()) with the verifier behind the encode: every coded slice decoded back on the device against its
     // records (avr_batch_set_verify).  A caller with a batch of its own (add_to / take_from) sets that on its batch.
     void set_verify(bool on) { verify_ = on; }
+    // The restore check: will decompress write back these bytes?  Before prepare().  The compressor's own CABAC decoder sees *state
+    // before every bin, so it also writes the resolved code AVR_CODE_CONTEXT(*state, bin) of each -- the byte decompress_recorder
+    // writes on the way back, in bitstream order (the order of the hook calls, not the recorder's queued order), whatever the model,
+    // the residual hooks and the place the estimators are resolved -- and keeps where the slice's payload lies in the file.  run()
+    // then codes the slices once more in a K1 batch of its own, from those codes, with the payloads as expectations
+    // (avr_batch_expect): K1, finish and the tail patch with the container's two fields against the real payload.  A caller with
+    // batches of its own uses add_restore_to / take_restore_from, beside add_to / take_from.
+    void set_restore_check(bool on) { restore_check_ = on; }
+    struct restore_slice { std::vector<uint8_t> codes; size_t payload_at, payload_size; };   // the payload: original[payload_at .. + payload_size)
+    std::vector<restore_slice> &restore_slices() { return restore_pending_; }
+    const std::string &original() const { return original_; }
+    size_t restore_bins() const { size_t bins = 0; for (auto &p : restore_pending_) bins += p.codes.size(); return bins; }
+    void add_restore_to(avr_batch *b) {                  // into a K1 batch of resolved codes; consecutive indices, the first one kept
+        first_in_restore_batch_ = -1;
+        for (auto &p : restore_pending_) {
+            const int idx = avr_batch_add_slice_codes(b, p.codes.data(), p.codes.size());
+            gpu_check(idx);
+            gpu_check(avr_batch_expect(b, size_t(idx), reinterpret_cast<const uint8_t *>(original_.data()) + p.payload_at, p.payload_size));
+            if (first_in_restore_batch_ < 0) first_in_restore_batch_ = idx;
+            std::vector<uint8_t>().swap(p.codes);        // the batch has its copy
+        }
+    }
+    void take_restore_from(avr_batch *b) {               // nothing is taken but the answers: the coded bytes were the check's input
+        for (size_t i = 0; i < restore_pending_.size(); i++) {
+            int status;
+            gpu_check(avr_batch_get(b, size_t(first_in_restore_batch_) + i, nullptr, nullptr, &status));
+            if (status == AVR_SLICE_VERIFY_FAILED) {
+                uint32_t at = AVR_VERIFY_NONE;
+                gpu_check(avr_batch_get_restore(b, size_t(first_in_restore_batch_) + i, &at));
+                if (at == AVR_VERIFY_NONE) {             // the K1 verifier's, in a batch that had it on
+                    gpu_check(avr_batch_get_verify(b, size_t(first_in_restore_batch_) + i, &at));
+                    throw std::runtime_error("Verify error: coded slice does not decode to its bins (slice " + std::to_string(i) + ", bin " + std::to_string(at) + ")");
+                }
+                throw std::runtime_error("Verify error: coded slice does not restore its payload (slice " + std::to_string(i) + ", byte " + std::to_string(at) + ")");
+            }
+            if (status != AVR_SLICE_OK) throw std::runtime_error("avr: slice status " + std::to_string(status));
+        }
+        restore_pending_.clear();
+    }
     size_t pending_slices() const { return pending_.size(); }
     size_t pending_bins() const { size_t bins = 0; for (auto &p : pending_) bins += p.recs.size(); return bins; }
     void add_to(avr_batch *b) {                          // the slice indices the batch hands out are consecutive: the first one is kept
@@ -236,21 +283,34 @@ class compressor {                                       // recode.cpp:1109-1316
             c->out_.block[block_].has_size = true;       // :1154
             c->out_.block[block_].size = size;
             recorder_.reset(new compress_recorder(&c->model_, c->device_estimators_));   // :1161-1163
+            if (c->restore_check_) {                     // the payload was just found in the file: it ends where the next search begins
+                restore_ = true;
+                payload_at_ = size_t(c->prev_coded_block_end_) - size_t(size);
+                payload_size_ = size_t(size);
+            }
         }
-        ~cabac_decoder() { if (recorder_) c_->pending_.push_back({block_, recorder_->records()}); }
+        ~cabac_decoder() {
+            if (!recorder_) return;
+            c_->pending_.push_back({block_, recorder_->records()});
+            if (restore_) c_->restore_pending_.push_back({std::move(codes_), payload_at_, payload_size_});
+        }
         bool hooked() const { return block_ >= 0; }
         int get(uint8_t *state) {                        // :1182-1186
+            const uint8_t before = *state;               // (the decoder moves it on)
             const int symbol = decoder_.get(state);      // ::ff_get_cabac on the private context copy
+            if (restore_) codes_.push_back(uint8_t(AVR_CODE_CONTEXT(before, symbol)));
             recorder_->execute_symbol(symbol, c_->contexts_.id_of(state));   // context identity is the address (recode.cpp:325)
             return symbol;
         }
         int get_bypass() {                               // :1188-1192
             const int symbol = decoder_.get_bypass();
+            if (restore_) codes_.push_back(uint8_t(AVR_CODE_BYPASS(symbol)));
             recorder_->execute_symbol(symbol, kKeyBypass);
             return symbol;
         }
         int get_terminate() {                            // :1194-1199
             const int symbol = decoder_.get_terminate() != 0;
+            if (restore_) codes_.push_back(uint8_t(AVR_CODE_TERMINATE(symbol)));
             recorder_->execute_symbol(symbol, kKeyTerminate);
             return symbol;
         }
@@ -264,6 +324,9 @@ class compressor {                                       // recode.cpp:1109-1316
         cabac_bin_decoder decoder_;
         int block_ = -1;
         std::unique_ptr<compress_recorder> recorder_;
+        bool restore_ = false;                           // the restore check is on: the resolved codes and the payload's place are kept
+        std::vector<uint8_t> codes_;
+        size_t payload_at_ = 0, payload_size_ = 0;
     };
 
     h264_model *get_model() { return &model_; }          // :1276-1278
@@ -320,9 +383,19 @@ class compressor {                                       // recode.cpp:1109-1316
         take_from(bh.b);
     }
 
+    void check_restore_pending() {                       // one K1 batch of the file's own, from the codes, the payloads as expectations
+        if (restore_pending_.empty()) return;
+        batch_holder bh(device_, restore_pending_.size(), restore_bins() + 16 * restore_pending_.size() + 64);
+        add_restore_to(bh.b);
+        gpu_check(avr_batch_run(bh.b));
+        report_restore_ms(bh.b);
+        take_restore_from(bh.b);
+    }
+
     struct pending { int block; std::vector<uint16_t> recs; };
-    int first_in_batch_ = -1;
-    bool device_estimators_ = false, verify_ = false;
+    int first_in_batch_ = -1, first_in_restore_batch_ = -1;
+    bool device_estimators_ = false, verify_ = false, restore_check_ = false;
+    std::vector<restore_slice> restore_pending_;
     std::string original_;
     int device_;
     int read_offset_ = 0, prev_coded_block_end_ = 0;

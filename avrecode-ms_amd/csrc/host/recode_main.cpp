@@ -28,6 +28,13 @@
 // (avr_batch_set_verify_k1): every coded slice is decoded back on the device, as the CABAC stream it is, against the codes it was made
 // from before its bytes go into the H.264 file; a slice that does not decode ends the file with "Verify error: coded slice does not
 // decode to its bins (slice N, bin M)" (exit status 1).  The file's bytes are the same either way.  Off by default.
+// AVR_VERIFY_RESTORE=1 = compress, roundtrip and test <dir> ask at compress time whether decompress will write back the payload of
+// every coded slice: the compressor also keeps the resolved code of every bin and the slices are coded once more, by K1 in a batch of
+// their own (in test <dir>: one restore batch per window), with the payloads as expectations (avr_batch_expect) -- K1, finish and the
+// tail patch with the container's two fields against the real bytes.  A slice that does not restore ends the file with "Verify error:
+// coded slice does not restore its payload (slice N, byte M)" (exit status 1, nothing written for that file).  With or without
+// AVR_VERIFY, AVR_DEVICE_ESTIMATORS and AVR_MODEL_HOOKS; the .recode bytes are the same either way; under AVR_TIMING=1 the lines
+// "compress: GPU restore check (K1)" and "compress: restore check kernel".  Read here, not by the library.  Off by default.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +70,7 @@ bool device_estimators() {
 }
 
 bool verify() { static const bool on = [] { const char *d = getenv("AVR_VERIFY"); return d && atoi(d) != 0; }(); return on; }
+bool verify_restore() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_RESTORE"); return d && atoi(d) != 0; }(); return on; }
 bool verify_k1() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_K1"); return d && atoi(d) != 0; }(); return on; }
 
 std::string slurp(const std::string &path) {
@@ -77,6 +85,7 @@ std::string compress_bytes(const std::string &original) {            // compress
     host::compressor c(original, device());
     c.set_device_estimators(device_estimators());
     c.set_verify(verify());
+    c.set_restore_check(verify_restore());
     h264::h264_stream_decoder d;
     d.residual_hooks = model_hooks();
     return c.run(&d);
@@ -273,9 +282,9 @@ void perf_test_driver(const std::string &directory_path) {
     const size_t window = std::max<long>(1, w ? atol(w) : 64);
     const unsigned hw = std::thread::hardware_concurrency();
     const unsigned threads = std::min<unsigned>(hw ? hw : 4, 32);
-    shared_batch batch_in, batch_out;
+    shared_batch batch_in, batch_out, batch_restore;
     const bool on_device = device_estimators();                      // read here, once, not in the files' threads
-    const bool verify_on = verify(), verify_k1_on = verify_k1();
+    const bool verify_on = verify(), verify_k1_on = verify_k1(), restore_on = verify_restore();
     for (size_t base = 0; base < files.size(); base += window) {
         const size_t n = std::min(window, files.size() - base);
         std::vector<file_job> jobs(n);
@@ -292,6 +301,7 @@ void perf_test_driver(const std::string &directory_path) {
                 j.log_text = captured.str();
                 j.c.reset(new host::compressor(j.original, device()));
                 j.c->set_device_estimators(on_device);
+                j.c->set_restore_check(restore_on);
                 h264::h264_stream_decoder dec;
                 dec.residual_hooks = model_hooks();
                 dec.dry_run_threads = 1;                             // the cores are taken by the files
@@ -314,6 +324,19 @@ void perf_test_driver(const std::string &directory_path) {
                 for (file_job &j : jobs) if (!j.failed) { try { j.c->take_from(b); } catch (const std::exception &e) { log_exception(j, e); } }
                 const double ms = ms_since(t0);
                 for (file_job &j : jobs) j.c_gpu_ms = bins ? ms * double(j.c_bins) / double(bins) : 0;
+            }
+        } catch (const std::exception &e) { for (file_job &j : jobs) if (!j.failed) log_exception(j, e); }
+        // ---- the restore check: the window's slices once more through K1, from the compressors' codes, against their payloads
+        if (restore_on) try {
+            size_t slices = 0, bins = 0;
+            for (file_job &j : jobs) if (!j.failed) { slices += j.c->restore_slices().size(); bins += j.c->restore_bins(); }
+            if (slices) {
+                host::phase_timer t("compress: GPU restore check (K1)");
+                avr_batch *b = batch_restore.get(slices, bins + 16 * slices + 64);
+                for (file_job &j : jobs) if (!j.failed) j.c->add_restore_to(b);
+                host::gpu_check(avr_batch_run(b));
+                host::report_restore_ms(b);
+                for (file_job &j : jobs) if (!j.failed) { try { j.c->take_restore_from(b); } catch (const std::exception &e) { log_exception(j, e); } }
             }
         } catch (const std::exception &e) { for (file_job &j : jobs) if (!j.failed) log_exception(j, e); }
         // ---- the container's bytes, then decompress, host side (K3 + parse): one file per thread again

@@ -734,6 +734,36 @@ class DeviceWorkload:
                         init, self.n_states, *tail, final, self.status.data_ptr(), first_bad.data_ptr()))
         return first_bad
 
+    def restore_check(self, expect_list):
+        """K1 only, behind any encode call of the workload on torch's current stream: the restore check (avr_restore_check_device) of
+        every slice against expect_list[i] -- the payload (bytes) slice i is to restore through drop_stop_byte and tail_patch with the
+        payload's own parity and last byte, or None for a slice without an expectation.  Returns (status, first_diff): self.status,
+        where a slice with a finding has become SLICE_VERIFY_FAILED, and the first differing byte of each slice (int32; VERIFY_NONE
+        reads as -1).  Enqueues and returns."""
+        import numpy as np
+        import torch
+        if self.kind not in (KIND_CABAC, KIND_CABAC8):
+            raise AvrError("restore_check: the restore check exists for K1 (KIND_CABAC, KIND_CABAC8) workloads only")
+        if len(expect_list) != self.n_slices:
+            raise AvrError(f"restore_check: {len(expect_list)} expectations for {self.n_slices} slices")
+        off, lens, at = np.zeros(self.n_slices, np.int64), np.full(self.n_slices, -1, np.int32), 0     # -1: AVR_EXPECT_NONE
+        for i, e in enumerate(expect_list):
+            if e is not None:
+                off[i], lens[i] = at, len(e)
+                at += (len(e) + 7) & ~7
+        flat = np.zeros(at + 8, np.uint8)
+        for i, e in enumerate(expect_list):
+            if e:
+                flat[off[i]:off[i] + len(e)] = np.frombuffer(bytes(e), np.uint8)
+        dev = self.n_bins.device
+        expect, expect_off, expect_len = (torch.from_numpy(a).to(dev) for a in (flat, off, lens))
+        first_diff = torch.empty(self.n_slices, dtype=torch.int32, device=dev)
+        _check(lib().avr_restore_check_device(
+            self.device_index, _stream_ptr(torch), self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.n_slices,
+            expect.data_ptr(), expect_off.data_ptr(), expect_len.data_ptr(), self.status.data_ptr(), first_diff.data_ptr()))
+        self._restore_expect = (expect, expect_off, expect_len)          # the kernel reads them after this call returns
+        return self.status, first_diff
+
     # ---- accounting (DESIGN.md "algorithmic bytes")
     def output_bytes(self) -> int:
         import torch

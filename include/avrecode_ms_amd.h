@@ -98,6 +98,10 @@ extern "C" {
  * and length stay retrievable as they are. */
 #define AVR_SLICE_VERIFY_FAILED 4           /* only ever set by the verifier */
 #define AVR_VERIFY_NONE 0xFFFFFFFFu
+/* The restore check (avr_restore_check_device, avr_batch_expect) sets AVR_SLICE_VERIFY_FAILED too, on a slice that was AVR_SLICE_OK
+ * and whose coded bytes do not restore the payload the caller expects of it.  AVR_EXPECT_NONE as a slice's expect_len: this slice has
+ * no expectation, the check skips it. */
+#define AVR_EXPECT_NONE 0xFFFFFFFFu   /* expect_len: this slice has no expectation */
 
 #define AVR_SEL_BYPASS     1024
 #define AVR_SEL_TERMINATE  1025
@@ -262,6 +266,25 @@ int avr_batch_verify_est_ms(avr_batch *b, float *ms);
  * and the copies between the two runs -- an upper bound of the encode).  K1 verification exists for the decompress direction only: with it on, avr_batch_submit
  * of a K2 batch returns AVR_ERR_INVALID.  avr_batch_set_verify and its rule for K1 batches are unchanged. */
 int avr_batch_set_verify_k1(avr_batch *b, int on);
+
+/* The restore check of a K1 batch (AVR_KIND_CABAC, AVR_KIND_CABAC8, AVR_KIND_CABAC_CODES): will the decompressor's epilogue turn
+ * this slice's coded bytes into the payload they were made from?  For a caller that holds the original payload -- the compressor,
+ * which can run K1 from the codes its own CABAC decoder sees -- and wants to know it before the original is deleted.
+ * avr_batch_expect(b, slice, bytes, len): slice `slice` (already added) is expected to restore bytes[0 .. len); the bytes are copied
+ * now, into pinned staging padded to 8.  There is no switch: a run carries the check iff at least one of its slices has an
+ * expectation; avr_batch_reset drops them all.  avr_batch_submit sends the expectations to the device on the batch's stream and
+ * enqueues avr_restore_check_device (below) behind the encode on whichever path ran, behind the K1 verifier where that is on, between
+ * two events of its own; it still does not wait.  When avr_batch_wait runs a batch a second time, or runs K1p's second pass, the check
+ * follows again; the last answers are the ones reported.  A slice with a finding comes back from avr_batch_get with
+ * AVR_SLICE_VERIFY_FAILED, its bytes and length as the encoder left them; avr_batch_get_restore gives the index of the first byte that
+ * differs (the shorter length, where one string is the beginning of the other), AVR_VERIFY_NONE for every other slice and for a run
+ * without expectations; avr_batch_restore_ms the check's time (0 where it did not run; no part of avr_batch_timings or
+ * avr_batch_verify_ms).  avr_batch_get_verify stays the K1 verifier's answer.  AVR_ERR_INVALID: a K2 batch, a batch in flight or one
+ * that has run, a slice index not yet added, a second expectation for one slice, len >= 2^32 - 1, null bytes with len > 0.  With no
+ * expectation set, no buffer, event or launch of a run differs. */
+int avr_batch_expect(avr_batch *b, size_t slice, const uint8_t *bytes, size_t len);
+int avr_batch_get_restore(avr_batch *b, size_t slice, uint32_t *first_diff);
+int avr_batch_restore_ms(avr_batch *b, float *ms);
 
 /* ------------------------------------------------------------------ one batch over several GPUs
  * Slices are independent (one coder object each in the reference, recode.cpp:1270, :1525), so a batch shards
@@ -468,6 +491,33 @@ int avr_cabac_verify_codes_device(int device, void *stream, const uint8_t *codes
                                   const uint32_t *n_bins, const uint32_t *order /* may be NULL */, size_t n_slices,
                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
                                   int32_t *status, uint32_t *first_bad);
+
+/* Restore check: the decompressor's epilogue applied to coded K1 slices where they lie, a wave per slice, and the result compared with
+ * the payload the caller expects (avrecode-ms_amd/csrc/avr_restore.h holds the rule, avr_restore.hip the kernel).  For slice i with
+ * coded bytes out[out_off[i] .. + L), L = min(out_len[i], capacity), and expectation expect[expect_off[i] .. + E), E = expect_len[i]:
+ *   finish       L1 = L - 1 if L > 0 and the last coded byte is 0x80, else L (avr_drop_stop_byte: one byte, never two);
+ *   tail patch   with what the compressor writes into the container, parity E & 1 and last byte expect[E - 1], both for E >= 2 only
+ *                (for E < 2 nothing is patched and R = L1): if (L1 & 1) != (E & 1) the restored bytes are the L1 coded bytes and the
+ *                last byte behind them, R = L1 + 1; otherwise the L1 coded bytes with the last of them replaced by the last byte (where
+ *                L1 > 0), R = L1 (avr_tail_patch);
+ *   answer       first_diff[i] = the smallest j < min(R, E) at which the restored bytes differ from the expectation; else min(R, E)
+ *                if R != E; else AVR_VERIFY_NONE.
+ * expect_off: n_slices entries, multiples of 8, and each expectation readable to the next multiple of 8; `expect` itself 8-byte aligned;
+ * out_off as everywhere (n_slices + 1 entries, multiples of 8).  expect_len[i] == AVR_EXPECT_NONE: no expectation.  status is in/out:
+ *   a slice takes part when it comes in as AVR_SLICE_OK or AVR_SLICE_VERIFY_FAILED (a verifier may have run before) and has an
+ *   expectation; every other slice is skipped: first_diff[i] = AVR_VERIFY_NONE, its status left as it was;
+ *   a finding turns AVR_SLICE_OK into AVR_SLICE_VERIFY_FAILED.
+ * Nothing else is written: not out, out_len or expect.  No word of `out` that starts at or past L is read, whatever the region holds
+ * there, and nothing outside [out_off[i], out_off[i + 1]) and the padded expectation.  The call enqueues on `stream` and returns: it
+ * never blocks, allocates or uses a workspace.  It shares NOTHING with the encoders -- no table, no carry rule, no finish() -- and with
+ * avr_drop_stop_byte / avr_tail_patch the rule, written a second time and held equal by the tests.  What it proves: K1, finish, the
+ * tail patch and the container's two fields give back the real payload.  What it does not: the host range decoder (K3) and the host
+ * parser's agreement with itself on the way back.  Refused before anything touches a device (AVR_ERR_INVALID): a null pointer with
+ * n_slices > 0, n_slices >= 2^31, `expect` not 8-byte aligned. */
+int avr_restore_check_device(int device, void *stream,
+                             const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, size_t n_slices,
+                             const uint8_t *expect, const uint64_t *expect_off /* n_slices entries, multiples of 8 */,
+                             const uint32_t *expect_len, int32_t *status, uint32_t *first_diff);
 
 /* K1, intra-slice parallel form ("K1p", avrecode-ms_amd/csrc/avr_k1p.h): the same bytes as
  * avr_cabac_encode_tiles_device, produced by many lanes per slice -- for batches of few, long
