@@ -11,6 +11,7 @@
 #pragma once
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -178,7 +179,14 @@ class compressor {                                       // recode.cpp:1109-1316
         d->expect_payload_questions();
         hooks h = hook_adapter<compressor>::make(this);
         phase_timer t("compress: parse + record");
-        d->decode_video(&h, [](void *o, uint8_t *buf, int size) { return static_cast<compressor *>(o)->read_packet(buf, size); }, this);
+        // A throw out of the parse leaves the decoder of the slice it was in alive in the map: it goes here, while what its
+        // destructor writes to (pending_, restore_pending_) is certainly alive, not when the compressor itself is unwound.
+        try {
+            d->decode_video(&h, [](void *o, uint8_t *buf, int size) { return static_cast<compressor *>(o)->read_packet(buf, size); }, this);
+        } catch (...) {
+            cabac_contexts.clear();
+            throw;
+        }
         cabac_contexts.clear();
     }
     // The adaptive estimators on the device: the recorders write key records and the file's slices go into the batch as one group
@@ -331,7 +339,6 @@ class compressor {                                       // recode.cpp:1109-1316
 
     h264_model *get_model() { return &model_; }          // :1276-1278
     const context_ids &contexts() const { return contexts_; }
-    std::map<void *, std::unique_ptr<cabac_decoder>> cabac_contexts;     // :236
 
   private:
     // What the reference's find_next_coded_block_and_emit_literal does (recode.cpp:1282-1304).  libavcodec hands
@@ -404,6 +411,11 @@ class compressor {                                       // recode.cpp:1109-1316
     h264_model model_;
     Recoded out_;
     std::vector<pending> pending_;
+
+  public:
+    // The live decoders (:236).  ~cabac_decoder writes into pending_ and restore_pending_, so the map is the LAST member: it is
+    // destroyed first, while they are alive, whatever path (a hook adapter driven without prepare()) left a decoder in it.
+    std::map<void *, std::unique_ptr<cabac_decoder>> cabac_contexts;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -433,7 +445,12 @@ class decompressor {                                     // recode.cpp:1319-1598
         blocks_.resize(in_.block.size());
         hooks h = hook_adapter<decompressor>::make(this);
         phase_timer t("decompress: K3 + parse");
-        d->decode_video(&h, [](void *o, uint8_t *buf, int size) { return static_cast<decompressor *>(o)->read_packet(buf, size); }, this);
+        try {                                            // as compressor::prepare: no decoder outlives the parse, thrown out of or not
+            d->decode_video(&h, [](void *o, uint8_t *buf, int size) { return static_cast<decompressor *>(o)->read_packet(buf, size); }, this);
+        } catch (...) {
+            cabac_contexts.clear();
+            throw;
+        }
         cabac_contexts.clear();
     }
     size_t pending_slices() const { return pending_.size(); }
@@ -511,6 +528,7 @@ class decompressor {                                     // recode.cpp:1319-1598
         if (block.has_literal) {
             state.out_bytes = block.literal;
             state.done = true;
+            fed_bytes_ = std::min<uint64_t>(uint64_t(INT_MAX), fed_bytes_ + block.literal.size());
             return block.literal;
         }
         if (block.has_skip_coded) {
@@ -520,6 +538,12 @@ class decompressor {                                     // recode.cpp:1319-1598
             return std::string();
         }
         if (!block.has_size) throw std::runtime_error("CABAC block requires size field.");
+        // The size is a payload's, an int on the way in (init_decoder), out of a file whose offsets are ints there too
+        // (read_offset_): a size that is negative, or that takes the stream past INT_MAX, is nothing compress wrote, no
+        // init_decoder could announce it (recognize_coded_block compares with an int), and it is refused before it is allocated.
+        if (block.size < 0 || uint64_t(block.size) > uint64_t(INT_MAX) - fed_bytes_)
+            throw std::runtime_error("Invalid coded block size for surrogate: " + std::to_string(uint64_t(block.size)));
+        fed_bytes_ += uint64_t(block.size);
         state.coded = true;
         state.done = false;
         state.surrogate_marker = next_surrogate_marker(&surrogate_marker_sequence_number_);
@@ -560,7 +584,6 @@ class decompressor {                                     // recode.cpp:1319-1598
     };
 
     h264_model *get_model() { return &model_; }          // :1528-1530
-    std::map<void *, std::unique_ptr<cabac_decoder>> cabac_contexts;
 
   private:
     // The decoder announces a slice payload (init_decoder): which block is it?  Coded blocks -- recoded or
@@ -607,12 +630,17 @@ class decompressor {                                     // recode.cpp:1319-1598
     int read_index_ = 0;                                 // blocks the reader has opened
     std::string feed_;                                   // bytes of the block being read
     size_t feed_at_ = 0;
+    uint64_t fed_bytes_ = 0;                             // bytes of the stream the opened blocks stand for (saturates at INT_MAX)
     std::vector<block_state> blocks_;
     uint64_t surrogate_marker_sequence_number_ = 1;      // :1592
     int next_coded_block_ = 0;
     context_ids contexts_;                               // one numbering of the state addresses for the whole file
     h264_model model_;
     std::vector<pending> pending_;
+
+  public:
+    // The live decoders.  ~cabac_decoder writes into pending_, so the map is the LAST member (destroyed first), as compressor's.
+    std::map<void *, std::unique_ptr<cabac_decoder>> cabac_contexts;
 };
 
 // recode.cpp:1601-1640: compress, decompress, compare.  `make_decoder` supplies a fresh stream

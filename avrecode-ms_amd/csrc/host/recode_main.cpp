@@ -459,13 +459,19 @@ int main(int argc, char **argv) {
     }
     const std::string command = argv[1], input_filename = argv[2];
     std::ofstream out_file;
-    if (argc > 3) out_file.open(argv[3], std::ios::binary);
+    // compress / decompress: the output is opened once there are bytes to write, so a run that ends in an exception leaves
+    // nothing at the output path (no empty file that looks like a restored one)
+    auto write_out = [&](const std::string &bytes) {
+        if (argc > 3) out_file.open(argv[3], std::ios::binary);
+        (out_file.is_open() ? out_file : std::cout) << bytes;
+    };
     try {
         if (command == "compress") {
-            (out_file.is_open() ? out_file : std::cout) << compress_bytes(slurp(input_filename));
+            write_out(compress_bytes(slurp(input_filename)));
         } else if (command == "decompress") {
-            (out_file.is_open() ? out_file : std::cout) << decompress_bytes(slurp(input_filename));
+            write_out(decompress_bytes(slurp(input_filename)));
         } else if (command == "roundtrip") {
+            if (argc > 3) out_file.open(argv[3], std::ios::binary);
             return roundtrip(input_filename, out_file.is_open() ? &out_file : nullptr);
         } else if (command == "test") {
             perf_test_driver(input_filename);

@@ -193,6 +193,38 @@ size_t avr_oracle_cabac_encode(const uint16_t *recs, size_t n, uint8_t *states, 
     return e.n;
 }
 
+/* The same encoder from RESOLVED CODES (AVR_CODE_* of include/avrecode_ms_amd.h): every byte is the (symbol, *state)
+ * pair of one put -- code < 252: a context bin met in state code >> 1 (2*pStateIdx + valMPS <= 125), bin code & 1;
+ * 252 | bin: put_bypass(bin); 255 - bin: put_terminate(bin).  No state array: the caller resolved the states.
+ * A bin after put_terminate(1) is AVR_ORACLE_ERR_BAD_RECORD, as in avr_oracle_cabac_encode. */
+size_t avr_oracle_cabac_encode_codes(const uint8_t *codes, size_t n, uint8_t *out, size_t cap, int *status) {
+    pthread_once(&g_tables_once, build_tables_once);
+    c32_16_enc e;
+    c32_16_enc_init(&e, (uint32_t)((((uint32_t)1 << 31) / 0x200u) * 0x1FEu), out, cap);   /* cabac_code.h:30 */
+    int finished = 0;
+    for (size_t i = 0; i < n && !e.error; i++) {
+        unsigned code = codes[i];
+        if (finished) { e.error = AVR_ORACLE_ERR_BAD_RECORD; break; }
+        int normalize = floor_log2_u32(e.range / 0x100u);                /* cabac_code.h:37,59 */
+        if (code < 252) {
+            unsigned state = code >> 1;
+            int is_lps = (int)(code & 1) != (int)(state & 1);            /* cabac_code.h:34 */
+            unsigned approx = e.range >> (normalize - 1);                /* :39 */
+            uint32_t rlps = (uint32_t)g_lps_range[(approx & 0x180) + state] << normalize;   /* :40-41 */
+            c32_16_enc_put(&e, is_lps, rlps);                            /* :35 */
+        } else if (code < 254) {
+            c32_16_enc_put(&e, (int)(code & 1), e.range / 2);            /* :52-54 */
+        } else {
+            int bin = 255 - (int)code;
+            c32_16_enc_put(&e, bin, (uint32_t)2 << normalize);           /* :58-61 */
+            if (bin) { c32_16_enc_finish(&e); finished = 1; }            /* :63-65 */
+        }
+    }
+    if (!e.error && !finished) c32_16_enc_finish(&e);                    /* arithmetic_code.h:100 */
+    set_status(status, e.error);
+    return e.n;
+}
+
 /* ------------------------------------------------------------------ a16 tail / a17 */
 
 size_t avr_oracle_drop_stop_byte(const uint8_t *buf, size_t len) {

@@ -77,6 +77,11 @@ void avr_oracle_range_decode(const uint8_t *bytes, size_t len, const uint16_t *r
 size_t avr_oracle_cabac_encode(const uint16_t *recs, size_t n, uint8_t *states, size_t n_states,
                                uint8_t *out, size_t cap, int *status);
 
+/* The same encoder from resolved codes: one byte per bin, the (symbol, *state) pair of the put itself
+ * (AVR_CODE_CONTEXT / _BYPASS / _TERMINATE of include/avrecode_ms_amd.h).  Held to avr_oracle_cabac_encode on random
+ * streams by tests/test_damaged_recode.py; what tests/cpu_batch.cpp codes the decompress direction with. */
+size_t avr_oracle_cabac_encode_codes(const uint8_t *codes, size_t n, uint8_t *out, size_t cap, int *status);
+
 /* The two re-indexed tables, for tests that compare them with the product's. */
 void avr_oracle_cabac_tables(uint8_t lps_range[512], uint8_t mlps_state[256]);
 
