@@ -310,7 +310,7 @@ def test_hooks(**hooks):
     chain_lanes, k1_form_ref, k1_path [1 serial, 2 chunked], no_dense, no_hint, k2p_seg_len, local_waves, k2p_wave); all of them keep the bytes exact and
     only force paths that real batches take rarely -- except est_flip / est_flip_bin, which add one to neg of one resolved record of a batch of key records with set_verify on
     (between the resolver and the encode: only the estimator checker can see it), verify_flip, which corrupts one slice's first byte on the device in front of the verifier (a batch with
-    set_verify or set_verify_k1 on) so that a test sees a failure travel through the batch API, and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
+    set_verify or set_verify_k1 on) so that a test sees a failure travel through the batch API, restore_flip, the same in front of the restore check (a batch with expectations), and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status
     AVR_SLICE_RETRY_SERIAL) so that a test can see which ones it coded itself.  The product library has no such switches."""
     global _lib, _hooks_lib
     if _hooks_lib is None:

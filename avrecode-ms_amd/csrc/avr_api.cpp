@@ -276,6 +276,7 @@ int avr_test_hook_set(const char *name, uint32_t value) {
     else if (!strcmp(name, "verify_flip")) h.verify_flip = value;
     else if (!strcmp(name, "est_flip")) h.est_flip = value;
     else if (!strcmp(name, "est_flip_bin")) h.est_flip_bin = value;
+    else if (!strcmp(name, "restore_flip")) h.restore_flip = value;
     else if (!strcmp(name, "reset")) h = avr::TestHooks{};
     else return fail(AVR_ERR_INVALID, "unknown test hook %s", name);
     return AVR_OK;
@@ -498,6 +499,14 @@ static int enqueue_verify_k1(avr_batch *b, uint32_t n32, int form, const void *r
 static int reserve_restore(avr_batch *b, size_t n);
 static int stage_restore(avr_batch *b, size_t n);
 static int enqueue_restore(avr_batch *b, uint32_t n32);
+#ifdef AVR_TEST_HOOKS
+// Test build only (restore_flip, avr_internal.h): verify_flip in front of the restore check of a run's first pass -- not in front of
+// the one that follows K1p's second pass at avr_batch_wait, over the same bytes: the hook has had its turn.
+static int restore_flip_hook(avr_batch *b, uint32_t n32) {
+    if (const uint32_t k = avr::test_hooks().restore_flip; k && k <= n32) AVR_HIP(avr::launch_verify_flip(b->stream, b->d_out.p, b->d_out_off.p, k - 1));
+    return AVR_OK;
+}
+#endif
 // what the expectations' offsets and lengths take of the arena
 static size_t staged_restore(const avr_batch *b, size_t n) { return b->n_expect ? staged<uint64_t>(n) + staged<uint32_t>(n) : 0; }
 
@@ -549,6 +558,9 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     }
     b->last_path = chunked;
     if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kCodes, d_codes, b->d_res_off.p, chunked ? nullptr : b->d_order.p))) return rc;
+#ifdef AVR_TEST_HOOKS
+    if (b->restored && (rc = restore_flip_hook(b, n32))) return rc;
+#endif
     if (b->restored && (rc = enqueue_restore(b, n32))) return rc;
     return enqueue_lengths(b, n32);
 }
@@ -747,6 +759,9 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         if (rc) return rc;
         if (b->verified_est && (rc = enqueue_verify_est(b, n32))) return rc;
     }
+#ifdef AVR_TEST_HOOKS
+    if (b->restored && (rc = restore_flip_hook(b, n32))) return rc;
+#endif
     if (b->restored && (rc = enqueue_restore(b, n32))) return rc;    // (K1 only: a K2 batch takes no expectations)
     return enqueue_lengths(b, n32);
 }

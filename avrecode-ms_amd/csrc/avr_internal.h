@@ -56,6 +56,7 @@ struct TestHooks {
     uint32_t verify_flip;            // batch API with verify on: k > 0 complements bit 7 of byte 0 of slice k - 1's output region between the encode and the verifier
     uint32_t est_flip, est_flip_bin; // batch API with verify on, key records: k > 0 adds one to neg of bin est_flip_bin of slice k - 1's resolved record, between the
                                      // resolver and the encode: encoder and K2 verifier agree on the wrong pair, only the estimator checker can see it
+    uint32_t restore_flip;           // batch API, a run that carries the restore check: verify_flip in front of the check (behind the K1 verifier where that is on)
     uint32_t k1p_keep_retry;         // K1p (every form): the slices that leave the parallel path -- declined by the scheme, handed over by phase D -- keep
                                      // AVR_SLICE_RETRY_SERIAL (no serial kernel after it), so a test sees which slices phase D coded itself
 };

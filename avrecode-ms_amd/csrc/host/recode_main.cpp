@@ -183,9 +183,13 @@ void perf_test_driver_sequential(const std::string &directory_path) {
         std::stringstream captured;
         std::streambuf *saved = std::cerr.rdbuf(captured.rdbuf());       // the run's messages go to the log (test.cpp:129)
         int ctime = 0, dtime = 0, rc = 1;
-        try {
-            std::ofstream output_file(directory_path + "/output/" + files[i].filename().string(), std::ios::binary);
-            rc = roundtrip(files[i].string(), output_file.is_open() ? &output_file : nullptr, &ctime, &dtime, int(i));
+        try {                                            // the output file is opened once the roundtrip has held: a file that fails leaves none
+            std::ostringstream recoded;
+            rc = roundtrip(files[i].string(), &recoded, &ctime, &dtime, int(i));
+            if (rc == 0) {
+                std::ofstream output_file(directory_path + "/output/" + files[i].filename().string(), std::ios::binary);
+                if (output_file.is_open()) output_file << recoded.str();
+            }
         } catch (const std::exception &e) {
             std::cerr << "Exception (" << typeid(e).name() << "): " << e.what() << std::endl;
         }
@@ -471,8 +475,11 @@ int main(int argc, char **argv) {
         } else if (command == "decompress") {
             write_out(decompress_bytes(slurp(input_filename)));
         } else if (command == "roundtrip") {
-            if (argc > 3) out_file.open(argv[3], std::ios::binary);
-            return roundtrip(input_filename, out_file.is_open() ? &out_file : nullptr);
+            if (argc <= 3) return roundtrip(input_filename, nullptr);
+            std::ostringstream recoded;                  // as above: no file at the output path unless the roundtrip has held
+            const int rc = roundtrip(input_filename, &recoded);
+            if (rc == 0) write_out(recoded.str());
+            return rc;
         } else if (command == "test") {
             perf_test_driver(input_filename);
             return 0;

@@ -105,6 +105,9 @@ size_t avr_spec_cabac_encode(const uint16_t *recs, size_t n, uint8_t *states, si
  * 1195): recovers bins_out[i] for the selector of recs[i] (the bin bit of recs is ignored). */
 int avr_spec_cabac_decode(const uint8_t *bytes, size_t len, const uint16_t *recs, size_t n,
                           uint8_t *states, size_t n_states, uint8_t *bins_out);
+/* The same decoder over a slice of resolved codes (AVR_CODE_*: each byte is the (state, bin) pair of its bin, so no states are kept):
+ * bins_out[i] is the bin decoded in the state codes[i] >> 1 names (126: bypass), whatever codes[i] & 1 says. */
+int avr_spec_cabac_decode_codes(const uint8_t *bytes, size_t len, const uint8_t *codes, size_t n, uint8_t *bins_out);
 
 /* ---- batch helper for bench.py's cpu_baseline leg and large parity checks:
  * encode `n_slices` slices whose records are rec[off[i] .. off[i+1]) with

@@ -160,3 +160,32 @@ int avr_spec_cabac_decode(const uint8_t *bytes, size_t len, const uint16_t *recs
     }
     return AVR_ORACLE_OK;
 }
+
+/* The same engine for a slice given as RESOLVED CODES (AVR_CODE_* of include/avrecode_ms_amd.h): one byte per bin, the (state, bin)
+ * pair of the put itself, so no states are kept.  code >> 1 is the state byte 2 * pStateIdx + valMPS the bin was coded in: 126 (codes
+ * 252, 253) stands for bypass (Figure 9-5), every other value is decoded by Figure 9-3 with that state -- 127 (codes 254, 255) among
+ * them: pStateIdx 63, whose rangeTabLPS row is 2 in every quarter, is what a terminate bin and a context bin at state 126 / 127 both
+ * are, seen from valMPS 1.  DecodeTerminate (Figure 9-6) does no RenormD behind binVal 1; Figure 9-3 does, which differs only in
+ * what would be read after the slice's last bin.  bins_out[i]: the decoded bin, to be held against codes[i] & 1. */
+int avr_spec_cabac_decode_codes(const uint8_t *bytes, size_t len, const uint8_t *codes, size_t n, uint8_t *bins_out) {
+    spec_dec d = { bytes, len * 8, 0, 510, 0 };
+    for (int i = 0; i < 9; i++) d.offset = (d.offset << 1) | read_bit(&d);      /* 9.3.1.2 */
+    for (size_t i = 0; i < n; i++) {
+        unsigned state = codes[i] >> 1;
+        int bin;
+        if (state == 126) {                                                      /* Figure 9-5 */
+            d.offset = (d.offset << 1) | read_bit(&d);
+            bin = d.offset >= d.range;
+            if (bin) d.offset -= d.range;
+        } else {                                                                 /* Figure 9-3 */
+            int p = (int)(state >> 1), mps = (int)(state & 1);
+            unsigned rlps = avr_oracle_rangeTabLPS[p][(d.range >> 6) & 3];
+            d.range -= rlps;
+            if (d.offset >= d.range) { bin = !mps; d.offset -= d.range; d.range = rlps; }
+            else bin = mps;
+            while (d.range < 256) { d.range <<= 1; d.offset = (d.offset << 1) | read_bit(&d); }
+        }
+        bins_out[i] = (uint8_t)bin;
+    }
+    return AVR_ORACLE_OK;
+}

@@ -38,7 +38,7 @@ def build_cached():
     tests, which compare the product with it and have no use for a build per session."""
     out = os.path.join(ROOT, "tests", "_recode_cpu")
     host = os.path.join(CSRC, "host")
-    deps = [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(ROOT, "include", "avrecode_ms_amd.h"), os.path.join(ROOT, "tests", "cpu_batch.cpp")]
+    deps = [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(ROOT, "include", "avrecode_ms_amd.h"), os.path.join(ROOT, "tests", "cpu_batch.cpp"), os.path.join(ROOT, "tests", "est_plain.cpp")]
     deps += [os.path.join(ROOT, "oracle", f) for f in ("avr_oracle.c", "avr_oracle.h", "avr_oracle_coder.inc", "avr_oracle_tables.h", "spec_cabac.c")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         _compile(out + ".tmp", ["-O2"], [os.path.join(host, "recode_main.cpp"), os.path.join(ROOT, "tests", "cpu_batch.cpp")])

@@ -139,20 +139,6 @@ def test_the_stand_in_restores_the_clip_and_its_container_reads_back(cli, clip, 
     assert len(dmg.coded_blocks(blocks)) >= 3 and s["pending"].startswith("%d slices" % len(dmg.coded_blocks(blocks)))
 
 
-def test_the_stand_in_refuses_what_it_does_not_stand_for(cli, tmp_path):
-    """Key records, the verify switches and the restore check: a clean error through avr_last_error, no quiet other route."""
-    src = os.path.join(cpu_recode.GOLDEN, "realshort.mp4")
-    recoded = tmp_path / "sound.recode"
-    recoded.write_bytes(cli.sound("realshort", 0)["container"])
-    for command, source, switch in (("compress", src, "AVR_VERIFY"), ("compress", src, "AVR_VERIFY_RESTORE"), ("compress", src, "AVR_DEVICE_ESTIMATORS"),
-                                    ("decompress", recoded, "AVR_VERIFY_K1")):
-        out = tmp_path / "out"
-        o = cpu_recode.run(cli.asan, command, source, out, 0, env={switch: "1"})
-        clean(o)
-        assert o.status == 1 and "cpu_batch" in o.messages[0] and "not part of the CPU stand-in" in o.messages[0], (switch, o.stderr)
-        assert not out.exists()
-
-
 # ------------------------------------------------------------------------------------------------ damaged containers
 def damaged_container(cli, tmp_path, clip, model_hooks, case):
     s = cli.sound(clip, model_hooks)

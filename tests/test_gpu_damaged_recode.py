@@ -1,7 +1,8 @@
 """The product command line on the device against the CPU stand-in (tests/cpu_batch.cpp: the same host code, the oracle coding the
 batches), on sound clips and on the damaged containers of tests/damaged_recode.py.
 
-The stand-in is the plain reference of the whole direction: `compress` must write the same .recode bytes on both (both clips, both
+The stand-in is the plain reference of the whole command (every route of it: tests/test_gpu_cli_verify_faults.py holds the verify
+switches to it); here, of the decompress direction on damaged input: `compress` must write the same .recode bytes on both (both clips, both
 hook settings -- which is also what proves the stand-in codes what the device codes), and on every damaged container `decompress`
 must end the same way on both: exit status, message line, and the output's bytes when the status is 0.  Once more with
 AVR_VERIFY_K1=1 on the product only: the verifier decodes what K1 coded from the recorder's codes, so it finds nothing in a run the
