@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "avr_cabac_verify.h"
@@ -58,55 +60,99 @@ int select_device(int device) {
     return AVR_OK;
 }
 
-template <class T>
-struct DevBuf {
+// Memory of the device (DevBuf) or pinned memory of the host (PinBuf) that grows and never shrinks; reserve keeps nothing of what
+// the buffer held.  A buffer owns its memory: it moves, it is not copied, and whoever holds it need not release it.
+template <class T, bool Pinned>
+struct Buf {
     T *p = nullptr;
     size_t cap = 0;       // elements
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf &operator=(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~Buf() { release(); }
     int reserve(size_t n) {
         if (n <= cap) return AVR_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
+        release();
         size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T));
-        if (e != hipSuccess) return fail(AVR_ERR_NOMEM, "hipMalloc(%zu bytes): %s", want * sizeof(T), hipGetErrorString(e));
+        hipError_t e = Pinned ? hipHostMalloc(reinterpret_cast<void **>(&p), want * sizeof(T), hipHostMallocDefault)
+                              : hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T));
+        if (e != hipSuccess) return fail(AVR_ERR_NOMEM, "%s(%zu bytes): %s", Pinned ? "hipHostMalloc" : "hipMalloc", want * sizeof(T), hipGetErrorString(e));
         cap = want;
         return AVR_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinBuf = Buf<T, true>;
+
+// N timing events, made together or not at all: a create that fails leaves none behind, and the next one tries again.
+template <int N>
+struct Events {
+    hipEvent_t e[N] = {};
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events() { clear(); }
+    void clear() { for (auto &x : e) { if (x) (void)hipEventDestroy(x); x = nullptr; } }
+    hipError_t create() {                                        // (the caller has selected the device)
+        if (e[0]) return hipSuccess;
+        for (auto &x : e)
+            if (hipError_t err = hipEventCreate(&x); err != hipSuccess) { clear(); return err; }
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int i) const { return e[i]; }
 };
 
-template <class T>
-struct PinBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n) {
-        if (n <= cap) return AVR_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), want * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) return fail(AVR_ERR_NOMEM, "hipHostMalloc(%zu bytes): %s", want * sizeof(T), hipGetErrorString(e));
-        cap = want;
-        return AVR_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+// A batch's stream.  Declared in front of everything that may have work on it, so destroyed behind all of that.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) { avr::forget_part_streams(s); avr::forget_stream(s); (void)hipStreamDestroy(s); } }
+    operator hipStream_t() const { return s; }
 };
 
-// Host-side plan shared by the batch API and tests: process slices longest first, 64 per tile.  records_per_chunk: 8 for two-byte
-// records, 16 for one-byte tiles (k_pack_tiles8_narrow).
-void plan_tiles(const std::vector<uint32_t> &n_bins, std::vector<uint32_t> &order, std::vector<uint64_t> &tile_off,
-                uint32_t records_per_chunk = 8) {
-    const size_t n = n_bins.size();
-    order.resize(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return n_bins[a] > n_bins[b]; });
-    const size_t n_tiles = (n + 63) / 64;
-    tile_off.assign(n_tiles + 1, 0);
-    for (size_t t = 0; t < n_tiles; t++) {
-        const uint64_t chunks = (uint64_t(n_bins[order[t * 64]]) + records_per_chunk - 1) / records_per_chunk;   // sorted: first lane is the longest
-        tile_off[t + 1] = tile_off[t] + chunks * 64;
-    }
+int check_states8(size_t n_states) {
+    if (n_states > AVR_MAX_STATES8)
+        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    return AVR_OK;
 }
+
+// A check behind the encode of a run.  A batch has three: the verifier of its kind, the estimator checker, the restore check.  Which
+// settings arm one, which kernel it launches and what else that kernel reads stay with the check; this is what the three share.
+// Off by default, and then none of this is touched: the events are made when the check is first asked for, the arrays when first armed.
+struct Check {
+    bool on = false;                        // the run in flight / the last run had it
+    Events<2> ev;                           // its start and end, as last recorded
+    float ms = 0, before = 0;               // what it took; of that, in front of K1p's second pass (where there was one)
+    DevBuf<uint32_t> d_first;               // per slice: the first bin (byte) it found wrong, AVR_VERIFY_NONE for none
+    PinBuf<uint32_t> h_first;
+
+    int make_events(int device) {
+        if (ev[0]) return AVR_OK;
+        if (int rc = select_device(device)) return rc;
+        if (hipError_t e = ev.create(); e != hipSuccess) return hip_fail(e, "hipEventCreate(&e)");
+        return AVR_OK;
+    }
+    // at submit: whether this run has the check, and room for the answers of n slices
+    int arm(bool has, size_t n) {
+        on = has; before = 0;
+        if (!on) return AVR_OK;
+        if (int rc = d_first.reserve(n)) return rc;
+        return h_first.reserve(n);
+    }
+    int start(hipStream_t s) { AVR_HIP(hipEventRecord(ev[0], s)); return AVR_OK; }
+    int end(hipStream_t s) { AVR_HIP(hipEventRecord(ev[1], s)); return AVR_OK; }
+    int fetch(hipStream_t s, size_t n) {
+        if (on) AVR_HIP(hipMemcpyAsync(h_first.p, d_first.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        return AVR_OK;
+    }
+    uint32_t answer(size_t slice) const { return on ? h_first.p[slice] : AVR_VERIFY_NONE; }
+    float span() const { float t = 0; if (on) (void)hipEventElapsedTime(&t, ev[0], ev[1]); return t; }
+    void carry() { before = span(); }       // in front of a second pass, which records both events again
+    void finish() { ms = before + span(); }
+};
 
 }  // namespace
 
@@ -118,9 +164,15 @@ struct avr_batch {
     bool keys = false;                      // the slices came as key records (AVR_KIND_RANGE_KEYS); kind is AVR_KIND_RANGE
     size_t n_states = 0;
     bool ran = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {};
+    Stream stream;
+    Events<5> ev;
     float ms[4] = {0, 0, 0, 0};
+    // Nothing below is released by name: every buffer and event frees itself, behind this -- the device selected, the stream drained --
+    // and in front of the stream's own end.
+    ~avr_batch() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 
     // host side
     PinBuf<uint16_t> h_recs;
@@ -169,31 +221,51 @@ struct avr_batch {
     // verification of a run (K2: avr_batch_set_verify, K1: avr_batch_set_verify_k1): off by default, and then none of this is touched
     bool verify = false;                    // the setting: the next submit of a K2 batch enqueues the verifier behind the encode
     bool verify_k1 = false;                 // the same for a K1 batch (avr_cabac_verify.hip)
-    bool verified = false;                  // the run in flight / the last run had it
-    hipEvent_t vev[3] = {};                 // end of the encode, start and end of the verifier (created when verify is first set)
-    float verify_ms = 0;
-    DevBuf<uint32_t> d_first_bad;
-    PinBuf<uint32_t> h_first_bad;
-    // ... and of a run of key records the estimator checker (avr_est_verify.hip) behind it, with events and answers of its own
-    bool verified_est = false;              // the run in flight / the last run had it
-    hipEvent_t eev[2] = {};                 // start and end of the checker (created with vev)
-    float verify_est_ms = 0;
-    DevBuf<uint32_t> d_first_bad_est;
-    PinBuf<uint32_t> h_first_bad_est;
-
+    Check verifier;                         // armed by the setting of the batch's kind (events: made when either is first set)
+    // ... and of a run of key records the estimator checker (avr_est_verify.hip) behind it
+    Check est_checker;                      // armed by verify, for key records (events: made when verify is first set)
     // the restore check of a K1 run (avr_batch_expect): a batch without expectations touches none of this
+    Check restorer;                         // armed by any expectation (events: made with the first one)
     std::vector<uint64_t> expect_off;       // per slice: where its expectation lies in h_expect (bytes, multiples of 8)
     std::vector<uint32_t> expect_len;       // per slice: its length, AVR_EXPECT_NONE for a slice without one
     size_t n_expect = 0, expect_used = 0;   // slices that have one; bytes of h_expect in use (a multiple of 8)
     PinBuf<uint8_t> h_expect;               // the expectations as they came, each padded to 8
-    bool restored = false;                  // the run in flight / the last run had the check
-    hipEvent_t rev[2] = {};                 // end of what ran before the check (the encode, or the K1 verifier), end of the check (created with the first expectation)
-    float restore_ms = 0;
     DevBuf<uint8_t> d_expect;
     DevBuf<uint64_t> d_expect_off;
-    DevBuf<uint32_t> d_expect_len, d_first_diff;
-    PinBuf<uint32_t> h_first_diff;
+    DevBuf<uint32_t> d_expect_len;
+    // the three in the order they run in; the encode's slot of the timings ends where the first of them that a run has starts
+    std::array<Check *, 3> checks() { return {&verifier, &est_checker, &restorer}; }
+
+    // what the encoder of the run in flight read, for the verifier behind it to read the same
+    struct Coded {
+        int form = 0;                       // K1: a cabac_verify::Form; K2: 1 for tiles, 0 for slice-major records
+        const void *recs = nullptr;         // the records (tiles, codes) ...
+        const uint64_t *off = nullptr;      // ... and where each slice's (tile's) begin
+        const uint32_t *order = nullptr;    // the slices' order, where the path has one
+    } coded;
 };
+
+// The refusals the entry points open with.  check_idle: for what changes a batch between runs; check_open: for what adds to a batch
+// that has not run yet; check_ran, check_slice: for the getters (more: the caller's other pointers).
+static int check_idle(const avr_batch *b) {
+    if (!b) return fail(AVR_ERR_INVALID, "null batch");
+    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    return AVR_OK;
+}
+static int check_open(const avr_batch *b) {
+    if (int rc = check_idle(b)) return rc;
+    if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
+    return AVR_OK;
+}
+static int check_ran(const avr_batch *b, bool more = true) {
+    if (!b || !b->ran || !more) return fail(AVR_ERR_INVALID, "batch has not run");
+    return AVR_OK;
+}
+static int check_slice(const avr_batch *b, size_t slice) {
+    if (int rc = check_ran(b)) return rc;
+    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
+    return AVR_OK;
+}
 
 // One plan array to the device through the batch's pinned arena: the copy is asynchronous for real (a copy from
 // pageable memory is staged by the runtime inside the call), and the source stays put until avr_batch_wait.
@@ -252,34 +324,21 @@ extern "C" {
 #ifdef AVR_TEST_HOOKS
 // Test build only (libavrecode_hip_hooks.so): set a hook by name; returns AVR_ERR_INVALID for an unknown name.
 int avr_test_hook_set(const char *name, uint32_t value) {
+    static const struct { const char *name; uint32_t avr::TestHooks::*field; } kHooks[] = {
+#define AVR_HOOK(f) {#f, &avr::TestHooks::f}
+        AVR_HOOK(k1p_force_retry_every), AVR_HOOK(census_stride), AVR_HOOK(chain_lanes), AVR_HOOK(k1_form_ref), AVR_HOOK(k1_emit_lds),
+        AVR_HOOK(k1_path), AVR_HOOK(no_dense), AVR_HOOK(no_hint), AVR_HOOK(k2p_seg_len), AVR_HOOK(local_waves), AVR_HOOK(k2p_wave),
+        AVR_HOOK(k1p_keep_retry), AVR_HOOK(k1_waves), AVR_HOOK(k1_fwd), AVR_HOOK(k1_words8), AVR_HOOK(chain_nsegs), AVR_HOOK(chain_whole),
+        AVR_HOOK(chain_segments), AVR_HOOK(chain_force_redo), AVR_HOOK(verify_flip), AVR_HOOK(est_flip), AVR_HOOK(est_flip_bin),
+        AVR_HOOK(restore_flip),
+#undef AVR_HOOK
+    };
     avr::TestHooks &h = avr::test_hooks();
     if (!name) return fail(AVR_ERR_INVALID, "null hook name");
-    if (!strcmp(name, "k1p_force_retry_every")) h.k1p_force_retry_every = value;
-    else if (!strcmp(name, "census_stride")) h.census_stride = value;
-    else if (!strcmp(name, "chain_lanes")) h.chain_lanes = value;
-    else if (!strcmp(name, "k1_form_ref")) h.k1_form_ref = value;
-    else if (!strcmp(name, "k1_emit_lds")) h.k1_emit_lds = value;
-    else if (!strcmp(name, "k1_path")) h.k1_path = value;
-    else if (!strcmp(name, "no_dense")) h.no_dense = value;
-    else if (!strcmp(name, "no_hint")) h.no_hint = value;
-    else if (!strcmp(name, "k2p_seg_len")) h.k2p_seg_len = value;
-    else if (!strcmp(name, "local_waves")) h.local_waves = value;
-    else if (!strcmp(name, "k2p_wave")) h.k2p_wave = value;
-    else if (!strcmp(name, "k1p_keep_retry")) h.k1p_keep_retry = value;
-    else if (!strcmp(name, "k1_waves")) h.k1_waves = value;
-    else if (!strcmp(name, "k1_fwd")) h.k1_fwd = value;
-    else if (!strcmp(name, "k1_words8")) h.k1_words8 = value;
-    else if (!strcmp(name, "chain_nsegs")) h.chain_nsegs = value;
-    else if (!strcmp(name, "chain_whole")) h.chain_whole = value;
-    else if (!strcmp(name, "chain_segments")) h.chain_segments = value;
-    else if (!strcmp(name, "chain_force_redo")) h.chain_force_redo = value;
-    else if (!strcmp(name, "verify_flip")) h.verify_flip = value;
-    else if (!strcmp(name, "est_flip")) h.est_flip = value;
-    else if (!strcmp(name, "est_flip_bin")) h.est_flip_bin = value;
-    else if (!strcmp(name, "restore_flip")) h.restore_flip = value;
-    else if (!strcmp(name, "reset")) h = avr::TestHooks{};
-    else return fail(AVR_ERR_INVALID, "unknown test hook %s", name);
-    return AVR_OK;
+    if (!strcmp(name, "reset")) { h = avr::TestHooks{}; return AVR_OK; }
+    for (const auto &k : kHooks)
+        if (!strcmp(name, k.name)) { h.*k.field = value; return AVR_OK; }
+    return fail(AVR_ERR_INVALID, "unknown test hook %s", name);
 }
 #endif
 
@@ -305,9 +364,8 @@ avr_batch *avr_batch_create(int device, size_t max_slices, size_t max_bins) {
     b->device = device;
     b->max_slices = max_slices;
     b->max_bins = max_bins;
-    bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < 5; i++) ok = hipEventCreate(&b->ev[i]) == hipSuccess;
-    ok = ok && b->h_recs.reserve(max_bins + 16 * max_slices) == AVR_OK;   // records: n + 7 per slice; codes (bytes): n + 31
+    const bool ok = hipStreamCreateWithFlags(&b->stream.s, hipStreamNonBlocking) == hipSuccess && b->ev.create() == hipSuccess &&
+                    b->h_recs.reserve(max_bins + 16 * max_slices) == AVR_OK;   // records: n + 7 per slice; codes (bytes): n + 31
     if (!ok) {
         if (!g_err[0]) fail(AVR_ERR_HIP, "stream/event creation failed");
         avr_batch_destroy(b);
@@ -319,34 +377,10 @@ avr_batch *avr_batch_create(int device, size_t max_slices, size_t max_bins) {
     return b;
 }
 
-void avr_batch_destroy(avr_batch *b) {
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    b->h_recs.release(); b->h_states.release(); b->h_out.release(); b->h_final.release();
-    b->h_out_len.release(); b->h_status.release(); b->h_plan.release(); b->h_ndense.release();
-    b->d_recs.release(); b->d_recs8.release(); b->d_tiles.release(); b->d_rec_off.release(); b->d_tile_off.release();
-    b->d_out_off.release(); b->d_dense_off.release(); b->d_n_bins.release(); b->d_order.release();
-    b->d_out_len.release(); b->d_status.release(); b->d_states.release(); b->d_final.release();
-    b->d_out.release(); b->d_dense.release(); b->d_first_bad_est.release(); b->h_first_bad_est.release();
-    b->d_res_off.release(); b->d_dig_off.release(); b->d_chunk_base.release(); b->d_chunk_slice.release();
-    b->d_blk_base.release(); b->d_blk_slice.release(); b->d_workspace.release();
-    b->h_est_in.release(); b->h_est_out.release(); b->d_keys.release(); b->d_group_first.release();
-    b->d_est_in.release(); b->d_est_out.release(); b->d_est_ws.release();
-    b->d_first_bad.release(); b->h_first_bad.release();
-    b->h_expect.release(); b->d_expect.release(); b->d_expect_off.release(); b->d_expect_len.release();
-    b->d_first_diff.release(); b->h_first_diff.release();
-    for (auto &e : b->rev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : b->vev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : b->eev) if (e) (void)hipEventDestroy(e);
-    if (b->stream) { avr::forget_part_streams(b->stream); avr::forget_stream(b->stream); (void)hipStreamDestroy(b->stream); }
-    delete b;
-}
+void avr_batch_destroy(avr_batch *b) { delete b; }
 
 int avr_batch_reset(avr_batch *b) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    if (int rc = check_idle(b)) return rc;
     b->kind = -1; b->recs8 = false; b->keys = false; b->n_states = 0; b->ran = false; b->total_bins = 0;
     b->group_first.clear(); b->est_in.clear(); b->any_est_in = false; b->est_out_fetched = false;
     b->rec_off.assign(1, 0);
@@ -359,9 +393,7 @@ int avr_batch_reset(avr_batch *b) {
 constexpr size_t kEstTable = size_t(AVR_EST_KEYS) * 2;           // bytes of one table of estimators
 
 int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
-    if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
+    if (int rc = check_open(b)) return rc;
     if (b->kind >= 0 && !b->keys) return fail(AVR_ERR_INVALID, "a batch holds slices of one kind only: groups belong to key records");
     if (b->group_first.size() >= b->max_slices) return fail(AVR_ERR_CAPACITY, "batch holds max_slices=%zu groups", b->max_slices);
     for (size_t k = 0; est_in && k < AVR_EST_KEYS; k++) {
@@ -380,9 +412,7 @@ int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in) {
 
 // Room for one more slice in the pinned staging buffer (padding written); *where = its first element.
 static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_states, size_t n_states, void **where) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
-    if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
+    if (int rc = check_open(b)) return rc;
     if (kind != AVR_KIND_CABAC && kind != AVR_KIND_RANGE && kind != AVR_KIND_CABAC_CODES && kind != AVR_KIND_CABAC8 &&
         kind != AVR_KIND_RANGE_KEYS)
         return fail(AVR_ERR_INVALID, "unknown kind %d", kind);
@@ -392,7 +422,7 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
     // one-byte records are K1 records in another width: the batch is an AVR_KIND_CABAC batch whose staging buffer holds bytes
     const bool recs8 = kind == AVR_KIND_CABAC8;
     if (recs8) {
-        if (n_states > AVR_MAX_STATES8) return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+        if (int rc = check_states8(n_states)) return rc;
         kind = AVR_KIND_CABAC;
     }
     if ((b->kind >= 0 && (b->kind != kind || b->recs8 != recs8 || b->keys != keys)) || (!keys && !b->group_first.empty()))
@@ -452,63 +482,125 @@ int avr_batch_reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *ini
     return reserve_slice(b, kind, n, init_states, n_states, buffer);
 }
 
+// one slice copied in: `elem` bytes a record (code) of `src`
+static int add_slice(avr_batch *b, int kind, const void *src, size_t n, size_t elem, const uint8_t *init_states, size_t n_states) {
+    if (!src && n) return fail(AVR_ERR_INVALID, kind == AVR_KIND_CABAC_CODES ? "null codes" : "null records");
+    void *dst = nullptr;
+    const int idx = reserve_slice(b, kind, n, init_states, n_states, &dst);
+    if (idx >= 0 && n) memcpy(dst, src, n * elem);
+    return idx;
+}
+
 int avr_batch_add_slice_cabac(avr_batch *b, const uint16_t *recs, size_t n, const uint8_t *init_states, size_t n_states) {
-    if (!recs && n) return fail(AVR_ERR_INVALID, "null records");
-    void *dst = nullptr;
-    const int idx = reserve_slice(b, AVR_KIND_CABAC, n, init_states, n_states, &dst);
-    if (idx >= 0 && n) memcpy(dst, recs, n * sizeof(uint16_t));
-    return idx;
+    return add_slice(b, AVR_KIND_CABAC, recs, n, 2, init_states, n_states);
 }
-
-int avr_batch_add_slice_range(avr_batch *b, const uint16_t *recs, size_t n) {
-    if (!recs && n) return fail(AVR_ERR_INVALID, "null records");
-    void *dst = nullptr;
-    const int idx = reserve_slice(b, AVR_KIND_RANGE, n, nullptr, 0, &dst);
-    if (idx >= 0 && n) memcpy(dst, recs, n * sizeof(uint16_t));
-    return idx;
-}
-
-int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n) {
-    if (!recs && n) return fail(AVR_ERR_INVALID, "null records");
-    void *dst = nullptr;
-    const int idx = reserve_slice(b, AVR_KIND_RANGE_KEYS, n, nullptr, 0, &dst);
-    if (idx >= 0 && n) memcpy(dst, recs, n * sizeof(uint16_t));
-    return idx;
-}
-
+int avr_batch_add_slice_range(avr_batch *b, const uint16_t *recs, size_t n) { return add_slice(b, AVR_KIND_RANGE, recs, n, 2, nullptr, 0); }
+int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n) { return add_slice(b, AVR_KIND_RANGE_KEYS, recs, n, 2, nullptr, 0); }
 int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n, const uint8_t *init_states, size_t n_states) {
-    if (!recs8 && n) return fail(AVR_ERR_INVALID, "null records");
-    void *dst = nullptr;
-    const int idx = reserve_slice(b, AVR_KIND_CABAC8, n, init_states, n_states, &dst);
-    if (idx >= 0 && n) memcpy(dst, recs8, n);
-    return idx;
+    return add_slice(b, AVR_KIND_CABAC8, recs8, n, 1, init_states, n_states);
 }
-
-int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n) {
-    if (!codes && n) return fail(AVR_ERR_INVALID, "null codes");
-    void *dst = nullptr;
-    const int idx = reserve_slice(b, AVR_KIND_CABAC_CODES, n, nullptr, 0, &dst);
-    if (idx >= 0 && n) memcpy(dst, codes, n);
-    return idx;
-}
+int avr_batch_add_slice_codes(avr_batch *b, const uint8_t *codes, size_t n) { return add_slice(b, AVR_KIND_CABAC_CODES, codes, n, 1, nullptr, 0); }
 
 #define AVR_STAGE(dst, src, n) do { if (int rc_ = stage_h2d(b, dst, src, n)) return rc_; } while (0)
 
-static int enqueue_lengths(avr_batch *b, uint32_t n32);
-static int enqueue_verify_k1(avr_batch *b, uint32_t n32, int form, const void *recs, const uint64_t *off, const uint32_t *order, bool again = false);
-static int reserve_restore(avr_batch *b, size_t n);
-static int stage_restore(avr_batch *b, size_t n);
-static int enqueue_restore(avr_batch *b, uint32_t n32);
-#ifdef AVR_TEST_HOOKS
-// Test build only (restore_flip, avr_internal.h): verify_flip in front of the restore check of a run's first pass -- not in front of
-// the one that follows K1p's second pass at avr_batch_wait, over the same bytes: the hook has had its turn.
-static int restore_flip_hook(avr_batch *b, uint32_t n32) {
-    if (const uint32_t k = avr::test_hooks().restore_flip; k && k <= n32) AVR_HIP(avr::launch_verify_flip(b->stream, b->d_out.p, b->d_out_off.p, k - 1));
+// The restore check's expectations.  staged_restore: what their offsets and lengths take of the arena; reserve_restore: decides whether
+// the run has the check (iff a slice has an expectation) and makes room; stage_restore: the expectations with their offsets and
+// lengths on their way to the device, among the run's other H2D copies.
+static size_t staged_restore(const avr_batch *b, size_t n) { return b->n_expect ? staged<uint64_t>(n) + staged<uint32_t>(n) : 0; }
+
+static int reserve_restore(avr_batch *b, size_t n) {
+    int rc = b->restorer.arm(b->n_expect > 0, n);
+    if (rc || !b->restorer.on) return rc;
+    b->expect_off.resize(n, 0);
+    b->expect_len.resize(n, AVR_EXPECT_NONE);
+    if ((rc = b->d_expect.reserve(b->expect_used + 8)) || (rc = b->d_expect_off.reserve(n)) || (rc = b->d_expect_len.reserve(n))) return rc;
     return AVR_OK;
 }
+
+static int stage_restore(avr_batch *b, size_t n) {
+    if (!b->restorer.on) return AVR_OK;
+    if (b->expect_used) AVR_HIP(hipMemcpyAsync(b->d_expect.p, b->h_expect.p, b->expect_used, hipMemcpyHostToDevice, b->stream));
+    AVR_STAGE(b->d_expect_off.p, b->expect_off.data(), n);
+    AVR_STAGE(b->d_expect_len.p, b->expect_len.data(), n);
+    return AVR_OK;
+}
+
+// What every run begins with: room for what every path has (`arena`: what the path stages of its own), which checks the run has
+// and room for their answers, the arena empty.
+static int begin_run(avr_batch *b, size_t n, size_t arena) {
+    int rc;
+    if ((rc = b->d_out_off.reserve(n + 1)) || (rc = b->d_dense_off.reserve(n + 1)) || (rc = b->d_n_bins.reserve(n)) ||
+        (rc = b->d_order.reserve(n)) || (rc = b->d_out_len.reserve(n)) || (rc = b->d_status.reserve(n)) ||
+        (rc = b->d_out.reserve(b->hp.out_off.back())) || (rc = b->h_out_len.reserve(n)) || (rc = b->h_status.reserve(n)) ||
+        (rc = b->h_plan.reserve(arena + staged_plan(b->hp) + staged_restore(b, n))))
+        return rc;
+    const bool verify = b->kind == AVR_KIND_RANGE ? b->verify : b->verify_k1;
+    if ((rc = b->verifier.arm(verify, n)) || (rc = b->est_checker.arm(verify && b->keys, n)) || (rc = reserve_restore(b, n))) return rc;
+    b->plan_used = 0;
+    return AVR_OK;
+}
+
+// lengths, statuses, final states and the checks' answers on their way to the host behind the kernels
+static int enqueue_lengths(avr_batch *b, uint32_t n32) {
+    const size_t n = n32, ns = b->n_states;
+    const bool with_states = b->kind == AVR_KIND_CABAC && ns;
+    hipStream_t s = b->stream;
+    AVR_HIP(hipEventRecord(b->ev[3], s));
+    AVR_HIP(hipMemcpyAsync(b->h_out_len.p, b->d_out_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    AVR_HIP(hipMemcpyAsync(b->h_status.p, b->d_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (with_states) AVR_HIP(hipMemcpyAsync(b->h_final.p, b->d_final.p, n * ns, hipMemcpyDeviceToHost, s));
+    for (Check *c : b->checks())
+        if (int rc = c->fetch(s, n)) return rc;
+    return AVR_OK;
+}
+
+// What follows the encode kernels of every path, in this order: the verifier of the batch's kind, the estimator checker, the restore
+// check -- each that the run has, between its two events -- and the lengths.
+// The verifier reads what that path's encoder read (b->coded).  K2: the range decoder over tiles or slice-major records.  K1: the
+// CABAC decoder over whatever form the records or codes have, with the encoder's final states where the kind has states.
+// The estimator checker holds the resolver's records to the key records and the tables, in the resolver's workspace (it is done with
+// it, and the checker's is no larger).
+// again: behind K1p's second pass at avr_batch_wait, over the same bytes.  The test build's hooks (verify_flip, restore_flip: a byte
+// of a slice's output complemented in front of a check's start event) have had their turn then.
+static int enqueue_checks(avr_batch *b, uint32_t n32, bool again = false) {
+    hipStream_t s = b->stream;
+    const avr_batch::Coded &c = b->coded;
+    int rc;
+    if (b->verifier.on) {
+#ifdef AVR_TEST_HOOKS
+        if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
 #endif
-// what the expectations' offsets and lengths take of the arena
-static size_t staged_restore(const avr_batch *b, size_t n) { return b->n_expect ? staged<uint64_t>(n) + staged<uint32_t>(n) : 0; }
+        if ((rc = b->verifier.start(s))) return rc;
+        if (b->kind == AVR_KIND_RANGE) {
+            AVR_HIP(avr::launch_range_verify(c.form != 0, s, c.recs, c.off, b->d_n_bins.p, c.order, n32, b->d_out.p, b->d_out_off.p, b->d_out_len.p,
+                                             b->d_status.p, b->verifier.d_first.p));
+        } else {
+            const bool states = c.form != avr::cabac_verify::kCodes;
+            AVR_HIP(avr::launch_cabac_verify(c.form, s, c.recs, c.off, b->d_n_bins.p, c.order, n32, states ? b->d_states.p : nullptr,
+                                             states ? uint32_t(b->n_states) : 0u, b->d_out.p, b->d_out_off.p, b->d_out_len.p,
+                                             states ? b->d_final.p : nullptr, b->d_status.p, b->verifier.d_first.p));
+        }
+        if ((rc = b->verifier.end(s))) return rc;
+    }
+    if (b->est_checker.on) {
+        if ((rc = b->est_checker.start(s))) return rc;
+        AVR_HIP(avr::launch_est_verify(s, b->d_keys.p, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p,
+                                       uint32_t(b->group_first.size()), b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p,
+                                       b->d_chunk_base.p, b->d_chunk_slice.p, b->hp.chunk_base.back(), avr::align256(b->d_est_ws.p),
+                                       b->d_status.p, b->est_checker.d_first.p));
+        if ((rc = b->est_checker.end(s))) return rc;
+    }
+    if (b->restorer.on) {                                        // (K1 only: a K2 batch takes no expectations)
+#ifdef AVR_TEST_HOOKS
+        if (const uint32_t k = avr::test_hooks().restore_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
+#endif
+        if ((rc = b->restorer.start(s))) return rc;
+        AVR_HIP(avr::launch_restore_check(s, b->d_out.p, b->d_out_off.p, b->d_out_len.p, n32, b->d_expect.p, b->d_expect_off.p, b->d_expect_len.p,
+                                          b->d_status.p, b->restorer.d_first.p));
+        if ((rc = b->restorer.end(s))) return rc;
+    }
+    return enqueue_lengths(b, n32);
+}
 
 // A batch of resolved codes: H2D of one byte per bin, K1p phases B-D (or the one-lane-per-slice coder), lengths back.
 static int submit_codes(avr_batch *b, uint32_t n32) {
@@ -518,23 +610,14 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     std::vector<uint32_t> order;
     if (!chunked) {
         std::vector<uint64_t> tile_off;
-        plan_tiles(b->n_bins, order, tile_off);                  // longest first: the lanes of a wave finish together
+        avr::plan_tiles(b->n_bins, order, tile_off);             // longest first: the lanes of a wave finish together
     }
-    const uint64_t total_codes = b->rec_off.back(), total_out = b->hp.out_off.back();
-    const size_t arena = staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) * 2 + staged_plan(b->hp) + staged_restore(b, n);    // rec_off, out_off, n_bins, order; the plan
+    const uint64_t total_codes = b->rec_off.back();
     int rc;
     if ((rc = b->d_recs.reserve((total_codes + 64) / 2 + 1)) || (rc = b->d_res_off.reserve(n + 1)) ||
-        (rc = b->d_out_off.reserve(n + 1)) || (rc = b->d_dense_off.reserve(n + 1)) || (rc = b->d_n_bins.reserve(n)) ||
-        (rc = b->d_order.reserve(n)) || (rc = b->d_out_len.reserve(n)) || (rc = b->d_status.reserve(n)) || (rc = b->d_out.reserve(total_out)) ||
-        (rc = b->h_out_len.reserve(n)) || (rc = b->h_status.reserve(n)) || (rc = b->h_plan.reserve(arena)))
+        (rc = begin_run(b, n, staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) * 2)))                   // rec_off, out_off, n_bins, order
         return rc;
-    b->verified = b->verify_k1;
-    if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
-    b->verified_est = b->verified && b->keys;
-    if (b->verified_est && ((rc = b->d_first_bad_est.reserve(n)) || (rc = b->h_first_bad_est.reserve(n)))) return rc;
-    if ((rc = reserve_restore(b, n))) return rc;
     hipStream_t s = b->stream;
-    b->plan_used = 0;
     b->hint_used = 0;
     AVR_HIP(hipEventRecord(b->ev[0], s));
     AVR_HIP(hipMemcpyAsync(b->d_recs.p, b->h_recs.p, total_codes, hipMemcpyHostToDevice, s));
@@ -544,7 +627,7 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     AVR_STAGE(b->d_out_off.p, b->hp.out_off.data(), n + 1);
     AVR_STAGE(b->d_n_bins.p, b->n_bins.data(), n);
     if (!chunked) AVR_STAGE(b->d_order.p, order.data(), n);
-    if (b->restored && (rc = stage_restore(b, n))) return rc;
+    if ((rc = stage_restore(b, n))) return rc;
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipEventRecord(b->ev[2], s));
@@ -557,16 +640,10 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
                                                b->d_out_off.p, b->d_out_len.p, b->d_status.p));
     }
     b->last_path = chunked;
-    if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kCodes, d_codes, b->d_res_off.p, chunked ? nullptr : b->d_order.p))) return rc;
-#ifdef AVR_TEST_HOOKS
-    if (b->restored && (rc = restore_flip_hook(b, n32))) return rc;
-#endif
-    if (b->restored && (rc = enqueue_restore(b, n32))) return rc;
-    return enqueue_lengths(b, n32);
+    b->coded = {avr::cabac_verify::kCodes, d_codes, b->d_res_off.p, chunked ? nullptr : b->d_order.p};
+    return enqueue_checks(b, n32);
 }
 
-// Everything of a run up to the lengths on their way back.  `use_hint`: size the kernels by the context count of this
-// object's previous run instead of asking the device and waiting (avr::DenseHint); avr_batch_wait checks the guess.
 // A batch of key records: the estimators of every group resolved on the device, d_keys -> d_recs (K2 range records with their
 // padding), the groups' tables after the run left in d_est_out.  Enqueues and returns.
 static int resolve_keys(avr_batch *b, uint32_t n32) {
@@ -590,73 +667,25 @@ static int resolve_keys(avr_batch *b, uint32_t n32) {
                                     b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, b->d_chunk_base.p,
                                     b->d_chunk_slice.p, total_chunks, avr::align256(b->d_est_ws.p), b->d_recs.p, b->d_status.p));
 #ifdef AVR_TEST_HOOKS
-    if (const uint32_t k = avr::test_hooks().est_flip; k && k <= n32 && b->verified)
+    if (const uint32_t k = avr::test_hooks().est_flip; k && k <= n32 && b->verifier.on)
         AVR_HIP(avr::launch_est_flip(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, k - 1, avr::test_hooks().est_flip_bin));
 #endif
     return AVR_OK;
 }
 
-// The estimator checker behind the K2 verifier of a run of key records, between events of its own: the resolver's records held to the
-// key records and the tables, in the resolver's workspace (it is done with it, and the checker's is no larger).
-static int enqueue_verify_est(avr_batch *b, uint32_t n32) {
-    hipStream_t s = b->stream;
-    AVR_HIP(hipEventRecord(b->eev[0], s));
-    AVR_HIP(avr::launch_est_verify(s, b->d_keys.p, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p,
-                                   uint32_t(b->group_first.size()), b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p,
-                                   b->d_chunk_base.p, b->d_chunk_slice.p, b->hp.chunk_base.back(), avr::align256(b->d_est_ws.p),
-                                   b->d_status.p, b->d_first_bad_est.p));
-    AVR_HIP(hipEventRecord(b->eev[1], s));
-    return AVR_OK;
-}
-
-// The verifier behind the encode kernels of a K2 run, between events of its own (the encode's slot of the timings ends at vev[0]).
-static int enqueue_verify(avr_batch *b, uint32_t n32, bool tiled) {
-    hipStream_t s = b->stream;
-    AVR_HIP(hipEventRecord(b->vev[0], s));
-#ifdef AVR_TEST_HOOKS
-    if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
-#endif
-    AVR_HIP(hipEventRecord(b->vev[1], s));
-    if (tiled)
-        AVR_HIP(avr::launch_range_verify(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
-                                         b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_first_bad.p));
-    else
-        AVR_HIP(avr::launch_range_verify(false, s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, nullptr, n32, b->d_out.p,
-                                         b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_first_bad.p));
-    AVR_HIP(hipEventRecord(b->vev[2], s));
-    return AVR_OK;
-}
-
-// The same behind the encode kernels of a K1 run: the CABAC decoder over whatever that path's encoder read -- `form` (cabac_verify::Form),
-// the records or codes at `recs` / `off`, `order` where the path has one -- with the encoder's final states where the kind has states.
-// again: behind K1p's second pass at avr_batch_wait, over the same bytes (the test build's hook has had its turn).
-static int enqueue_verify_k1(avr_batch *b, uint32_t n32, int form, const void *recs, const uint64_t *off, const uint32_t *order, bool again) {
-    hipStream_t s = b->stream;
-    const bool states = form != avr::cabac_verify::kCodes;
-    AVR_HIP(hipEventRecord(b->vev[0], s));
-#ifdef AVR_TEST_HOOKS
-    if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
-#endif
-    AVR_HIP(hipEventRecord(b->vev[1], s));
-    AVR_HIP(avr::launch_cabac_verify(form, s, recs, off, b->d_n_bins.p, order, n32, states ? b->d_states.p : nullptr, states ? uint32_t(b->n_states) : 0u,
-                                     b->d_out.p, b->d_out_off.p, b->d_out_len.p, states ? b->d_final.p : nullptr, b->d_status.p,
-                                     b->d_first_bad.p));
-    AVR_HIP(hipEventRecord(b->vev[2], s));
-    return AVR_OK;
-}
-
+// Everything of a run up to the lengths on their way back.  `use_hint`: size the kernels by the context count of this
+// object's previous run instead of asking the device and waiting (avr::DenseHint); avr_batch_wait checks the guess.
 static int submit_impl(avr_batch *b, bool use_hint) {
     const size_t n = b->n_bins.size();
     const uint32_t n32 = uint32_t(n);
     if (b->kind == AVR_KIND_CABAC_CODES) return submit_codes(b, n32);
     const size_t ns = b->n_states;
     const bool cabac = b->kind == AVR_KIND_CABAC;
-
-    std::vector<uint32_t> order;
-    std::vector<uint64_t> tile_off;
-    plan_tiles(b->n_bins, order, tile_off, b->recs8 ? 16 : 8);  // one-byte records: one-byte tiles (the chunked path has no tiles)
     const bool chunked = pick_chunked(b);
     b->last_path = chunked;
+    std::vector<uint32_t> order;
+    std::vector<uint64_t> tile_off(1, 0);
+    if (!chunked) avr::plan_tiles(b->n_bins, order, tile_off, b->recs8 ? 16 : 8);     // one-byte records: one-byte tiles (the chunked path has no tiles)
     // the chunk arrays once, whichever of the resolver and K2p reads them
     avr::fill_plan(b->hp, b->n_bins.data(), n,
                    chunked && cabac ? avr::PlanFor::K1p : chunked || b->keys ? avr::PlanFor::Chunks : avr::PlanFor::Serial);
@@ -664,28 +693,18 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     const size_t n_tiles = tile_off.size() - 1;
 
     int rc;
-    if ((b->recs8 ? (rc = b->d_recs8.reserve(total_recs + 16)) : (rc = b->d_recs.reserve(total_recs))) || (!chunked && (rc = b->d_tiles.reserve(total_chunks))) ||
-        (rc = b->d_rec_off.reserve(n + 1)) || (rc = b->d_tile_off.reserve(n_tiles + 1)) ||
-        (rc = b->d_out_off.reserve(n + 1)) || (rc = b->d_dense_off.reserve(n + 1)) ||
-        (rc = b->d_n_bins.reserve(n)) || (rc = b->d_order.reserve(n)) || (rc = b->d_out_len.reserve(n)) ||
-        (rc = b->d_status.reserve(n)) || (rc = b->d_out.reserve(total_out)) ||
-        (rc = b->h_out_len.reserve(n)) || (rc = b->h_status.reserve(n)) || (rc = b->h_ndense.reserve(16)))
+    if ((b->recs8 ? (rc = b->d_recs8.reserve(total_recs + 16)) : (rc = b->d_recs.reserve(total_recs))) ||
+        (!chunked && ((rc = b->d_tiles.reserve(total_chunks)) || (rc = b->d_tile_off.reserve(n_tiles + 1)))) ||
+        (rc = b->d_rec_off.reserve(n + 1)) || (rc = b->h_ndense.reserve(16)) || (b->keys && (rc = b->d_keys.reserve(total_recs))))
         return rc;
     if (cabac && ((rc = b->d_states.reserve(n * std::max<size_t>(ns, 1))) || (rc = b->d_final.reserve(n * std::max<size_t>(ns, 1))) ||
                   (rc = b->h_final.reserve(n * std::max<size_t>(ns, 1)))))
         return rc;
-    // rec_off, out_off, n_bins; tile_off, order; group_first; the plan's arrays
-    if ((rc = b->h_plan.reserve(staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) + (chunked ? 0 : staged<uint64_t>(n_tiles + 1) + staged<uint32_t>(n)) +
-                                (b->keys ? staged<uint32_t>(b->group_first.size() + 1) : 0) + staged_plan(b->hp) + staged_restore(b, n)))) return rc;
-    if (b->keys && (rc = b->d_keys.reserve(total_recs))) return rc;
-    b->verified = cabac ? b->verify_k1 : b->verify;
-    if (b->verified && ((rc = b->d_first_bad.reserve(n)) || (rc = b->h_first_bad.reserve(n)))) return rc;
-    b->verified_est = b->verified && b->keys;
-    if (b->verified_est && ((rc = b->d_first_bad_est.reserve(n)) || (rc = b->h_first_bad_est.reserve(n)))) return rc;
-    if ((rc = reserve_restore(b, n))) return rc;
+    // rec_off, out_off, n_bins; tile_off, order; group_first
+    if ((rc = begin_run(b, n, staged<uint64_t>(n + 1) * 2 + staged<uint32_t>(n) + (chunked ? 0 : staged<uint64_t>(n_tiles + 1) + staged<uint32_t>(n)) +
+                                  (b->keys ? staged<uint32_t>(b->group_first.size() + 1) : 0)))) return rc;
 
     hipStream_t s = b->stream;
-    b->plan_used = 0;
     const avr::DenseHint hint{use_hint ? std::min<uint32_t>(b->dense_hint, uint32_t(ns)) : 0u, b->h_ndense.p, b->h_ndense.p + 1};
     b->hint_used = hint.rows;
     b->h_ndense.p[0] = b->h_ndense.p[1] = 0;
@@ -704,7 +723,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         AVR_STAGE(b->d_order.p, order.data(), n);
     }
     if (cabac && ns) AVR_HIP(hipMemcpyAsync(b->d_states.p, b->h_states.p, n * ns, hipMemcpyHostToDevice, s));
-    if (b->restored && (rc = stage_restore(b, n))) return rc;
+    if ((rc = stage_restore(b, n))) return rc;
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
     // Both K1 paths renumber a two-byte batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
@@ -721,8 +740,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         AVR_HIP(hipEventRecord(b->ev[2], s));
         AVR_HIP(avr::launch_k2p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_chunk_base.p, b->d_chunk_slice.p,
                                 plan.total_chunks, total_out, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-        if (b->verified && (rc = enqueue_verify(b, n32, false))) return rc;      // over the slice-major records K2p read
-        if (b->verified_est && (rc = enqueue_verify_est(b, n32))) return rc;
+        b->coded = {0, b->d_recs.p, b->d_rec_off.p, nullptr};                    // the slice-major records K2p read
     } else if (chunked) {
         b->plan = plan;
         AVR_HIP(hipEventRecord(b->ev[2], s));
@@ -732,9 +750,9 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         else
             AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
                                     avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}, &hint));
-        // over the slice-major records K1p read, in the caller's numbering: the census, the dense map and the chains are checked with the bytes
-        if (b->verified && (rc = b->recs8 ? enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices8, b->d_recs8.p, b->d_rec_off.p, nullptr)
-                                          : enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr))) return rc;
+        // the slice-major records K1p read, in the caller's numbering: the census, the dense map and the chains are checked with the bytes
+        if (b->recs8) b->coded = {avr::cabac_verify::kSlices8, b->d_recs8.p, b->d_rec_off.p, nullptr};
+        else b->coded = {avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr};
     } else {
         if (b->recs8)                                            // one-byte records validated and transposed in one pass, as they are
             AVR_HIP(avr::launch_pack_tiles8_narrow(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
@@ -753,68 +771,14 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         else
             AVR_HIP(avr::launch_range_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
                                              b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-        if (b->verified && cabac)                                // over the tiles the encoder read
-            rc = enqueue_verify_k1(b, n32, b->recs8 ? avr::cabac_verify::kTiles8 : avr::cabac_verify::kTiles2, b->d_tiles.p, b->d_tile_off.p, b->d_order.p);
-        else if (b->verified) rc = enqueue_verify(b, n32, true);
-        if (rc) return rc;
-        if (b->verified_est && (rc = enqueue_verify_est(b, n32))) return rc;
+        // the tiles the encoder read
+        b->coded = {cabac ? (b->recs8 ? avr::cabac_verify::kTiles8 : avr::cabac_verify::kTiles2) : 1, b->d_tiles.p, b->d_tile_off.p, b->d_order.p};
     }
-#ifdef AVR_TEST_HOOKS
-    if (b->restored && (rc = restore_flip_hook(b, n32))) return rc;
-#endif
-    if (b->restored && (rc = enqueue_restore(b, n32))) return rc;    // (K1 only: a K2 batch takes no expectations)
-    return enqueue_lengths(b, n32);
-}
-
-// The restore check of a K1 run.  reserve_restore: decides whether the run has it (iff a slice has an expectation) and makes room;
-// stage_restore: the expectations with their offsets and lengths on their way to the device, among the run's other H2D copies;
-// enqueue_restore: the check behind the encode of whichever path ran -- behind the K1 verifier where that is on -- between its two events.
-static int reserve_restore(avr_batch *b, size_t n) {
-    b->restored = b->n_expect > 0;
-    if (!b->restored) return AVR_OK;
-    b->expect_off.resize(n, 0);
-    b->expect_len.resize(n, AVR_EXPECT_NONE);
-    int rc;
-    if ((rc = b->d_expect.reserve(b->expect_used + 8)) || (rc = b->d_expect_off.reserve(n)) || (rc = b->d_expect_len.reserve(n)) ||
-        (rc = b->d_first_diff.reserve(n)) || (rc = b->h_first_diff.reserve(n)))
-        return rc;
-    return AVR_OK;
-}
-
-static int stage_restore(avr_batch *b, size_t n) {
-    if (b->expect_used) AVR_HIP(hipMemcpyAsync(b->d_expect.p, b->h_expect.p, b->expect_used, hipMemcpyHostToDevice, b->stream));
-    AVR_STAGE(b->d_expect_off.p, b->expect_off.data(), n);
-    AVR_STAGE(b->d_expect_len.p, b->expect_len.data(), n);
-    return AVR_OK;
-}
-
-static int enqueue_restore(avr_batch *b, uint32_t n32) {
-    hipStream_t s = b->stream;
-    AVR_HIP(hipEventRecord(b->rev[0], s));
-    AVR_HIP(avr::launch_restore_check(s, b->d_out.p, b->d_out_off.p, b->d_out_len.p, n32, b->d_expect.p, b->d_expect_off.p, b->d_expect_len.p,
-                                      b->d_status.p, b->d_first_diff.p));
-    AVR_HIP(hipEventRecord(b->rev[1], s));
-    return AVR_OK;
-}
-
-// lengths, statuses and final states on their way to the host behind the kernels
-static int enqueue_lengths(avr_batch *b, uint32_t n32) {
-    const size_t n = n32, ns = b->n_states;
-    const bool with_states = b->kind == AVR_KIND_CABAC && ns;
-    hipStream_t s = b->stream;
-    AVR_HIP(hipEventRecord(b->ev[3], s));
-    AVR_HIP(hipMemcpyAsync(b->h_out_len.p, b->d_out_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    AVR_HIP(hipMemcpyAsync(b->h_status.p, b->d_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (with_states) AVR_HIP(hipMemcpyAsync(b->h_final.p, b->d_final.p, n * ns, hipMemcpyDeviceToHost, s));
-    if (b->verified) AVR_HIP(hipMemcpyAsync(b->h_first_bad.p, b->d_first_bad.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (b->verified_est) AVR_HIP(hipMemcpyAsync(b->h_first_bad_est.p, b->d_first_bad_est.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (b->restored) AVR_HIP(hipMemcpyAsync(b->h_first_diff.p, b->d_first_diff.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    return AVR_OK;
+    return enqueue_checks(b, n32);
 }
 
 int avr_batch_submit(avr_batch *b) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
+    if (int rc = check_idle(b)) return rc;
     if (int rc = select_device(b->device)) return rc;
     b->ran = false;                                              // a batch may be submitted again after avr_batch_wait: same slices, coded anew
     const size_t n = b->n_bins.size();
@@ -823,7 +787,7 @@ int avr_batch_submit(avr_batch *b) {
         return fail(AVR_ERR_INVALID, "verification exists for the compress direction only: not for a K1 batch");
     if (b->verify_k1 && b->kind == AVR_KIND_RANGE)
         return fail(AVR_ERR_INVALID, "K1 verification exists for the decompress direction only: not for a K2 batch");
-    b->verified = b->verified_est = b->restored = false;
+    for (Check *c : b->checks()) (void)c->arm(false, 0);
     if (n == 0) { b->in_flight = true; return AVR_OK; }
     const bool use_hint = b->dense_hint > 0 && !avr::no_hint();
     if (int rc = submit_impl(b, use_hint)) { (void)hipStreamSynchronize(b->stream); return rc; }
@@ -844,7 +808,6 @@ int avr_batch_wait(avr_batch *b) {
     int rc;
     AVR_HIP(hipStreamSynchronize(s));
     b->info[0] = uint32_t(b->last_path); b->info[1] = b->info[2] = b->info[3] = 0;
-    float verify_before = 0, restore_before = 0;                 // of the verifier and the restore check in front of K1p's second pass, where there is one
     if (b->kind == AVR_KIND_CABAC) {
         // The run was sized by a guess of the context count.  The one-lane-per-slice kernel is exact whatever the
         // guess; the intra-slice parallel kernels only if the batch needs no more rows than guessed: else once more,
@@ -856,13 +819,12 @@ int avr_batch_wait(avr_batch *b) {
             b->info[3] = 1;
         }
         if (b->last_path == 1 && b->h_ndense.p[1]) {             // slices with a context the sampled census missed: their second pass
-            if (b->verified || b->restored) {
+            if (b->verifier.on || b->restorer.on) {
                 // The verifier has run in front of this pass, and the pass treats a slice it marked AVR_SLICE_VERIFY_FAILED like one with a bad
                 // record (length 0).  Such a slice goes in as AVR_SLICE_OK -- finished, so the pass leaves it alone -- and the verifier behind
                 // the pass, which decodes every slice again, fails it again at the same bin.  (h_status is the device's, behind a synchronise.)
                 // The same holds for the restore check and its findings.
-                if (b->verified) (void)hipEventElapsedTime(&verify_before, b->vev[1], b->vev[2]);
-                if (b->restored) (void)hipEventElapsedTime(&restore_before, b->rev[0], b->rev[1]);
+                for (Check *c : b->checks()) c->carry();
                 bool any = false;
                 for (size_t i = 0; i < n; i++)
                     if (b->h_status.p[i] == AVR_SLICE_VERIFY_FAILED) { b->h_status.p[i] = AVR_SLICE_OK; any = true; }
@@ -870,10 +832,8 @@ int avr_batch_wait(avr_batch *b) {
             }
             AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(b->n_states), &b->plan, avr::align256(b->d_workspace.p),
                                           avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
-            // the verifier skipped the slices of this pass (their status was not AVR_SLICE_OK yet): once more behind it
-            if (b->verified && (rc = enqueue_verify_k1(b, n32, avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr, true))) return rc;
-            if (b->restored && (rc = enqueue_restore(b, n32))) return rc;        // ... and the restore check, for the same reason
-            if ((rc = enqueue_lengths(b, n32))) return rc;
+            // the verifier and the restore check skipped the slices of this pass (their status was not AVR_SLICE_OK yet): once more behind it
+            if ((rc = enqueue_checks(b, n32, true))) return rc;
             AVR_HIP(hipStreamSynchronize(s));
             b->info[3] |= 2;
         }
@@ -894,27 +854,18 @@ int avr_batch_wait(avr_batch *b) {
     AVR_HIP(hipEventRecord(b->ev[4], s));
     AVR_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&b->ms[i], b->ev[i], b->ev[i + 1]);
-    b->verify_ms = 0;
-    if (b->verified) {                                           // the encode's slot ends where the verifier's events begin
-        (void)hipEventElapsedTime(&b->ms[2], b->ev[2], b->vev[0]);
-        (void)hipEventElapsedTime(&b->verify_ms, b->vev[1], b->vev[2]);
-        // Behind K1p's second pass (rare) vev[0] was recorded again: the span from ev[2] then also holds the first verifier, taken off
-        // here, and what lay between the two runs -- the host's wait, the status and length copies -- which stays in: on that path
-        // ms[2] is an upper bound of the encode, not the encode alone.
-        b->ms[2] -= verify_before + restore_before;
-        b->verify_ms += verify_before;
+    // The encode's slot ends where the first check the run has starts, as last recorded.  Behind K1p's second pass (rare) that is the
+    // check's second recording: the span from ev[2] then also holds the checks' first runs, taken off here, and what lay between the
+    // two -- the host's wait, the status and length copies -- which stays in: on that path ms[2] is an upper bound of the encode, not
+    // the encode alone.
+    bool first = true;
+    for (Check *c : b->checks()) {
+        c->finish();
+        if (!c->on) continue;
+        if (first) (void)hipEventElapsedTime(&b->ms[2], b->ev[2], c->ev[0]);
+        first = false;
+        b->ms[2] -= c->before;
     }
-    b->restore_ms = 0;
-    if (b->restored) {                                           // without a verifier in front of it the check's first event ends the encode's slot
-        if (!b->verified) {
-            (void)hipEventElapsedTime(&b->ms[2], b->ev[2], b->rev[0]);
-            b->ms[2] -= restore_before;                          // (behind K1p's second pass: as above, an upper bound of the encode)
-        }
-        (void)hipEventElapsedTime(&b->restore_ms, b->rev[0], b->rev[1]);
-        b->restore_ms += restore_before;
-    }
-    b->verify_est_ms = 0;
-    if (b->verified_est) (void)hipEventElapsedTime(&b->verify_est_ms, b->eev[0], b->eev[1]);
     b->ran = true;                                               // only now: the getters hand out h_out / h_status
     return AVR_OK;
 }
@@ -927,8 +878,7 @@ int avr_batch_run(avr_batch *b) {
 }
 
 int avr_batch_get(avr_batch *b, size_t slice, const uint8_t **bytes, size_t *len, int *status) {
-    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
-    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
+    if (int rc = check_slice(b, slice)) return rc;
     if (bytes) *bytes = b->h_out.p + b->dense_off[slice];
     if (len) *len = size_t(b->dense_off[slice + 1] - b->dense_off[slice]);
     if (status) *status = b->h_status.p[slice];
@@ -936,16 +886,16 @@ int avr_batch_get(avr_batch *b, size_t slice, const uint8_t **bytes, size_t *len
 }
 
 int avr_batch_get_states(avr_batch *b, size_t slice, const uint8_t **states, size_t *n_states) {
-    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (int rc = check_ran(b)) return rc;
     if (b->kind != AVR_KIND_CABAC) return fail(AVR_ERR_INVALID, "not a CABAC batch");
-    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
+    if (int rc = check_slice(b, slice)) return rc;
     if (states) *states = b->h_final.p + slice * b->n_states;
     if (n_states) *n_states = b->n_states;
     return AVR_OK;
 }
 
 int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg, size_t *n_keys) {
-    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (int rc = check_ran(b)) return rc;
     if (!b->keys) return fail(AVR_ERR_INVALID, "not a batch of key records");
     if (group >= b->group_first.size()) return fail(AVR_ERR_INVALID, "group %zu out of range", group);
     if (!b->est_out_fetched) {                                   // on first use: most callers want the table of a file's last batch only
@@ -962,90 +912,64 @@ int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg
 }
 
 int avr_batch_run_info(avr_batch *b, uint32_t info[4]) {
-    if (!b || !b->ran || !info) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (int rc = check_ran(b, info != nullptr)) return rc;
     memcpy(info, b->info, sizeof b->info);
     return AVR_OK;
 }
 
 int avr_batch_timings(avr_batch *b, float ms[4]) {
-    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
+    if (int rc = check_ran(b, ms != nullptr)) return rc;
     memcpy(ms, b->ms, sizeof b->ms);
     return AVR_OK;
 }
 
 int avr_batch_set_verify(avr_batch *b, int on) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
-    if (on && !b->vev[0]) {
-        if (int rc = select_device(b->device)) return rc;
-        for (auto &e : b->vev) AVR_HIP(hipEventCreate(&e));
-    }
-    if (on && !b->eev[0]) {
-        if (int rc = select_device(b->device)) return rc;
-        for (auto &e : b->eev) AVR_HIP(hipEventCreate(&e));
-    }
+    int rc = check_idle(b);
+    if (rc || (on && ((rc = b->verifier.make_events(b->device)) || (rc = b->est_checker.make_events(b->device))))) return rc;
     b->verify = on != 0;
     return AVR_OK;
 }
 
 int avr_batch_set_verify_k1(avr_batch *b, int on) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
-    if (on && !b->vev[0]) {
-        if (int rc = select_device(b->device)) return rc;
-        for (auto &e : b->vev) AVR_HIP(hipEventCreate(&e));
-    }
+    int rc = check_idle(b);
+    if (rc || (on && (rc = b->verifier.make_events(b->device)))) return rc;
     b->verify_k1 = on != 0;
     return AVR_OK;
 }
 
-int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad) {
-    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
-    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
-    if (first_bad) *first_bad = b->verified ? b->h_first_bad.p[slice] : AVR_VERIFY_NONE;
+// a check's answer for one slice (AVR_VERIFY_NONE where the run did not have the check), and what the check took
+static int check_answer(const avr_batch *b, Check avr_batch::*which, size_t slice, uint32_t *first) {
+    if (int rc = check_slice(b, slice)) return rc;
+    if (first) *first = (b->*which).answer(slice);
     return AVR_OK;
 }
-
-int avr_batch_verify_ms(avr_batch *b, float *ms) {
-    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
-    *ms = b->verify_ms;
+static int check_ms(const avr_batch *b, Check avr_batch::*which, float *ms) {
+    if (int rc = check_ran(b, ms != nullptr)) return rc;
+    *ms = (b->*which).ms;
     return AVR_OK;
 }
-
-int avr_batch_get_verify_est(avr_batch *b, size_t slice, uint32_t *first_bad) {
-    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
-    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
-    if (first_bad) *first_bad = b->verified_est ? b->h_first_bad_est.p[slice] : AVR_VERIFY_NONE;
-    return AVR_OK;
-}
-
-int avr_batch_verify_est_ms(avr_batch *b, float *ms) {
-    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
-    *ms = b->verify_est_ms;
-    return AVR_OK;
-}
+int avr_batch_get_verify(avr_batch *b, size_t slice, uint32_t *first_bad) { return check_answer(b, &avr_batch::verifier, slice, first_bad); }
+int avr_batch_verify_ms(avr_batch *b, float *ms) { return check_ms(b, &avr_batch::verifier, ms); }
+int avr_batch_get_verify_est(avr_batch *b, size_t slice, uint32_t *first_bad) { return check_answer(b, &avr_batch::est_checker, slice, first_bad); }
+int avr_batch_verify_est_ms(avr_batch *b, float *ms) { return check_ms(b, &avr_batch::est_checker, ms); }
+int avr_batch_get_restore(avr_batch *b, size_t slice, uint32_t *first_diff) { return check_answer(b, &avr_batch::restorer, slice, first_diff); }
+int avr_batch_restore_ms(avr_batch *b, float *ms) { return check_ms(b, &avr_batch::restorer, ms); }
 
 int avr_batch_expect(avr_batch *b, size_t slice, const uint8_t *bytes, size_t len) {
-    if (!b) return fail(AVR_ERR_INVALID, "null batch");
-    if (b->in_flight) return fail(AVR_ERR_INVALID, "batch is in flight; call avr_batch_wait first");
-    if (b->ran) return fail(AVR_ERR_INVALID, "batch already ran; call avr_batch_reset first");
+    if (int rc = check_open(b)) return rc;
     if (b->kind == AVR_KIND_RANGE) return fail(AVR_ERR_INVALID, "the restore check exists for K1 batches only: not for a K2 batch");
     if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu has not been added", slice);
     if (len >= 0xffffffffull) return fail(AVR_ERR_INVALID, "expectation too long");
     if (!bytes && len) return fail(AVR_ERR_INVALID, "null bytes");
     if (slice < b->expect_len.size() && b->expect_len[slice] != AVR_EXPECT_NONE)
         return fail(AVR_ERR_INVALID, "slice %zu has an expectation already", slice);
-    if (!b->rev[0]) {
-        if (int rc = select_device(b->device)) return rc;
-        for (auto &e : b->rev) AVR_HIP(hipEventCreate(&e));
-    }
+    if (int rc = b->restorer.make_events(b->device)) return rc;
     const size_t padded = (len + 7) & ~size_t(7), need = b->expect_used + padded;
-    if (need > b->h_expect.cap) {                                // grown with what it holds (PinBuf::reserve keeps nothing)
+    if (need > b->h_expect.cap) {                                // grown with what it holds (reserve keeps nothing)
         PinBuf<uint8_t> grown;
         if (int rc = grown.reserve(std::max(need, 2 * b->h_expect.cap))) return rc;
         if (b->expect_used) memcpy(grown.p, b->h_expect.p, b->expect_used);
-        b->h_expect.release();
-        b->h_expect = grown;
+        b->h_expect = std::move(grown);
     }
     uint8_t *dst = b->h_expect.p + b->expect_used;
     if (len) memcpy(dst, bytes, len);
@@ -1056,19 +980,6 @@ int avr_batch_expect(avr_batch *b, size_t slice, const uint8_t *bytes, size_t le
     b->expect_len[slice] = uint32_t(len);
     b->expect_used = need;
     b->n_expect++;
-    return AVR_OK;
-}
-
-int avr_batch_get_restore(avr_batch *b, size_t slice, uint32_t *first_diff) {
-    if (!b || !b->ran) return fail(AVR_ERR_INVALID, "batch has not run");
-    if (slice >= b->n_bins.size()) return fail(AVR_ERR_INVALID, "slice %zu out of range", slice);
-    if (first_diff) *first_diff = b->restored ? b->h_first_diff.p[slice] : AVR_VERIFY_NONE;
-    return AVR_OK;
-}
-
-int avr_batch_restore_ms(avr_batch *b, float *ms) {
-    if (!b || !b->ran || !ms) return fail(AVR_ERR_INVALID, "batch has not run");
-    *ms = b->restore_ms;
     return AVR_OK;
 }
 
@@ -1141,8 +1052,7 @@ int avr_multi_add_slice_cabac(avr_multi *m, const uint16_t *recs, size_t n, cons
 int avr_multi_add_slice_range(avr_multi *m, const uint16_t *recs, size_t n) { return multi_add(m, AVR_KIND_RANGE, recs, n, 2, nullptr, 0); }
 int avr_multi_add_slice_codes(avr_multi *m, const uint8_t *codes, size_t n) { return multi_add(m, AVR_KIND_CABAC_CODES, codes, n, 1, nullptr, 0); }
 int avr_multi_add_slice_cabac8(avr_multi *m, const uint8_t *recs8, size_t n, const uint8_t *init_states, size_t n_states) {
-    if (n_states > AVR_MAX_STATES8)                              // (first: what needs no batch is checked without one)
-        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    if (int rc = check_states8(n_states)) return rc;             // (first: what needs no batch is checked without one)
     return multi_add(m, AVR_KIND_CABAC8, recs8, n, 1, init_states, n_states);
 }
 
@@ -1239,8 +1149,7 @@ int avr_pack_tiles_device(int device, void *stream, int kind, size_t n_states, c
 // one-byte records: what the host can check of the layout -- the base 16-byte aligned, the offsets' array 8-byte aligned (the offsets
 // themselves live on the device, where the kernels flag a slice whose offset is not a multiple of 16)
 static int check_recs8(const uint8_t *recs8, const uint64_t *rec_off, size_t n_states) {
-    if (n_states > AVR_MAX_STATES8)
-        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    if (int rc = check_states8(n_states)) return rc;
     if (reinterpret_cast<uintptr_t>(recs8) & 15) return fail(AVR_ERR_INVALID, "recs8 is not 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(rec_off) & 7) return fail(AVR_ERR_INVALID, "rec_off is not 8-byte aligned");
     return AVR_OK;
@@ -1275,8 +1184,7 @@ int avr_cabac8_encode_tiles_device(int device, void *stream, const void *tiles, 
                                    const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                    uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states) {
     if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES8)
-        return fail(AVR_ERR_INVALID, "n_states %zu > %d: one-byte records name at most %d contexts", n_states, AVR_MAX_STATES8, AVR_MAX_STATES8);
+    if (int rc = check_states8(n_states)) return rc;
     if (n_slices && (!tiles || !out || !out_len || !status || (n_states && !init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
     if (reinterpret_cast<uintptr_t>(tiles) & 15) return fail(AVR_ERR_INVALID, "tiles is not 16-byte aligned");
     if (int rc = select_device(device)) return rc;

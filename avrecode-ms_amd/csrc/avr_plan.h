@@ -1,9 +1,11 @@
 // What a batch's slice lengths decide before anything is laid out (csrc/avr_layout.h takes these as its inputs): the arrays of an
-// avr_chunk_plan, the slices' output regions, and whether the batch goes through the intra-slice parallel kernels.  Each rule is
+// avr_chunk_plan, the slices' output regions, the tiles, and whether the batch goes through the intra-slice parallel kernels.  Each rule is
 // written ONCE here; the kernels index chunk_slice[], res_off[] and dig_off[] unchecked, so these rules keep them inside their
 // buffers.  Python twin: chunk_plan_arrays() in avrecode-ms_amd/device.py; tests/test_plan.py holds the two to each other and to
 // recorded numbers.  Host only, plain C++17, no HIP header: tests/plan_check.cpp compiles it alone.
 #pragma once
+#include <algorithm>
+#include <numeric>
 #include <vector>
 
 #include "avr_layout.h"
@@ -58,6 +60,25 @@ inline void fill_plan(HostPlan &p, const uint32_t *n_bins, size_t n, PlanFor pat
         p.res_off[i + 1] = p.res_off[i] + slice_work_bytes(nb);
         p.blk_base[i + 1] = p.blk_base[i] + nk;
         p.blk_slice.insert(p.blk_slice.end(), nk, uint32_t(i));
+    }
+}
+
+// The tiles of the one-lane-per-slice paths: slices are processed longest first (stable: equal lengths keep the caller's order), 64 to
+// a tile, and a tile is as long as its first -- its longest -- slice.  tile_off: n_tiles + 1 offsets in 16-byte chunks.
+// records_per_chunk: 8 for two-byte records, 16 for one-byte tiles (k_pack_tiles8_narrow).  Python twin: plan_tiles() in
+// avrecode-ms_amd/device.py; tests/test_plan.py holds the two to each other.  (static: the sort's instantiations stay out of the
+// library's exported symbols.)
+static inline void plan_tiles(const std::vector<uint32_t> &n_bins, std::vector<uint32_t> &order, std::vector<uint64_t> &tile_off,
+                              uint32_t records_per_chunk = 8) {
+    const size_t n = n_bins.size();
+    order.resize(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return n_bins[a] > n_bins[b]; });
+    const size_t n_tiles = (n + 63) / 64;
+    tile_off.assign(n_tiles + 1, 0);
+    for (size_t t = 0; t < n_tiles; t++) {
+        const uint64_t chunks = (uint64_t(n_bins[order[t * 64]]) + records_per_chunk - 1) / records_per_chunk;   // sorted: first lane is the longest
+        tile_off[t + 1] = tile_off[t] + chunks * 64;
     }
 }
 

@@ -26,7 +26,7 @@ def plan_tiles(n_bins, records_per_chunk=8):
     Slices are processed longest first, 64 per tile (one wave); a tile is as long as its
     longest slice.  Returns (order int32[n], tile_off int64[n_tiles+1] in 16-byte chunks).
     records_per_chunk: 8 for two-byte records, 16 for one-byte tiles (avr_pack_tiles8_narrow_device).
-    Same plan as plan_tiles() in csrc/avr_api.cpp.
+    Same plan as plan_tiles() in csrc/avr_plan.h (tests/test_plan.py holds the two to each other).
     """
     import torch
     n = n_bins.numel()

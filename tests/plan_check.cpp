@@ -1,10 +1,12 @@
 // The plan rules of csrc/avr_plan.h, printed: the header compiled alone by g++ (no HIP), driven by tests/test_plan.py.
-// stdin, a line each:   "plan k nb_0 ... nb_(k-1)"   or   "big k nb_0 ... nb_(k-1)"   or   "path n_slices total_bins".
+// stdin, a line each:   "plan k nb_0 ... nb_(k-1)"   or   "big k nb_0 ... nb_(k-1)"   or   "path n_slices total_bins"   or
+// "tiles records_per_chunk k nb_0 ... nb_(k-1)".
 // stdout for a plan: the per-slice values (chunks, blocks, work, digits, out), then every array of the K1p plan by name; and a line
 // "lesser" telling whether the lesser paths (Serial, Chunks, Codes) build the same arrays and leave the others empty.
 // stdout for "big" (slices of up to 2^32 - 1 bins: millions of chunks): the same without the per-chunk arrays, of which a line
 // "slices" gives the two sizes and whether every entry is the slice whose range of chunk_base / blk_base holds it.
 // stdout for a path: "path 0" or "path 1" (want_chunked).
+// stdout for tiles: "order" and "tile_off" of plan_tiles.
 #include <inttypes.h>
 #include <stdio.h>
 #include <string.h>
@@ -30,6 +32,18 @@ int main() {
             uint64_t n_slices, total_bins;
             if (scanf("%" SCNu64 " %" SCNu64, &n_slices, &total_bins) != 2) return 1;
             printf("path %d\n", int(want_chunked(size_t(n_slices), total_bins)));
+            continue;
+        }
+        if (!strcmp(what, "tiles")) {
+            uint32_t per_chunk;
+            uint64_t k;
+            if (scanf("%" SCNu32 " %" SCNu64, &per_chunk, &k) != 2) return 1;
+            std::vector<uint32_t> nb(k), order;
+            std::vector<uint64_t> tile_off;
+            for (auto &x : nb)
+                if (scanf("%" SCNu32, &x) != 1) return 1;
+            plan_tiles(nb, order, tile_off, per_chunk);
+            line("order", order); line("tile_off", tile_off);
             continue;
         }
         uint64_t k;

@@ -396,6 +396,8 @@ def test_the_second_pass_from_wait_is_verified_too(avr, oracle, hooks):
             for i in range(1, 5):
                 assert (b.get(i), b.get_states(i), b.get_verify(i)) == ((want[i][0], 0), want[i][1], VERIFY_NONE), f"run {run} slice {i}"
             assert b.verify_ms() > 0.0
+            t = b.timings()                                      # the second pass: the verifier in front of it is taken off the encode's slot
+            assert all(v >= 0.0 for v in t.values()) and t["encode_ms"] > 0.0, t
 
 
 def test_batch_verify_k1_refusals(avr):

@@ -404,6 +404,8 @@ def test_a_batch_that_wait_runs_again_is_checked_again(avr, oracle, hooks):
                     assert b.get(i) == (want[i][0], VERIFY_FAILED if i == 1 else OK) and b.get_states(i) == want[i][1], f"batch {k} slice {i}"
                     assert b.get_restore(i) == (100 if i == 1 else VERIFY_NONE) and b.get_verify(i) == VERIFY_NONE
                 assert b.restore_ms() > 0.0 and (b.verify_ms() > 0.0) == verify_k1
+                t = b.timings()
+                assert all(v >= 0.0 for v in t.values()) and t["encode_ms"] > 0.0, t
 
 
 def test_the_second_pass_from_wait_is_checked_too(avr, oracle, hooks):
@@ -435,6 +437,8 @@ def test_the_second_pass_from_wait_is_checked_too(avr, oracle, hooks):
                     assert (b.get(i), b.get_states(i)) == ((want[i][0], VERIFY_FAILED if i == bad_slice else OK), want[i][1]), f"run {run} slice {i}"
                     assert b.get_restore(i) == (7 if i == bad_slice else VERIFY_NONE) and b.get_verify(i) == VERIFY_NONE
                 assert b.restore_ms() > 0.0 and (b.verify_ms() > 0.0) == verify_k1
+                t = b.timings()                                  # the second pass: the checks in front of it are taken off the encode's slot
+                assert all(v >= 0.0 for v in t.values()) and t["encode_ms"] > 0.0, t
 
 
 # ------------------------------------------------------------------ 7. the command line

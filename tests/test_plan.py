@@ -1,5 +1,5 @@
 """What a batch's slice lengths decide -- the arrays of an avr_chunk_plan, the output regions, the choice of path -- is written once
-in C++ (csrc/avr_plan.h) and once in Python (chunk_plan_arrays in avrecode_ms_amd/device.py).  tests/plan_check.cpp compiles the
+in C++ (csrc/avr_plan.h) and once in Python (chunk_plan_arrays and plan_tiles in avrecode_ms_amd/device.py).  tests/plan_check.cpp compiles the
 header with g++ alone and prints every array for lists of lengths; here the two are held to each other element for element, to the
 numbers below (worked out by hand from the rules as they stood, spread over csrc/avr_api.cpp, before the header existed) and to
 plan_totals() of tests/test_layouts.py, a third statement of the rules.  The kernels index these arrays unchecked.  No device needed."""
@@ -94,6 +94,24 @@ def test_cpp_against_python(plan_check, which):
         assert tensor.tolist() == p[name], name
     assert list(totals) == p["totals"] and p["lesser"] == [1]
     assert p["out_off"][-1] == sum((x + 16 + 7) // 8 * 8 for x in lengths)
+
+
+def test_tile_plan_cpp_against_python(plan_check):
+    """plan_tiles of csrc/avr_plan.h and of avrecode_ms_amd/device.py, element for element: lengths full of ties and zeros, so that the
+    stable order is what is compared, and slice counts either side of a tile's 64, so that the tiles' boundaries are."""
+    import torch
+    from avrecode_ms_amd.device import plan_tiles
+    rng = np.random.default_rng(64)
+    for n in (0, 1, 63, 64, 65, 129):
+        lengths = rng.choice([0, 1, 7, 8, 9, 16, 17, 1000], n).tolist()
+        for per_chunk in (8, 16):
+            out = plan_check("tiles %d %d %s\n" % (per_chunk, n, " ".join(map(str, lengths))))
+            assert [line.split()[0] for line in out[:-1]] == ["order", "tile_off"] and out[-1] == ""
+            order, tile_off = (list(map(int, line.split()[1:])) for line in out[:-1])
+            want_order, want_tile_off = plan_tiles(torch.tensor(lengths, dtype=torch.int32), per_chunk)
+            assert want_order.dtype == torch.int32 and want_tile_off.dtype == torch.int64
+            assert (order, tile_off) == (want_order.tolist(), want_tile_off.tolist()), (n, per_chunk)
+            assert sorted(order) == list(range(n)) and len(tile_off) == (n + 63) // 64 + 1
 
 
 def test_totals_against_the_layout_tests(plan_check):
