@@ -202,6 +202,8 @@ struct avr_batch {
     std::vector<uint32_t> group_first;
     std::vector<uint8_t> est_in;            // one table a group, fresh ones included
     PinBuf<uint8_t> h_est_in, h_est_out;
+    // any_est_in only spares a copy: est_in holds a table for every group, {1, 1} for the fresh ones, so a run that sends it computes
+    // what a run without start tables computes.  Nothing goes wrong while it is true; avr_batch_reset clears it to spare the copy again.
     bool any_est_in = false, est_out_fetched = false;
     DevBuf<uint16_t> d_keys;
     DevBuf<uint32_t> d_group_first;
@@ -802,7 +804,14 @@ int avr_batch_wait(avr_batch *b) {
     if (int rc = select_device(b->device)) return rc;
     b->in_flight = false;
     const size_t n = b->n_bins.size();
-    if (n == 0) { b->ran = true; return AVR_OK; }
+    if (n == 0) {                                                // nothing ran: the run's info and times are zeros, not the previous run's
+        memset(b->info, 0, sizeof b->info);
+        memset(b->ms, 0, sizeof b->ms);
+        for (Check *c : b->checks()) c->ms = c->before = 0;     // (avr_batch_submit has set every check off)
+        b->last_path = 0;
+        b->ran = true;
+        return AVR_OK;
+    }
     const uint32_t n32 = uint32_t(n);
     hipStream_t s = b->stream;
     int rc;

@@ -224,9 +224,11 @@ int avr_batch_get_states(avr_batch *b, size_t slice, const uint8_t **states, siz
  * so [1] is 0 and [2] is the batch's declared n_states, every one of which has a row; [3] bit 0 = avr_batch_wait found the guess
  * too small and ran the batch again, bit 1 = it ran the second pass of the intra-slice parallel path (slices with a bin in a context
  * the sampled census missed).  CABAC-record batches; zeros otherwise, except that [0] is also 1 when a K2 batch ran K2p (a test of key
- * records sees through it which K2 path coded the batch). */
+ * records sees through it which K2 path coded the batch).  A run of a batch without slices ran nothing: all four are 0, whatever the
+ * object's previous run was. */
 int avr_batch_run_info(avr_batch *b, uint32_t info[4]);
-/* milliseconds of the last run: [0] H2D, [1] pack kernel (for key records: the estimator resolver and the pack kernel), [2] encode kernel, [3] D2H */
+/* milliseconds of the last run: [0] H2D, [1] pack kernel (for key records: the estimator resolver and the pack kernel), [2] encode kernel, [3] D2H;
+ * all 0 for a run of a batch without slices, as are avr_batch_verify_ms, avr_batch_verify_est_ms and avr_batch_restore_ms */
 int avr_batch_timings(avr_batch *b, float ms[4]);
 
 /* Verification of a K2 batch (AVR_KIND_RANGE, AVR_KIND_RANGE_KEYS) on the device: off by default, and then nothing of a run differs.

@@ -9,7 +9,8 @@
 // EVERY ROUTE OF THE COMMAND LINE.
 //   * Slices of range records (avr_batch_add_slice_range) are coded by avr_oracle_range_encode, slices of resolved codes
 //     (avr_batch_add_slice_codes) by avr_oracle_cabac_encode_codes; statuses are the oracle's (a bin after a put_terminate(1):
-//     AVR_SLICE_BAD_RECORD, as on the device).
+//     AVR_SLICE_BAD_RECORD for records, as on the device; for codes only here -- the device's coders from codes trust them, "resolved
+//     codes have no bad value", and no recorder writes such a slice).
 //   * Key records (avr_batch_begin_group, avr_batch_add_slice_range_keys; AVR_DEVICE_ESTIMATORS=1) are resolved per group by the
 //     sequential rule -- a table of AVR_EST_KEYS {pos, neg} pairs, fresh {1, 1} or the caller's -- and then coded as range records.  A
 //     malformed key: AVR_SLICE_BAD_RECORD for its slice and the rest of its group.  avr_batch_get_estimators: the group's table afterwards.
@@ -68,8 +69,8 @@ struct group { size_t first; bool given; estimators in, out; };
 
 struct faults { uint32_t verify_flip = 0, est_flip = 0, est_flip_bin = 0, restore_flip = 0; };
 
-const faults &fault_points() {                           // "name=value,...": unknown names end the program, a typo must not pass for a sound run
-    static const faults f = [] {
+faults &fault_points() {                                 // "name=value,...": unknown names end the program, a typo must not pass for a sound run
+    static faults f = [] {
         faults v;
         const char *p = getenv("AVR_CPU_BATCH_FAULT");
         std::string s = p ? p : "";
@@ -221,6 +222,20 @@ extern "C" {
 
 const char *avr_last_error(void) { return g_error.c_str(); }
 
+// The test build's call (csrc/avr_api.cpp, AVR_TEST_HOOKS), for a test that loads the stand-in as a library and changes the fault points
+// between runs: one of the four names above, or "reset" (all off).  Not for use while another thread runs a batch.
+int avr_test_hook_set(const char *name, uint32_t value) {
+    faults &f = fault_points();
+    const std::string n = name ? name : "";
+    if (n == "reset") f = faults{};
+    else if (n == "verify_flip") f.verify_flip = value;
+    else if (n == "est_flip") f.est_flip = value;
+    else if (n == "est_flip_bin") f.est_flip_bin = value;
+    else if (n == "restore_flip") f.restore_flip = value;
+    else return fail(AVR_ERR_INVALID, "cpu_batch: unknown fault point " + n);
+    return AVR_OK;
+}
+
 avr_batch *avr_batch_create(int, size_t max_slices, size_t max_bins) {
     avr_batch *b = new avr_batch();
     b->max_slices = max_slices;
@@ -263,8 +278,7 @@ int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in) {
             if (!g.in.e[k][0] || !g.in.e[k][1] || unsigned(g.in.e[k][0]) + unsigned(g.in.e[k][1]) > 0x60)
                 return fail(AVR_ERR_INVALID, "cpu_batch: an estimator with pos or neg 0, or pos + neg above 0x60");
     }
-    if (!b->groups.empty() && b->groups.back().first == g.first) b->groups.back() = g;       // an empty group: replaced
-    else b->groups.push_back(g);
+    b->groups.push_back(g);                              // (a group may stay without a slice, as in the product: its table afterwards is its start table)
     b->kind = AVR_KIND_RANGE_KEYS;
     return int(b->groups.size()) - 1;
 }
