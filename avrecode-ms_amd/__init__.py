@@ -90,7 +90,7 @@ _HOST = os.path.join(_CSRC, "host")
 def build_recode(force: bool = False, verbose: bool = False) -> str:
     """Compile the `recode` command line (csrc/host/recode_main.cpp: the reference's CLI, recode.cpp:1642-1677, on this
     build's H.264 syntax parser and GPU batches) next to libavrecode_hip.so, which it links."""
-    deps = [os.path.join(_HOST, f) for f in ("recode_main.cpp", "avr_h264.h", "avr_h264_tables.h", "avr_recode.h", "avr_host.h", "avr_model.h")]
+    deps = [os.path.join(_HOST, f) for f in ("recode_main.cpp", "avr_h264.h", "avr_h264_tables.h", "avr_recode.h", "avr_host.h", "avr_model.h", "avr_sha256.h")]
     deps += [HEADER_PATH, LIB_PATH]
     if not force and os.path.exists(RECODE_PATH) and all(os.path.getmtime(RECODE_PATH) >= os.path.getmtime(d) for d in deps):
         return RECODE_PATH

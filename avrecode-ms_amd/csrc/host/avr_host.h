@@ -329,7 +329,19 @@ struct Block {                                          // recode.proto:10-17
     bool has_last_byte = false;      std::string last_byte;
 };
 
+// Recoded.metadata (recode.proto: optional Metadata metadata = 1, whose own sub-fields 1-4 nobody writes) carries, when the writer is
+// asked for it, two sub-fields the reference's schema does not define: 5 = original_sha256 (bytes, exactly 32: the SHA-256 of the
+// whole original file) and 6 = original_size (varint).  A proto2 reader skips fields it does not know -- the reference's does, and
+// this one did before it knew them -- so an archive with them restores everywhere; without them it is byte for byte the reference's.
+// The field is the FIRST of the file (field-number order): a truncated archive keeps its digest.
+struct Metadata {
+    bool has_original_sha256 = false;  std::string original_sha256;
+    bool has_original_size = false;    uint64_t original_size = 0;
+    bool any() const { return has_original_sha256 || has_original_size; }
+};
+
 struct Recoded {
+    Metadata metadata;                                  // recode.proto:19; written only where it has one of its two sub-fields
     std::vector<Block> block;                           // recode.proto:18
 
     static void put_varint(std::string &o, uint64_t v) {
@@ -343,6 +355,12 @@ struct Recoded {
     }
     std::string SerializeAsString() const {             // recode.cpp:1131
         std::string out;
+        if (metadata.any()) {
+            std::string m;
+            if (metadata.has_original_sha256) put_bytes(m, 5, metadata.original_sha256);
+            if (metadata.has_original_size) { put_varint(m, 6 << 3 | 0); put_varint(m, metadata.original_size); }
+            put_bytes(out, 1, m);
+        }
         for (const Block &b : block) {
             std::string m;
             if (b.has_size) { put_varint(m, 1 << 3 | 0); put_varint(m, uint64_t(b.size)); }
@@ -399,8 +417,32 @@ struct Recoded {
         }
         return true;
     }
+    // Sub-field 5 must be 32 bytes long (anything else is not a digest, and the file is refused); every sub-field but 5 and 6 is
+    // skipped; a later occurrence replaces an earlier one, as protobuf merges an optional message that occurs twice.
+    static bool parse_metadata(const uint8_t *p, const uint8_t *end, Metadata *m) {
+        while (p < end) {
+            uint64_t tag, v;
+            if (!get_varint(p, end, &tag)) return false;
+            const uint64_t field = tag >> 3;
+            const int wire = int(tag & 7);
+            if (field == 5 && wire == 2) {
+                if (!get_varint(p, end, &v) || v != 32 || uint64_t(end - p) < v) return false;
+                m->has_original_sha256 = true;
+                m->original_sha256.assign(reinterpret_cast<const char *>(p), size_t(v));
+                p += v;
+            } else if (field == 6 && wire == 0) {
+                if (!get_varint(p, end, &v)) return false;
+                m->has_original_size = true;
+                m->original_size = v;
+            } else if (!skip_field(p, end, wire)) {
+                return false;
+            }
+        }
+        return true;
+    }
     bool ParseFromArray(const void *data, size_t size) {  // recode.cpp:1338, :1342
         block.clear();
+        metadata = Metadata();
         const uint8_t *p = static_cast<const uint8_t *>(data), *end = p + size;
         while (p < end) {
             uint64_t tag, len;
@@ -410,6 +452,10 @@ struct Recoded {
                 Block b;
                 if (!parse_block(p, p + len, &b)) return false;
                 block.push_back(std::move(b));
+                p += len;
+            } else if ((tag >> 3) == 1 && (tag & 7) == 2) {
+                if (!get_varint(p, end, &len) || uint64_t(end - p) < len) return false;
+                if (!parse_metadata(p, p + len, &metadata)) return false;
                 p += len;
             } else if (!skip_field(p, end, int(tag & 7))) {
                 return false;

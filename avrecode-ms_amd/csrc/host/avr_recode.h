@@ -17,6 +17,7 @@
 #include <memory>
 
 #include "avr_host.h"
+#include "avr_sha256.h"
 
 namespace avr {
 namespace host {
@@ -203,6 +204,10 @@ class compressor {                                       // recode.cpp:1109-1316
     // (avr_batch_expect): K1, finish and the tail patch with the container's two fields against the real payload.  A caller with
     // batches of its own uses add_restore_to / take_restore_from, beside add_to / take_from.
     void set_restore_check(bool on) { restore_check_ = on; }
+    // The digest: finish() puts Recoded.metadata in front of the blocks, with the SHA-256 and the length of the whole original file
+    // (avr_host.h: Metadata), for decompressor::finish to hold the restored file to.  Off, the container is byte for byte what it is
+    // without this call; on, it is those bytes behind the metadata field.
+    void set_digest(bool on) { digest_ = on; }
     struct restore_slice { std::vector<uint8_t> codes; size_t payload_at, payload_size; };   // the payload: original[payload_at .. + payload_size)
     std::vector<restore_slice> &restore_slices() { return restore_pending_; }
     const std::string &original() const { return original_; }
@@ -273,6 +278,13 @@ class compressor {                                       // recode.cpp:1109-1316
         final_literal.has_literal = true;
         final_literal.literal = original_.substr(prev_coded_block_end_);
         out_.block.push_back(final_literal);
+        if (digest_) {
+            phase_timer t("compress: digest");
+            out_.metadata.has_original_sha256 = true;
+            out_.metadata.original_sha256 = sha256::of(original_);
+            out_.metadata.has_original_size = true;
+            out_.metadata.original_size = original_.size();
+        }
         return out_.SerializeAsString();
     }
 
@@ -401,7 +413,7 @@ class compressor {                                       // recode.cpp:1109-1316
 
     struct pending { int block; std::vector<uint16_t> recs; };
     int first_in_batch_ = -1, first_in_restore_batch_ = -1;
-    bool device_estimators_ = false, verify_ = false, restore_check_ = false;
+    bool device_estimators_ = false, verify_ = false, restore_check_ = false, digest_ = false;
     std::vector<restore_slice> restore_pending_;
     std::string original_;
     int device_;
@@ -495,8 +507,12 @@ class decompressor {                                     // recode.cpp:1319-1598
             }
             out += block.out_bytes;
         }
+        check_digest(out);
         return out;
     }
+    // Does the archive say what it must restore to (Recoded.metadata's SHA-256)?  Whether or not, finish() holds the file to whatever
+    // the archive records; the command `recode check` has to say which it was.
+    bool has_digest() const { return in_.metadata.has_original_sha256; }
 
     // The stream the decoder reads (decompressor::read_packet, recode.cpp:1366-1416): the blocks in order, a
     // literal as it is, a coded block as a surrogate payload of the recorded size, a skip_coded block as nothing
@@ -607,6 +623,20 @@ class decompressor {                                     // recode.cpp:1319-1598
                 throw std::runtime_error("Invalid surrogate marker in coded block.");
         }
         return index;
+    }
+
+    // The archive's digest against the assembled file, on every route (they all end in finish()), before the caller has a byte to
+    // write: the size first, where it is recorded, then the SHA-256, where it is.  It covers what no check of a single slice can:
+    // K3, the model, the parser, K1 and the tail patch together, the literal blocks, the order of the blocks, and whatever storage
+    // did to the archive.  No switch turns it off.  An archive without metadata is not checked: there is nothing to hold it to.
+    void check_digest(const std::string &out) const {
+        const Metadata &m = in_.metadata;
+        if (!m.any()) return;
+        phase_timer t("decompress: digest");
+        const bool size_ok = !m.has_original_size || m.original_size == out.size();
+        if (size_ok && (!m.has_original_sha256 || m.original_sha256 == sha256::of(out))) return;
+        throw std::runtime_error("Verify error: restored file does not match the archive's digest (" + std::to_string(out.size()) + " bytes restored, " +
+                                 (m.has_original_size ? std::to_string(m.original_size) : std::string("no size")) + " recorded)");
     }
 
     // One K1 batch for the whole file, from resolved codes: the recorder has *state in hand at every bin

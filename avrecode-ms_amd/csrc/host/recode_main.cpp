@@ -35,6 +35,18 @@
 // coded slice does not restore its payload (slice N, byte M)" (exit status 1, nothing written for that file).  With or without
 // AVR_VERIFY, AVR_DEVICE_ESTIMATORS and AVR_MODEL_HOOKS; the .recode bytes are the same either way; under AVR_TIMING=1 the lines
 // "compress: GPU restore check (K1)" and "compress: restore check kernel".  Read here, not by the library.  Off by default.
+// AVR_DIGEST=1 = compress, roundtrip and test <dir> put the SHA-256 and the length of the original file at the head of the .recode file
+// (Recoded.metadata, two sub-fields the reference's schema does not define and its reader skips: avr_host.h); behind them the bytes are
+// what they are without the switch.  Off by default.  The other direction has no switch: decompress, roundtrip, test <dir> and check hold
+// the restored file to the digest of every archive that carries one, once it is whole and before a byte of it is written -- "Verify
+// error: restored file does not match the archive's digest (N bytes restored, M recorded)" (exit status 1, nothing written; in
+// test <dir> only the file that owns the archive is lost) -- and restore an archive without one as ever.  Under AVR_TIMING=1 the lines
+// "compress: digest" and "decompress: digest".
+//
+// And `recode check <archive>`: restore the archive in memory, the way decompress does (K3, the parser, K1 on the device), and write
+// nothing.  "Digest OK: N bytes" and exit status 0 where the archive carries a digest and the restored bytes match it; "No digest in
+// this archive: N bytes restored, not checked" and exit status 1 where it carries none (the command is there to vouch, and cannot);
+// the usual Exception line and exit status 1 on a mismatch or any other error.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -71,6 +83,7 @@ bool device_estimators() {
 
 bool verify() { static const bool on = [] { const char *d = getenv("AVR_VERIFY"); return d && atoi(d) != 0; }(); return on; }
 bool verify_restore() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_RESTORE"); return d && atoi(d) != 0; }(); return on; }
+bool digest() { static const bool on = [] { const char *d = getenv("AVR_DIGEST"); return d && atoi(d) != 0; }(); return on; }
 bool verify_k1() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_K1"); return d && atoi(d) != 0; }(); return on; }
 
 std::string slurp(const std::string &path) {
@@ -86,13 +99,16 @@ std::string compress_bytes(const std::string &original) {            // compress
     c.set_device_estimators(device_estimators());
     c.set_verify(verify());
     c.set_restore_check(verify_restore());
+    c.set_digest(digest());
     h264::h264_stream_decoder d;
     d.residual_hooks = model_hooks();
     return c.run(&d);
 }
 
-std::string decompress_bytes(const std::string &recoded) {           // decompressor::run, recode.cpp:1345-1364
+// decompressor::run, recode.cpp:1345-1364; had_digest: whether the archive said what it must restore to (run() has then held it to that)
+std::string decompress_bytes(const std::string &recoded, bool *had_digest = nullptr) {
     host::decompressor d(recoded, device());
+    if (had_digest) *had_digest = d.has_digest();
     d.set_verify(verify_k1());
     h264::h264_stream_decoder dec;
     dec.residual_hooks = model_hooks();
@@ -288,7 +304,7 @@ void perf_test_driver(const std::string &directory_path) {
     const unsigned threads = std::min<unsigned>(hw ? hw : 4, 32);
     shared_batch batch_in, batch_out, batch_restore;
     const bool on_device = device_estimators();                      // read here, once, not in the files' threads
-    const bool verify_on = verify(), verify_k1_on = verify_k1(), restore_on = verify_restore();
+    const bool verify_on = verify(), verify_k1_on = verify_k1(), restore_on = verify_restore(), digest_on = digest();
     for (size_t base = 0; base < files.size(); base += window) {
         const size_t n = std::min(window, files.size() - base);
         std::vector<file_job> jobs(n);
@@ -306,6 +322,7 @@ void perf_test_driver(const std::string &directory_path) {
                 j.c.reset(new host::compressor(j.original, device()));
                 j.c->set_device_estimators(on_device);
                 j.c->set_restore_check(restore_on);
+                j.c->set_digest(digest_on);
                 h264::h264_stream_decoder dec;
                 dec.residual_hooks = model_hooks();
                 dec.dry_run_threads = 1;                             // the cores are taken by the files
@@ -421,6 +438,18 @@ void perf_test_driver(const std::string &directory_path) {
         std::cout << "Compress-decompress roundtrip failed on " << fail_count << " / " << files.size() << " files" << std::endl;
 }
 
+// recode check <archive>: what decompress would write, held to the archive's digest, and nothing written
+int check(const std::string &input_filename) {
+    bool had_digest = false;
+    const std::string restored = decompress_bytes(slurp(input_filename), &had_digest);
+    if (!had_digest) {
+        std::cout << "No digest in this archive: " << restored.size() << " bytes restored, not checked" << std::endl;
+        return 1;
+    }
+    std::cout << "Digest OK: " << restored.size() << " bytes" << std::endl;
+    return 0;
+}
+
 int probe(const std::string &input_filename) {
     const std::string bytes = slurp(input_filename);
     h264::h264_stream_decoder dec;
@@ -485,6 +514,8 @@ int main(int argc, char **argv) {
             return 0;
         } else if (command == "probe") {
             return probe(input_filename);
+        } else if (command == "check") {
+            return check(input_filename);
         } else {
             throw std::invalid_argument("Unknown command: " + command);
         }
