@@ -218,7 +218,7 @@ struct avr_batch {
     uint32_t dense_hint = 0;                // context rows the previous run of this object needed (0: no run yet)
     uint32_t hint_used = 0;                 // what the run in flight was sized by (0: it asked the device and waited)
     uint32_t info[4] = {0, 0, 0, 0};        // avr_batch_run_info
-    avr_chunk_plan plan{};                  // of the chunked run in flight (device arrays of this batch)
+    avr_chunk_plan plan{};                  // of the run in flight (device arrays of this batch)
 
     // verification of a run (K2: avr_batch_set_verify, K1: avr_batch_set_verify_k1): off by default, and then none of this is touched
     bool verify = false;                    // the setting: the next submit of a K2 batch enqueues the verifier behind the encode
@@ -238,13 +238,13 @@ struct avr_batch {
     // the three in the order they run in; the encode's slot of the timings ends where the first of them that a run has starts
     std::array<Check *, 3> checks() { return {&verifier, &est_checker, &restorer}; }
 
-    // what the encoder of the run in flight read, for the verifier behind it to read the same
-    struct Coded {
-        int form = 0;                       // K1: a cabac_verify::Form; K2: 1 for tiles, 0 for slice-major records
-        const void *recs = nullptr;         // the records (tiles, codes) ...
-        const uint64_t *off = nullptr;      // ... and where each slice's (tile's) begin
-        const uint32_t *order = nullptr;    // the slices' order, where the path has one
-    } coded;
+    // The arrays of the run in flight as the launchers take them (avr_internal.h), made once at submit: what its encoder read, for the
+    // verifier behind it to read the same; its context states (a K1 batch of records; none otherwise); its coded output.
+    avr::Slices read;
+    avr::States states;
+    avr::Output output;
+    // the key records of a run that has them, as the resolver and the estimator checker read them
+    avr::Slices key_records() const { return {d_keys.p, d_rec_off.p, d_n_bins.p, nullptr, uint32_t(n_bins.size())}; }
 };
 
 // The refusals the entry points open with.  check_idle: for what changes a batch between runs; check_open: for what adds to a batch
@@ -539,6 +539,7 @@ static int begin_run(avr_batch *b, size_t n, size_t arena) {
     const bool verify = b->kind == AVR_KIND_RANGE ? b->verify : b->verify_k1;
     if ((rc = b->verifier.arm(verify, n)) || (rc = b->est_checker.arm(verify && b->keys, n)) || (rc = reserve_restore(b, n))) return rc;
     b->plan_used = 0;
+    b->output = {b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p};
     return AVR_OK;
 }
 
@@ -548,8 +549,8 @@ static int enqueue_lengths(avr_batch *b, uint32_t n32) {
     const bool with_states = b->kind == AVR_KIND_CABAC && ns;
     hipStream_t s = b->stream;
     AVR_HIP(hipEventRecord(b->ev[3], s));
-    AVR_HIP(hipMemcpyAsync(b->h_out_len.p, b->d_out_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    AVR_HIP(hipMemcpyAsync(b->h_status.p, b->d_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    AVR_HIP(hipMemcpyAsync(b->h_out_len.p, b->output.out_len, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    AVR_HIP(hipMemcpyAsync(b->h_status.p, b->output.status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (with_states) AVR_HIP(hipMemcpyAsync(b->h_final.p, b->d_final.p, n * ns, hipMemcpyDeviceToHost, s));
     for (Check *c : b->checks())
         if (int rc = c->fetch(s, n)) return rc;
@@ -558,47 +559,37 @@ static int enqueue_lengths(avr_batch *b, uint32_t n32) {
 
 // What follows the encode kernels of every path, in this order: the verifier of the batch's kind, the estimator checker, the restore
 // check -- each that the run has, between its two events -- and the lengths.
-// The verifier reads what that path's encoder read (b->coded).  K2: the range decoder over tiles or slice-major records.  K1: the
-// CABAC decoder over whatever form the records or codes have, with the encoder's final states where the kind has states.
+// The verifier reads what that path's encoder read (b->read).  K2: the range decoder over tiles or slice-major records.  K1: the
+// CABAC decoder over whatever form the records or codes have, with the encoder's final states where the kind has states (b->states).
 // The estimator checker holds the resolver's records to the key records and the tables, in the resolver's workspace (it is done with
 // it, and the checker's is no larger).
 // again: behind K1p's second pass at avr_batch_wait, over the same bytes.  The test build's hooks (verify_flip, restore_flip: a byte
 // of a slice's output complemented in front of a check's start event) have had their turn then.
 static int enqueue_checks(avr_batch *b, uint32_t n32, bool again = false) {
     hipStream_t s = b->stream;
-    const avr_batch::Coded &c = b->coded;
     int rc;
     if (b->verifier.on) {
 #ifdef AVR_TEST_HOOKS
-        if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
+        if (const uint32_t k = avr::test_hooks().verify_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->output, k - 1));
 #endif
         if ((rc = b->verifier.start(s))) return rc;
-        if (b->kind == AVR_KIND_RANGE) {
-            AVR_HIP(avr::launch_range_verify(c.form != 0, s, c.recs, c.off, b->d_n_bins.p, c.order, n32, b->d_out.p, b->d_out_off.p, b->d_out_len.p,
-                                             b->d_status.p, b->verifier.d_first.p));
-        } else {
-            const bool states = c.form != avr::cabac_verify::kCodes;
-            AVR_HIP(avr::launch_cabac_verify(c.form, s, c.recs, c.off, b->d_n_bins.p, c.order, n32, states ? b->d_states.p : nullptr,
-                                             states ? uint32_t(b->n_states) : 0u, b->d_out.p, b->d_out_off.p, b->d_out_len.p,
-                                             states ? b->d_final.p : nullptr, b->d_status.p, b->verifier.d_first.p));
-        }
+        if (b->kind == AVR_KIND_RANGE) AVR_HIP(avr::launch_range_verify(s, b->read, b->output, b->verifier.d_first.p));
+        else AVR_HIP(avr::launch_cabac_verify(s, b->read, b->states, b->output, b->verifier.d_first.p));
         if ((rc = b->verifier.end(s))) return rc;
     }
     if (b->est_checker.on) {
         if ((rc = b->est_checker.start(s))) return rc;
-        AVR_HIP(avr::launch_est_verify(s, b->d_keys.p, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p,
-                                       uint32_t(b->group_first.size()), b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p,
-                                       b->d_chunk_base.p, b->d_chunk_slice.p, b->hp.chunk_base.back(), avr::align256(b->d_est_ws.p),
-                                       b->d_status.p, b->est_checker.d_first.p));
+        AVR_HIP(avr::launch_est_verify(s, b->key_records(), b->d_recs.p, b->d_group_first.p, uint32_t(b->group_first.size()),
+                                       b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, &b->plan, avr::align256(b->d_est_ws.p),
+                                       b->output.status, b->est_checker.d_first.p));
         if ((rc = b->est_checker.end(s))) return rc;
     }
     if (b->restorer.on) {                                        // (K1 only: a K2 batch takes no expectations)
 #ifdef AVR_TEST_HOOKS
-        if (const uint32_t k = avr::test_hooks().restore_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->d_out.p, b->d_out_off.p, k - 1));
+        if (const uint32_t k = avr::test_hooks().restore_flip; k && k <= n32 && !again) AVR_HIP(avr::launch_verify_flip(s, b->output, k - 1));
 #endif
         if ((rc = b->restorer.start(s))) return rc;
-        AVR_HIP(avr::launch_restore_check(s, b->d_out.p, b->d_out_off.p, b->d_out_len.p, n32, b->d_expect.p, b->d_expect_off.p, b->d_expect_len.p,
-                                          b->d_status.p, b->restorer.d_first.p));
+        AVR_HIP(avr::launch_restore_check(s, b->output, n32, b->d_expect.p, b->d_expect_off.p, b->d_expect_len.p, b->restorer.d_first.p));
         if ((rc = b->restorer.end(s))) return rc;
     }
     return enqueue_lengths(b, n32);
@@ -633,16 +624,11 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
     AVR_HIP(hipMemsetAsync(b->d_status.p, 0, n * sizeof(int32_t), s));
     AVR_HIP(hipEventRecord(b->ev[1], s));
     AVR_HIP(hipEventRecord(b->ev[2], s));
-    const uint8_t *d_codes = reinterpret_cast<const uint8_t *>(b->d_recs.p);
-    if (chunked) {
-        AVR_HIP(avr::launch_k1p_code(s, d_codes, b->d_n_bins.p, n32, &plan, avr::align256(b->d_workspace.p), b->d_out.p,
-                                     b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-    } else {
-        AVR_HIP(avr::launch_cabac_encode_codes(s, d_codes, b->d_res_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
-                                               b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-    }
+    b->read = {b->d_recs.p, b->d_res_off.p, b->d_n_bins.p, chunked ? nullptr : b->d_order.p, n32, false, avr::cabac_verify::kCodes};
+    b->states = {};                                              // codes carry their states
+    if (chunked) AVR_HIP(avr::launch_k1p_code(s, b->read, &plan, avr::align256(b->d_workspace.p), b->output));
+    else AVR_HIP(avr::launch_cabac_encode_codes(s, b->read, b->output));
     b->last_path = chunked;
-    b->coded = {avr::cabac_verify::kCodes, d_codes, b->d_res_off.p, chunked ? nullptr : b->d_order.p};
     return enqueue_checks(b, n32);
 }
 
@@ -652,9 +638,8 @@ static int resolve_keys(avr_batch *b, uint32_t n32) {
     const size_t n = n32, n_groups = b->group_first.size();
     std::vector<uint32_t> group_first(b->group_first);
     group_first.push_back(n32);
-    const uint32_t total_chunks = b->hp.chunk_base.back();
     int rc;
-    if ((rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(avr::est_layout(n, n_groups, total_chunks).total + 256)) ||
+    if ((rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(avr::est_layout(n, n_groups, b->plan.total_chunks).total + 256)) ||
         (rc = b->d_est_out.reserve(n_groups * kEstTable)) || (b->any_est_in && (rc = b->d_est_in.reserve(n_groups * kEstTable))))
         return rc;
     hipStream_t s = b->stream;
@@ -665,9 +650,8 @@ static int resolve_keys(avr_batch *b, uint32_t n32) {
         AVR_HIP(hipMemcpyAsync(b->d_est_in.p, b->h_est_in.p, n_groups * kEstTable, hipMemcpyHostToDevice, s));
     }
     b->est_out_fetched = false;
-    AVR_HIP(avr::launch_est_resolve(s, b->d_keys.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_group_first.p, uint32_t(n_groups),
-                                    b->any_est_in ? b->d_est_in.p : nullptr, b->d_est_out.p, b->d_chunk_base.p,
-                                    b->d_chunk_slice.p, total_chunks, avr::align256(b->d_est_ws.p), b->d_recs.p, b->d_status.p));
+    AVR_HIP(avr::launch_est_resolve(s, b->key_records(), b->d_group_first.p, uint32_t(n_groups), b->any_est_in ? b->d_est_in.p : nullptr,
+                                    b->d_est_out.p, &b->plan, avr::align256(b->d_est_ws.p), b->d_recs.p, b->output.status));
 #ifdef AVR_TEST_HOOKS
     if (const uint32_t k = avr::test_hooks().est_flip; k && k <= n32 && b->verifier.on)
         AVR_HIP(avr::launch_est_flip(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, k - 1, avr::test_hooks().est_flip_bin));
@@ -731,50 +715,35 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     // Both K1 paths renumber a two-byte batch onto the contexts it uses themselves (the intra-slice parallel kernels inside
     // their census pass, the one-lane-per-slice kernel through launch_cabac_encode): records and states go in as they are.
     // One-byte records name dense ids below n_states already: neither one-byte path counts or renumbers.
-    avr_chunk_plan plan;
-    if ((rc = stage_plan(b, avr::plan_total(b->hp.res_off), &plan))) return rc;
-    if (chunked && (rc = b->d_workspace.reserve((cabac ? avr::k1p_layout(n, uint32_t(ns), &plan).total
-                                                       : avr::k2p_layout(n, plan.total_chunks, total_out).total) + 256))) return rc;
+    if ((rc = stage_plan(b, avr::plan_total(b->hp.res_off), &b->plan))) return rc;
+    const avr_chunk_plan *plan = &b->plan;
+    if (chunked && (rc = b->d_workspace.reserve((cabac ? avr::k1p_layout(n, uint32_t(ns), plan).total
+                                                       : avr::k2p_layout(n, plan->total_chunks, total_out).total) + 256))) return rc;
     if (b->keys && (rc = resolve_keys(b, n32))) return rc;       // key records: d_keys -> d_recs, inside slot [1] of the timings
     uint8_t *wsp = avr::align256(b->d_workspace.p);
-    if (chunked && !cabac) {
-        // K2 for few, long slices: the range recurrence per slice, everything else per chunk (avr_k2p.hip)
+    b->states = cabac ? avr::States{b->d_states.p, uint32_t(ns), b->d_final.p} : avr::States{};
+    // the slice-major records as they lie on the device (the tiled paths: with the order their slices take in the tiles) ...
+    const avr::Slices recs{b->recs8 ? static_cast<const void *>(b->d_recs8.p) : b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, chunked ? nullptr : b->d_order.p,
+                           n32, false, b->recs8 ? avr::cabac_verify::kSlices8 : avr::cabac_verify::kSlices2};
+    if (chunked) {
+        // ... are what K2p and K1p read, K1p in the caller's numbering: the census, the dense map and the chains are checked with the bytes
+        b->read = recs;
         AVR_HIP(hipEventRecord(b->ev[2], s));
-        AVR_HIP(avr::launch_k2p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, b->d_chunk_base.p, b->d_chunk_slice.p,
-                                plan.total_chunks, total_out, wsp, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-        b->coded = {0, b->d_recs.p, b->d_rec_off.p, nullptr};                    // the slice-major records K2p read
-    } else if (chunked) {
-        b->plan = plan;
-        AVR_HIP(hipEventRecord(b->ev[2], s));
-        if (b->recs8)                                            // one-byte records: no census, no guess to check, nothing waits
-            AVR_HIP(avr::launch_k1p8(s, b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
-                                     avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
+        if (!cabac)                                              // K2 for few, long slices: the range recurrence per slice, everything else per chunk (avr_k2p.hip)
+            AVR_HIP(avr::launch_k2p(s, recs, plan, total_out, wsp, b->output));
+        else if (b->recs8)                                       // one-byte records: no census, no guess to check, nothing waits
+            AVR_HIP(avr::launch_k1p8(s, recs, b->states, plan, wsp, b->output));
         else
-            AVR_HIP(avr::launch_k1p(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(ns), &plan, wsp,
-                                    avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}, &hint));
-        // the slice-major records K1p read, in the caller's numbering: the census, the dense map and the chains are checked with the bytes
-        if (b->recs8) b->coded = {avr::cabac_verify::kSlices8, b->d_recs8.p, b->d_rec_off.p, nullptr};
-        else b->coded = {avr::cabac_verify::kSlices2, b->d_recs.p, b->d_rec_off.p, nullptr};
+            AVR_HIP(avr::launch_k1p(s, recs, b->states, plan, wsp, b->output, &hint));
     } else {
-        if (b->recs8)                                            // one-byte records validated and transposed in one pass, as they are
-            AVR_HIP(avr::launch_pack_tiles8_narrow(s, uint32_t(ns), b->d_recs8.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
-                                                   b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
-        else
-            AVR_HIP(avr::launch_pack_tiles(s, b->kind, uint32_t(ns), b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, b->d_order.p, n32,
-                                           b->d_tile_off.p, b->d_tiles.p, b->d_status.p));
+        // ... or go into the tiles the one-lane-per-slice coders read (one-byte records validated and transposed in one pass, as they are)
+        b->read = {b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, true, b->recs8 ? avr::cabac_verify::kTiles8 : avr::cabac_verify::kTiles2};
+        if (b->recs8) AVR_HIP(avr::launch_pack_tiles8_narrow(s, uint32_t(ns), recs, b->d_tile_off.p, b->d_tiles.p, b->output.status));
+        else AVR_HIP(avr::launch_pack_tiles(s, b->kind, uint32_t(ns), recs, b->d_tile_off.p, b->d_tiles.p, b->output.status));
         AVR_HIP(hipEventRecord(b->ev[2], s));
-        if (b->recs8)                                            // no census, no guess, nothing waits
-            AVR_HIP(avr::launch_cabac8_encode(s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_states.p,
-                                              uint32_t(ns), b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p));
-        else if (cabac)
-            AVR_HIP(avr::launch_cabac_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_states.p,
-                                             uint32_t(ns), b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p,
-                                             AVR_SLICE_OK, true, &hint));
-        else
-            AVR_HIP(avr::launch_range_encode(true, s, b->d_tiles.p, b->d_tile_off.p, b->d_n_bins.p, b->d_order.p, n32, b->d_out.p,
-                                             b->d_out_off.p, b->d_out_len.p, b->d_status.p));
-        // the tiles the encoder read
-        b->coded = {cabac ? (b->recs8 ? avr::cabac_verify::kTiles8 : avr::cabac_verify::kTiles2) : 1, b->d_tiles.p, b->d_tile_off.p, b->d_order.p};
+        if (b->recs8) AVR_HIP(avr::launch_cabac8_encode(s, b->read, b->states, b->output));      // no census, no guess, nothing waits
+        else if (cabac) AVR_HIP(avr::launch_cabac_encode(s, b->read, b->states, b->output, AVR_SLICE_OK, true, &hint));
+        else AVR_HIP(avr::launch_range_encode(s, b->read, b->output));
     }
     return enqueue_checks(b, n32);
 }
@@ -839,8 +808,7 @@ int avr_batch_wait(avr_batch *b) {
                     if (b->h_status.p[i] == AVR_SLICE_VERIFY_FAILED) { b->h_status.p[i] = AVR_SLICE_OK; any = true; }
                 if (any) AVR_HIP(hipMemcpyAsync(b->d_status.p, b->h_status.p, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
             }
-            AVR_HIP(avr::launch_k1p_retry(s, b->d_recs.p, b->d_rec_off.p, b->d_n_bins.p, n32, uint32_t(b->n_states), &b->plan, avr::align256(b->d_workspace.p),
-                                          avr::K1pIo{b->d_states.p, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_status.p, b->d_final.p}));
+            AVR_HIP(avr::launch_k1p_retry(s, b->read, b->states, &b->plan, avr::align256(b->d_workspace.p), b->output));
             // the verifier and the restore check skipped the slices of this pass (their status was not AVR_SLICE_OK yet): once more behind it
             if ((rc = enqueue_checks(b, n32, true))) return rc;
             AVR_HIP(hipStreamSynchronize(s));
@@ -858,7 +826,7 @@ int avr_batch_wait(avr_batch *b) {
     if ((rc = b->d_dense.reserve(dense_total + 1)) || (rc = b->h_out.reserve(dense_total + 1))) return rc;
     b->plan_used = 0;                                            // the run's plan arrays are consumed: the arena is free again
     AVR_STAGE(b->d_dense_off.p, b->dense_off.data(), n + 1);
-    AVR_HIP(avr::launch_compact(s, b->d_out.p, b->d_out_off.p, b->d_out_len.p, b->d_dense_off.p, n32, b->d_dense.p));
+    AVR_HIP(avr::launch_compact(s, b->output, b->d_dense_off.p, n32, b->d_dense.p));
     if (dense_total) AVR_HIP(hipMemcpyAsync(b->h_out.p, b->d_dense.p, dense_total, hipMemcpyDeviceToHost, s));
     AVR_HIP(hipEventRecord(b->ev[4], s));
     AVR_HIP(hipStreamSynchronize(s));
@@ -1136,9 +1104,22 @@ int avr_multi_load(avr_multi *m, uint64_t *bins_per_device) {
 
 // ------------------------------------------------------------------ device-resident API
 
+// Every entry point below packs its arguments into the launchers' structs (avr_internal.h), runs its checks -- on the caller's size_t
+// counts: the structs' are 32 bits wide -- and launches.  Which pointers a call checks is the call's own; the header says so per call.
+using avr::Output;
+using avr::OutputView;
+using avr::Slices;
+using avr::States;
+using avr::StatesView;
+static hipStream_t hip(void *stream) { return static_cast<hipStream_t>(stream); }
+
 static int check_common(const void *a, const void *b, const void *c, size_t n_slices) {
     if (n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_slices out of range");
     if (n_slices && (!a || !b || !c)) return fail(AVR_ERR_INVALID, "null device pointer");
+    return AVR_OK;
+}
+static int check_states(size_t n_states) {
+    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
     return AVR_OK;
 }
 
@@ -1147,46 +1128,42 @@ int avr_pack_tiles_device(int device, void *stream, int kind, size_t n_states, c
                           int32_t *status) {
     if (int rc = check_common(rec_off, n_bins, tile_off, n_slices)) return rc;
     if (kind != AVR_KIND_CABAC && kind != AVR_KIND_RANGE) return fail(AVR_ERR_INVALID, "kind %d", kind);
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
+    if (int rc = check_states(n_states)) return rc;
     if (n_slices && !status) return fail(AVR_ERR_INVALID, "null status");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_pack_tiles(static_cast<hipStream_t>(stream), kind, uint32_t(n_states), recs, rec_off, n_bins, order,
-                                   uint32_t(n_slices), tile_off, tiles, status));
+    AVR_HIP(avr::launch_pack_tiles(hip(stream), kind, uint32_t(n_states), Slices{recs, rec_off, n_bins, order, uint32_t(n_slices)}, tile_off, tiles, status));
     return AVR_OK;
 }
 
 // one-byte records: what the host can check of the layout -- the base 16-byte aligned, the offsets' array 8-byte aligned (the offsets
 // themselves live on the device, where the kernels flag a slice whose offset is not a multiple of 16)
-static int check_recs8(const uint8_t *recs8, const uint64_t *rec_off, size_t n_states) {
+static int check_recs8(const void *recs8, const uint64_t *rec_off, size_t n_states) {
     if (int rc = check_states8(n_states)) return rc;
     if (reinterpret_cast<uintptr_t>(recs8) & 15) return fail(AVR_ERR_INVALID, "recs8 is not 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(rec_off) & 7) return fail(AVR_ERR_INVALID, "rec_off is not 8-byte aligned");
     return AVR_OK;
 }
 
+// the two packers of one-byte records: the narrow one holds its one-byte tiles to their alignment as well
+static int pack_tiles8_device(bool narrow, int device, void *stream, size_t n_states, const Slices &in, size_t n_slices, const uint64_t *tile_off,
+                              void *tiles, int32_t *status) {
+    if (int rc = check_common(in.off, in.n_bins, tile_off, n_slices)) return rc;
+    if (int rc = check_recs8(in.recs, in.off, n_states)) return rc;
+    if (n_slices && (!in.recs || !tiles || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (narrow && (reinterpret_cast<uintptr_t>(tiles) & 15)) return fail(AVR_ERR_INVALID, "tiles is not 16-byte aligned");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP((narrow ? avr::launch_pack_tiles8_narrow : avr::launch_pack_tiles8)(hip(stream), uint32_t(n_states), in, tile_off, tiles, status));
+    return AVR_OK;
+}
 int avr_pack_tiles8_device(int device, void *stream, size_t n_states, const uint8_t *recs8, const uint64_t *rec_off,
                            const uint32_t *n_bins, const uint32_t *order, size_t n_slices, const uint64_t *tile_off, void *tiles,
                            int32_t *status) {
-    if (int rc = check_common(rec_off, n_bins, tile_off, n_slices)) return rc;
-    if (int rc = check_recs8(recs8, rec_off, n_states)) return rc;
-    if (n_slices && (!recs8 || !tiles || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_pack_tiles8(static_cast<hipStream_t>(stream), uint32_t(n_states), recs8, rec_off, n_bins, order,
-                                    uint32_t(n_slices), tile_off, tiles, status));
-    return AVR_OK;
+    return pack_tiles8_device(false, device, stream, n_states, Slices{recs8, rec_off, n_bins, order, uint32_t(n_slices)}, n_slices, tile_off, tiles, status);
 }
-
 int avr_pack_tiles8_narrow_device(int device, void *stream, size_t n_states, const uint8_t *recs8, const uint64_t *rec_off,
                                   const uint32_t *n_bins, const uint32_t *order, size_t n_slices, const uint64_t *tile_off, void *tiles,
                                   int32_t *status) {
-    if (int rc = check_common(rec_off, n_bins, tile_off, n_slices)) return rc;
-    if (int rc = check_recs8(recs8, rec_off, n_states)) return rc;
-    if (n_slices && (!recs8 || !tiles || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (reinterpret_cast<uintptr_t>(tiles) & 15) return fail(AVR_ERR_INVALID, "tiles is not 16-byte aligned");
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_pack_tiles8_narrow(static_cast<hipStream_t>(stream), uint32_t(n_states), recs8, rec_off, n_bins, order,
-                                           uint32_t(n_slices), tile_off, tiles, status));
-    return AVR_OK;
+    return pack_tiles8_device(true, device, stream, n_states, Slices{recs8, rec_off, n_bins, order, uint32_t(n_slices)}, n_slices, tile_off, tiles, status);
 }
 
 int avr_cabac8_encode_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
@@ -1197,52 +1174,104 @@ int avr_cabac8_encode_tiles_device(int device, void *stream, const void *tiles, 
     if (n_slices && (!tiles || !out || !out_len || !status || (n_states && !init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
     if (reinterpret_cast<uintptr_t>(tiles) & 15) return fail(AVR_ERR_INVALID, "tiles is not 16-byte aligned");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_cabac8_encode(static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices), init_states,
-                                      uint32_t(n_states), out, out_off, out_len, status, final_states));
+    AVR_HIP(avr::launch_cabac8_encode(hip(stream), Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true},
+                                      States{init_states, uint32_t(n_states), final_states}, Output{out, out_off, out_len, status}));
     return AVR_OK;
 }
 
+// the one-lane-per-slice K1 coder over two-byte tiles or slice-major records, sized by the device's count or (counts: the hinted form)
+// by the caller's guess
+static int cabac_encode_device(int device, void *stream, const Slices &in, size_t n_slices, const States &st, size_t n_states, const Output &o,
+                               uint32_t *counts = nullptr, uint32_t rows_hint = 0) {
+    if (int rc = check_common(in.off, in.n_bins, o.out_off, n_slices)) return rc;
+    if (int rc = check_states(n_states)) return rc;
+    if (int rc = select_device(device)) return rc;
+    if (!counts) {
+        AVR_HIP(avr::launch_cabac_encode(hip(stream), in, st, o));
+        return AVR_OK;
+    }
+    counts[0] = counts[1] = 0;
+    const avr::DenseHint hint{std::min<uint32_t>(rows_hint, uint32_t(n_states)), counts, nullptr};
+    AVR_HIP(avr::launch_cabac_encode(hip(stream), in, st, o, AVR_SLICE_OK, true, &hint));
+    return AVR_OK;
+}
 int avr_cabac_encode_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                   uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states) {
-    if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_cabac_encode(true, static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices),
-                                     init_states, uint32_t(n_states), out, out_off, out_len, status, final_states));
-    return AVR_OK;
+    return cabac_encode_device(device, stream, Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true}, n_slices,
+                               States{init_states, uint32_t(n_states), final_states}, n_states, Output{out, out_off, out_len, status});
+}
+int avr_cabac_encode_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                   uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states) {
+    return cabac_encode_device(device, stream, Slices{recs, rec_off, n_bins, order, uint32_t(n_slices)}, n_slices,
+                               States{init_states, uint32_t(n_states), final_states}, n_states, Output{out, out_off, out_len, status});
+}
+int avr_cabac_encode_tiles_device_hinted(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
+                                         const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
+                                         uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states,
+                                         uint32_t rows_hint, uint32_t *counts) {
+    if (!counts) return fail(AVR_ERR_INVALID, "null counts");
+    return cabac_encode_device(device, stream, Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true}, n_slices,
+                               States{init_states, uint32_t(n_states), final_states}, n_states, Output{out, out_off, out_len, status}, counts, rows_hint);
 }
 
+// the K2 coder and its verifier, over tiles or slice-major records
+static int range_encode_device(int device, void *stream, const Slices &in, size_t n_slices, const Output &o) {
+    if (int rc = check_common(in.off, in.n_bins, o.out_off, n_slices)) return rc;
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_range_encode(hip(stream), in, o));
+    return AVR_OK;
+}
 int avr_range_encode_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
                                   const uint32_t *order, size_t n_slices, uint8_t *out, const uint64_t *out_off,
                                   uint32_t *out_len, int32_t *status) {
-    if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_range_encode(true, static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices),
-                                     out, out_off, out_len, status));
-    return AVR_OK;
+    return range_encode_device(device, stream, Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true}, n_slices, Output{out, out_off, out_len, status});
+}
+int avr_range_encode_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, uint8_t *out, const uint64_t *out_off,
+                                   uint32_t *out_len, int32_t *status) {
+    return range_encode_device(device, stream, Slices{recs, rec_off, n_bins, order, uint32_t(n_slices)}, n_slices, Output{out, out_off, out_len, status});
 }
 
+static int range_verify_device(int device, void *stream, const Slices &in, size_t n_slices, const OutputView &o, uint32_t *first_bad, bool need_first_bad) {
+    if (int rc = check_common(in.off, in.n_bins, o.out_off, n_slices)) return rc;
+    if (n_slices && (!in.recs || !o.out || !o.out_len || !o.status || (need_first_bad && !first_bad))) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_range_verify(hip(stream), in, o, first_bad));
+    return AVR_OK;
+}
 int avr_range_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
                                   const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
                                   const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
-    if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
-    if (n_slices && (!tiles || !out || !out_len || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_range_verify(true, static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices),
-                                     out, out_off, out_len, status, first_bad));
+    return range_verify_device(device, stream, Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true}, n_slices,
+                               OutputView{out, out_off, out_len, status}, first_bad, false);
+}
+int avr_range_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
+                                   const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
+                                   const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
+    return range_verify_device(device, stream, Slices{recs, rec_off, n_bins, order, uint32_t(n_slices)}, n_slices,
+                               OutputView{out, out_off, out_len, status}, first_bad, true);
+}
+
+static int check_plan(const avr_chunk_plan *plan, size_t n_slices, bool need_blocks) {
+    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->dig_off ||
+                               (need_blocks && (!plan->blk_base || !plan->blk_slice)))))
+        return fail(AVR_ERR_INVALID, "null plan pointer");
     return AVR_OK;
 }
 
-static int check_chunked(const uint64_t *rec_off, const uint32_t *n_bins, const uint64_t *out_off, size_t n_slices, size_t n_states,
-                         const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, const int32_t *status) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
-    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->blk_base || !plan->blk_slice ||
-                               !plan->dig_off || !workspace || !status)))
-        return fail(AVR_ERR_INVALID, "null plan pointer");
+// The refusals of the chunked K1 family.  The one-byte form (recs8) has its own limit on n_states, holds its records to their
+// alignment, checks more of the caller's pointers and reads no blocks of the plan; the rest is the same.
+static int check_chunked(const Slices &in, size_t n_slices, const States &st, size_t n_states, const avr_chunk_plan *plan, void *workspace,
+                         size_t workspace_bytes, const Output &o, bool recs8 = false) {
+    if (int rc = check_common(in.off, in.n_bins, o.out_off, n_slices)) return rc;
+    if (int rc = recs8 ? check_recs8(in.recs, in.off, n_states) : check_states(n_states)) return rc;
+    if (recs8 && n_slices && (!in.recs || !o.out || !o.out_len || (n_states && !st.init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (int rc = check_plan(plan, n_slices, !recs8)) return rc;
+    if (n_slices && (!workspace || !o.status)) return fail(AVR_ERR_INVALID, "null plan pointer");
     if (workspace_bytes < avr::k1p_layout(n_slices, uint32_t(n_states), plan).total)
-        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac_chunked_workspace_bytes()", workspace_bytes);
+        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than %s_chunked_workspace_bytes()", workspace_bytes, recs8 ? "avr_cabac8" : "avr_cabac");
     return AVR_OK;
 }
 
@@ -1250,37 +1279,34 @@ size_t avr_cabac_chunked_workspace_bytes(size_t n_slices, size_t n_states, const
     if (!plan || n_states > AVR_MAX_STATES) return 0;
     return avr::k1p_layout(n_slices, uint32_t(n_states), plan).total;
 }
+size_t avr_cabac8_chunked_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan) {
+    if (!plan || n_states > AVR_MAX_STATES8) return 0;
+    return avr::k1p_layout(n_slices, uint32_t(n_states), plan).total;
+}
 
 int avr_cabac_encode_chunked_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                                     size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
                                     void *workspace, size_t workspace_bytes, uint8_t *out, const uint64_t *out_off,
                                     uint32_t *out_len, int32_t *status, uint8_t *final_states) {
-    if (int rc = check_chunked(rec_off, n_bins, out_off, n_slices, n_states, plan, workspace, workspace_bytes, status)) return rc;
+    const Slices in{recs, rec_off, n_bins, nullptr, uint32_t(n_slices)};
+    const States st{init_states, uint32_t(n_states), final_states};
+    const Output o{out, out_off, out_len, status};
+    if (int rc = check_chunked(in, n_slices, st, n_states, plan, workspace, workspace_bytes, o)) return rc;
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
-                            avr::K1pIo{init_states, out, out_off, out_len, status, final_states}));
+    AVR_HIP(avr::launch_k1p(hip(stream), in, st, plan, workspace, o));
     return AVR_OK;
-}
-
-size_t avr_cabac8_chunked_workspace_bytes(size_t n_slices, size_t n_states, const avr_chunk_plan *plan) {
-    if (!plan || n_states > AVR_MAX_STATES8) return 0;
-    return avr::k1p_layout(n_slices, uint32_t(n_states), plan).total;
 }
 
 int avr_cabac8_encode_chunked_device(int device, void *stream, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
                                      size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
                                      void *workspace, size_t workspace_bytes, uint8_t *out, const uint64_t *out_off,
                                      uint32_t *out_len, int32_t *status, uint8_t *final_states) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (int rc = check_recs8(recs8, rec_off, n_states)) return rc;
-    if (n_slices && (!recs8 || !out || !out_len || (n_states && !init_states))) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->dig_off || !workspace || !status)))
-        return fail(AVR_ERR_INVALID, "null plan pointer");
-    if (workspace_bytes < avr::k1p_layout(n_slices, uint32_t(n_states), plan).total)
-        return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_cabac8_chunked_workspace_bytes()", workspace_bytes);
+    const Slices in{recs8, rec_off, n_bins, nullptr, uint32_t(n_slices)};
+    const States st{init_states, uint32_t(n_states), final_states};
+    const Output o{out, out_off, out_len, status};
+    if (int rc = check_chunked(in, n_slices, st, n_states, plan, workspace, workspace_bytes, o, true)) return rc;
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k1p8(static_cast<hipStream_t>(stream), recs8, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
-                             avr::K1pIo{init_states, out, out_off, out_len, status, final_states}));
+    AVR_HIP(avr::launch_k1p8(hip(stream), in, st, plan, workspace, o));
     return AVR_OK;
 }
 
@@ -1288,14 +1314,16 @@ int avr_cabac_encode_chunked_device_hinted(int device, void *stream, const uint1
                                            size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
                                            void *workspace, size_t workspace_bytes, uint8_t *out, const uint64_t *out_off,
                                            uint32_t *out_len, int32_t *status, uint8_t *final_states, uint32_t rows_hint, uint32_t *counts) {
+    const Slices in{recs, rec_off, n_bins, nullptr, uint32_t(n_slices)};
+    const States st{init_states, uint32_t(n_states), final_states};
+    const Output o{out, out_off, out_len, status};
     if (!counts) return fail(AVR_ERR_INVALID, "null counts");
-    if (int rc = check_chunked(rec_off, n_bins, out_off, n_slices, n_states, plan, workspace, workspace_bytes, status)) return rc;
+    if (int rc = check_chunked(in, n_slices, st, n_states, plan, workspace, workspace_bytes, o)) return rc;
     if (int rc = select_device(device)) return rc;
     counts[0] = counts[1] = 0;
     if (n_slices == 0) return AVR_OK;
     const avr::DenseHint hint{std::min<uint32_t>(rows_hint, uint32_t(n_states)), counts, counts + 1};
-    AVR_HIP(avr::launch_k1p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
-                            avr::K1pIo{init_states, out, out_off, out_len, status, final_states}, &hint));
+    AVR_HIP(avr::launch_k1p(hip(stream), in, st, plan, workspace, o, &hint));
     return AVR_OK;
 }
 
@@ -1303,26 +1331,13 @@ int avr_cabac_encode_chunked_second_pass_device(int device, void *stream, const 
                                                 size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
                                                 void *workspace, size_t workspace_bytes, uint8_t *out, const uint64_t *out_off,
                                                 uint32_t *out_len, int32_t *status, uint8_t *final_states) {
-    if (int rc = check_chunked(rec_off, n_bins, out_off, n_slices, n_states, plan, workspace, workspace_bytes, status)) return rc;
+    const Slices in{recs, rec_off, n_bins, nullptr, uint32_t(n_slices)};
+    const States st{init_states, uint32_t(n_states), final_states};
+    const Output o{out, out_off, out_len, status};
+    if (int rc = check_chunked(in, n_slices, st, n_states, plan, workspace, workspace_bytes, o)) return rc;
     if (int rc = select_device(device)) return rc;
     if (n_slices == 0) return AVR_OK;
-    AVR_HIP(avr::launch_k1p_retry(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), uint32_t(n_states), plan, workspace,
-                                  avr::K1pIo{init_states, out, out_off, out_len, status, final_states}));
-    return AVR_OK;
-}
-
-int avr_cabac_encode_tiles_device_hinted(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
-                                         const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
-                                         uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states,
-                                         uint32_t rows_hint, uint32_t *counts) {
-    if (!counts) return fail(AVR_ERR_INVALID, "null counts");
-    if (int rc = check_common(tile_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
-    if (int rc = select_device(device)) return rc;
-    counts[0] = counts[1] = 0;
-    const avr::DenseHint hint{std::min<uint32_t>(rows_hint, uint32_t(n_states)), counts, nullptr};
-    AVR_HIP(avr::launch_cabac_encode(true, static_cast<hipStream_t>(stream), tiles, tile_off, n_bins, order, uint32_t(n_slices),
-                                     init_states, uint32_t(n_states), out, out_off, out_len, status, final_states, AVR_SLICE_OK, true, &hint));
+    AVR_HIP(avr::launch_k1p_retry(hip(stream), in, st, plan, workspace, o));
     return AVR_OK;
 }
 
@@ -1358,16 +1373,23 @@ void forget_part_streams(hipStream_t s) {
 }  // namespace avr
 }  // extern "C++"
 
+// a part's arrays, with what the parts share
+static Slices part_slices(const uint16_t *recs, const avr_chunked_part &q) { return {recs, q.rec_off, q.n_bins, nullptr, uint32_t(q.n_slices)}; }
+static States part_states(size_t n_states, const avr_chunked_part &q) { return {q.init_states, uint32_t(n_states), q.final_states}; }
+static Output part_output(uint8_t *out, const avr_chunked_part &q) { return {out, q.out_off, q.out_len, q.status}; }
+
 int avr_cabac_encode_chunked_device_parts(int device, void *stream, const uint16_t *recs, size_t n_states, uint8_t *out,
                                           const avr_chunked_part *parts, size_t n_parts) {
     if (!parts || n_parts == 0 || n_parts > AVR_MAX_PARTS) return fail(AVR_ERR_INVALID, "1 .. %d parts", AVR_MAX_PARTS);
     for (size_t i = 0; i < n_parts; i++) {
         const avr_chunked_part &q = parts[i];
         if (!q.counts) return fail(AVR_ERR_INVALID, "part %zu: null counts", i);
-        if (int rc = check_chunked(q.rec_off, q.n_bins, q.out_off, q.n_slices, n_states, q.plan, q.workspace, q.workspace_bytes, q.status)) return rc;
+        if (int rc = check_chunked(part_slices(recs, q), q.n_slices, part_states(n_states, q), n_states, q.plan, q.workspace, q.workspace_bytes,
+                                   part_output(out, q)))
+            return rc;
     }
     if (int rc = select_device(device)) return rc;
-    hipStream_t main = static_cast<hipStream_t>(stream);
+    hipStream_t main = hip(stream);
     PartStreams *ps = nullptr;
     if (n_parts > 1) {
         AVR_HIP(part_streams(main, &ps));
@@ -1380,8 +1402,7 @@ int avr_cabac_encode_chunked_device_parts(int device, void *stream, const uint16
         q.counts[0] = q.counts[1] = 0;
         if (q.n_slices) {
             const avr::DenseHint hint{std::min<uint32_t>(q.rows_hint, uint32_t(n_states)), q.counts, q.counts + 1, uint32_t(n_parts)};
-            AVR_HIP(avr::launch_k1p(s, recs, q.rec_off, q.n_bins, uint32_t(q.n_slices), uint32_t(n_states), q.plan, q.workspace,
-                                    avr::K1pIo{q.init_states, out, q.out_off, q.out_len, q.status, q.final_states}, &hint));
+            AVR_HIP(avr::launch_k1p(s, part_slices(recs, q), part_states(n_states, q), q.plan, q.workspace, part_output(out, q), &hint));
         }
         if (i) AVR_HIP(hipEventRecord(ps->done[i - 1], s));
     }
@@ -1403,8 +1424,8 @@ int avr_range_encode_chunked_device(int device, void *stream, const uint16_t *re
     if (workspace_bytes < avr::k2p_layout(n_slices, plan->total_chunks, out_total).total)
         return fail(AVR_ERR_CAPACITY, "workspace of %zu bytes is smaller than avr_range_chunked_workspace_bytes()", workspace_bytes);
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k2p(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), plan->chunk_base,
-                            plan->chunk_slice, plan->total_chunks, out_total, workspace, out, out_off, out_len, status));
+    AVR_HIP(avr::launch_k2p(hip(stream), Slices{recs, rec_off, n_bins, nullptr, uint32_t(n_slices)}, plan, out_total, workspace,
+                            Output{out, out_off, out_len, status}));
     return AVR_OK;
 }
 
@@ -1412,68 +1433,57 @@ size_t avr_range_resolve_workspace_bytes(size_t n_slices, size_t n_groups, const
     if (!plan) return 0;
     return avr::est_layout(n_slices, n_groups, plan->total_chunks).total;
 }
-
-int avr_range_resolve_device(int device, void *stream, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins,
-                             size_t n_slices, const uint32_t *group_first, size_t n_groups, const uint8_t *est_in, uint8_t *est_out,
-                             const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, uint16_t *recs_out, int32_t *status) {
-    if (int rc = check_common(rec_off, n_bins, keys, n_slices)) return rc;
-    if (n_groups > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_groups out of range");
-    if (n_slices && (n_groups == 0 || n_groups > n_slices))
-        return fail(AVR_ERR_INVALID, "n_groups %zu: a batch of %zu slices has between 1 and %zu groups", n_groups, n_slices, n_slices);
-    if (n_slices && (!group_first || !recs_out || !status)) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice))) return fail(AVR_ERR_INVALID, "null plan pointer");
-    if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
-    if (workspace_bytes < avr::est_layout(n_slices, n_groups, plan->total_chunks).total)
-        return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than avr_range_resolve_workspace_bytes()", workspace_bytes);
-    if (n_slices && recs_out == keys) return fail(AVR_ERR_INVALID, "recs_out must not alias keys");
-    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(recs_out)) & 15)
-        return fail(AVR_ERR_INVALID, "keys / recs_out not 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(est_in) | reinterpret_cast<uintptr_t>(est_out)) & 1)
-        return fail(AVR_ERR_INVALID, "est_in / est_out not 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AVR_ERR_INVALID, "workspace not 256-byte aligned");
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_est_resolve(static_cast<hipStream_t>(stream), keys, rec_off, n_bins, uint32_t(n_slices), group_first,
-                                    uint32_t(n_groups), est_in, est_out, plan->chunk_base, plan->chunk_slice, plan->total_chunks,
-                                    workspace, recs_out, status));
-    return AVR_OK;
-}
-
 size_t avr_range_keys_verify_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan) {
     (void)n_groups;
     if (!plan) return 0;
     return avr::est_verify_layout(n_slices, plan->total_chunks).total;
 }
 
+// The refusals of the estimator resolver and of its checker.  other: the call's second array of records, `name` in the header;
+// rest: whether the call's remaining pointers are there; quote: what sizes the call's workspace.
+static int check_est(const Slices &keys, size_t n_slices, const void *other, const char *name, const uint32_t *group_first, size_t n_groups,
+                     const uint8_t *est_in, const uint8_t *est_out, const avr_chunk_plan *plan, const void *workspace, size_t workspace_bytes,
+                     bool rest, size_t (*quote)(size_t, size_t, const avr_chunk_plan *), const char *quote_name) {
+    if (int rc = check_common(keys.off, keys.n_bins, keys.recs, n_slices)) return rc;
+    if (n_groups > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_groups out of range");
+    if (n_slices && (n_groups == 0 || n_groups > n_slices))
+        return fail(AVR_ERR_INVALID, "n_groups %zu: a batch of %zu slices has between 1 and %zu groups", n_groups, n_slices, n_slices);
+    if (n_slices && (!group_first || !other || !rest)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice))) return fail(AVR_ERR_INVALID, "null plan pointer");
+    if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
+    if (workspace_bytes < quote(n_slices, n_groups, plan))
+        return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than %s()", workspace_bytes, quote_name);
+    if (n_slices && other == keys.recs) return fail(AVR_ERR_INVALID, "%s must not alias keys", name);
+    if ((reinterpret_cast<uintptr_t>(keys.recs) | reinterpret_cast<uintptr_t>(other)) & 15)
+        return fail(AVR_ERR_INVALID, "keys / %s not 16-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(est_in) | reinterpret_cast<uintptr_t>(est_out)) & 1)
+        return fail(AVR_ERR_INVALID, "est_in / est_out not 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AVR_ERR_INVALID, "workspace not 256-byte aligned");
+    return AVR_OK;
+}
+
+int avr_range_resolve_device(int device, void *stream, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins,
+                             size_t n_slices, const uint32_t *group_first, size_t n_groups, const uint8_t *est_in, uint8_t *est_out,
+                             const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, uint16_t *recs_out, int32_t *status) {
+    const Slices in{keys, rec_off, n_bins, nullptr, uint32_t(n_slices)};
+    if (int rc = check_est(in, n_slices, recs_out, "recs_out", group_first, n_groups, est_in, est_out, plan, workspace, workspace_bytes, status != nullptr,
+                           avr_range_resolve_workspace_bytes, "avr_range_resolve_workspace_bytes"))
+        return rc;
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_est_resolve(hip(stream), in, group_first, uint32_t(n_groups), est_in, est_out, plan, workspace, recs_out, status));
+    return AVR_OK;
+}
+
 int avr_range_keys_verify_device(int device, void *stream, const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off,
                                  const uint32_t *n_bins, size_t n_slices, const uint32_t *group_first, size_t n_groups,
                                  const uint8_t *est_in, const uint8_t *est_out, const avr_chunk_plan *plan, void *workspace,
                                  size_t workspace_bytes, int32_t *status, uint32_t *first_bad) {
-    if (int rc = check_common(rec_off, n_bins, keys, n_slices)) return rc;
-    if (n_groups > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_groups out of range");
-    if (n_slices && (n_groups == 0 || n_groups > n_slices))
-        return fail(AVR_ERR_INVALID, "n_groups %zu: a batch of %zu slices has between 1 and %zu groups", n_groups, n_slices, n_slices);
-    if (n_slices && (!group_first || !recs || !status || !first_bad)) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (!plan || (n_slices && (!plan->chunk_base || !plan->chunk_slice))) return fail(AVR_ERR_INVALID, "null plan pointer");
-    if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
-    if (workspace_bytes < avr::est_verify_layout(n_slices, plan->total_chunks).total)
-        return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than avr_range_keys_verify_workspace_bytes()", workspace_bytes);
-    if (n_slices && recs == keys) return fail(AVR_ERR_INVALID, "recs must not alias keys");
-    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(recs)) & 15)
-        return fail(AVR_ERR_INVALID, "keys / recs not 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(est_in) | reinterpret_cast<uintptr_t>(est_out)) & 1)
-        return fail(AVR_ERR_INVALID, "est_in / est_out not 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AVR_ERR_INVALID, "workspace not 256-byte aligned");
+    const Slices in{keys, rec_off, n_bins, nullptr, uint32_t(n_slices)};
+    if (int rc = check_est(in, n_slices, recs, "recs", group_first, n_groups, est_in, est_out, plan, workspace, workspace_bytes, status && first_bad,
+                           avr_range_keys_verify_workspace_bytes, "avr_range_keys_verify_workspace_bytes"))
+        return rc;
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_est_verify(static_cast<hipStream_t>(stream), keys, recs, rec_off, n_bins, uint32_t(n_slices), group_first,
-                                   uint32_t(n_groups), est_in, est_out, plan->chunk_base, plan->chunk_slice, plan->total_chunks,
-                                   workspace, status, first_bad));
-    return AVR_OK;
-}
-
-static int check_plan(const avr_chunk_plan *plan, size_t n_slices, bool need_blocks) {
-    if (!plan || (n_slices && (!plan->res_off || !plan->chunk_base || !plan->chunk_slice || !plan->dig_off ||
-                               (need_blocks && (!plan->blk_base || !plan->blk_slice)))))
-        return fail(AVR_ERR_INVALID, "null plan pointer");
+    AVR_HIP(avr::launch_est_verify(hip(stream), in, recs, group_first, uint32_t(n_groups), est_in, est_out, plan, workspace, status, first_bad));
     return AVR_OK;
 }
 
@@ -1486,14 +1496,14 @@ int avr_cabac_resolve_device(int device, void *stream, const uint16_t *recs, con
                              size_t n_slices, const uint8_t *init_states, size_t n_states, const avr_chunk_plan *plan,
                              void *workspace, size_t workspace_bytes, uint8_t *codes, int32_t *status, uint8_t *final_states) {
     if (int rc = check_common(rec_off, n_bins, codes, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
+    if (int rc = check_states(n_states)) return rc;
     if (int rc = check_plan(plan, n_slices, true)) return rc;
     if (n_slices && (!workspace || !status)) return fail(AVR_ERR_INVALID, "null workspace / status");
     if (workspace_bytes < avr::resolve_layout(n_slices, uint32_t(n_states), plan).total)
         return fail(AVR_ERR_CAPACITY, "workspace smaller than avr_cabac_resolve_workspace_bytes()");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k1p_resolve(static_cast<hipStream_t>(stream), recs, rec_off, n_bins, uint32_t(n_slices), init_states,
-                                    uint32_t(n_states), plan, workspace, codes, status, final_states));
+    AVR_HIP(avr::launch_k1p_resolve(hip(stream), Slices{recs, rec_off, n_bins, nullptr, uint32_t(n_slices)},
+                                    States{init_states, uint32_t(n_states), final_states}, plan, workspace, codes, status));
     return AVR_OK;
 }
 
@@ -1510,8 +1520,8 @@ int avr_cabac_encode_resolved_device(int device, void *stream, const uint8_t *co
     if (workspace_bytes < avr::code_layout(n_slices, plan).total)
         return fail(AVR_ERR_CAPACITY, "workspace smaller than avr_cabac_resolved_workspace_bytes()");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_k1p_code(static_cast<hipStream_t>(stream), codes, n_bins, uint32_t(n_slices), plan, workspace, out, out_off,
-                                 out_len, status));
+    AVR_HIP(avr::launch_k1p_code(hip(stream), Slices{codes, plan->res_off, n_bins, nullptr, uint32_t(n_slices)}, plan, workspace,
+                                 Output{out, out_off, out_len, status}));
     return AVR_OK;
 }
 
@@ -1521,56 +1531,20 @@ int avr_cabac_encode_codes_device(int device, void *stream, const uint8_t *codes
     if (int rc = check_common(codes, n_bins, out_off, n_slices)) return rc;
     if (n_slices && (!res_off || !status || !out_len)) return fail(AVR_ERR_INVALID, "null device pointer");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_cabac_encode_codes(static_cast<hipStream_t>(stream), codes, res_off, n_bins, order, uint32_t(n_slices), out,
-                                           out_off, out_len, status));
-    return AVR_OK;
-}
-
-int avr_cabac_encode_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
-                                   uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint8_t *final_states) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_cabac_encode(false, static_cast<hipStream_t>(stream), recs, rec_off, n_bins, order, uint32_t(n_slices),
-                                     init_states, uint32_t(n_states), out, out_off, out_len, status, final_states));
-    return AVR_OK;
-}
-
-int avr_range_encode_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                                   const uint32_t *order, size_t n_slices, uint8_t *out, const uint64_t *out_off,
-                                   uint32_t *out_len, int32_t *status) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_range_encode(false, static_cast<hipStream_t>(stream), recs, rec_off, n_bins, order, uint32_t(n_slices),
-                                     out, out_off, out_len, status));
-    return AVR_OK;
-}
-
-int avr_range_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                                   const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
-                                   const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
-    if (int rc = check_common(rec_off, n_bins, out_off, n_slices)) return rc;
-    if (n_slices && (!recs || !out || !out_len || !status || !first_bad)) return fail(AVR_ERR_INVALID, "null device pointer");
-    if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_range_verify(false, static_cast<hipStream_t>(stream), recs, rec_off, n_bins, order, uint32_t(n_slices),
-                                     out, out_off, out_len, status, first_bad));
+    AVR_HIP(avr::launch_cabac_encode_codes(hip(stream), Slices{codes, res_off, n_bins, order, uint32_t(n_slices)}, Output{out, out_off, out_len, status}));
     return AVR_OK;
 }
 
 // The K1 verifier's five forms (avr_cabac_verify.hip).  One body: the checks that need no device, then the launch.
-static int cabac_verify_device(int form, int device, void *stream, const void *recs, const uint64_t *off, const uint32_t *n_bins,
-                               const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states, const uint8_t *out,
-                               const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states, int32_t *status,
+static int cabac_verify_device(int device, void *stream, const Slices &in, size_t n_slices, const StatesView &st, size_t n_states, const OutputView &o,
                                uint32_t *first_bad, bool need_first_bad) {
-    if (int rc = check_common(off, n_bins, out_off, n_slices)) return rc;
-    const size_t limit = avr::cabac_verify::form_max_states(form);
+    if (int rc = check_common(in.off, in.n_bins, o.out_off, n_slices)) return rc;
+    const size_t limit = avr::cabac_verify::form_max_states(in.form);
     if (n_states > limit) return fail(AVR_ERR_INVALID, "n_states %zu > %zu", n_states, limit);
-    if (n_slices && (!recs || !out || !out_len || !status || (need_first_bad && !first_bad) || (n_states && !init_states)))
+    if (n_slices && (!in.recs || !o.out || !o.out_len || !o.status || (need_first_bad && !first_bad) || (n_states && !st.init_states)))
         return fail(AVR_ERR_INVALID, "null device pointer");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_cabac_verify(form, static_cast<hipStream_t>(stream), recs, off, n_bins, order, uint32_t(n_slices), init_states,
-                                     uint32_t(n_states), out, out_off, out_len, final_states, status, first_bad));
+    AVR_HIP(avr::launch_cabac_verify(hip(stream), in, st, o, first_bad));
     return AVR_OK;
 }
 
@@ -1578,39 +1552,39 @@ int avr_cabac_verify_tiles_device(int device, void *stream, const void *tiles, c
                                   const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                   const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
                                   int32_t *status, uint32_t *first_bad) {
-    return cabac_verify_device(avr::cabac_verify::kTiles2, device, stream, tiles, tile_off, n_bins, order, n_slices, init_states, n_states,
-                               out, out_off, out_len, final_states, status, first_bad, false);
+    return cabac_verify_device(device, stream, Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true, avr::cabac_verify::kTiles2}, n_slices,
+                               StatesView{init_states, uint32_t(n_states), final_states}, n_states, OutputView{out, out_off, out_len, status}, first_bad, false);
 }
 
 int avr_cabac_verify_slices_device(int device, void *stream, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
                                    const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                    const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
                                    int32_t *status, uint32_t *first_bad) {
-    return cabac_verify_device(avr::cabac_verify::kSlices2, device, stream, recs, rec_off, n_bins, order, n_slices, init_states, n_states,
-                               out, out_off, out_len, final_states, status, first_bad, true);
+    return cabac_verify_device(device, stream, Slices{recs, rec_off, n_bins, order, uint32_t(n_slices), false, avr::cabac_verify::kSlices2}, n_slices,
+                               StatesView{init_states, uint32_t(n_states), final_states}, n_states, OutputView{out, out_off, out_len, status}, first_bad, true);
 }
 
 int avr_cabac8_verify_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,
                                    const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                    const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
                                    int32_t *status, uint32_t *first_bad) {
-    return cabac_verify_device(avr::cabac_verify::kTiles8, device, stream, tiles, tile_off, n_bins, order, n_slices, init_states, n_states,
-                               out, out_off, out_len, final_states, status, first_bad, false);
+    return cabac_verify_device(device, stream, Slices{tiles, tile_off, n_bins, order, uint32_t(n_slices), true, avr::cabac_verify::kTiles8}, n_slices,
+                               StatesView{init_states, uint32_t(n_states), final_states}, n_states, OutputView{out, out_off, out_len, status}, first_bad, false);
 }
 
 int avr_cabac8_verify_slices_device(int device, void *stream, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
                                     const uint32_t *order, size_t n_slices, const uint8_t *init_states, size_t n_states,
                                     const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
                                     int32_t *status, uint32_t *first_bad) {
-    return cabac_verify_device(avr::cabac_verify::kSlices8, device, stream, recs8, rec_off, n_bins, order, n_slices, init_states, n_states,
-                               out, out_off, out_len, final_states, status, first_bad, true);
+    return cabac_verify_device(device, stream, Slices{recs8, rec_off, n_bins, order, uint32_t(n_slices), false, avr::cabac_verify::kSlices8}, n_slices,
+                               StatesView{init_states, uint32_t(n_states), final_states}, n_states, OutputView{out, out_off, out_len, status}, first_bad, true);
 }
 
 int avr_cabac_verify_codes_device(int device, void *stream, const uint8_t *codes, const uint64_t *res_off, const uint32_t *n_bins,
                                   const uint32_t *order, size_t n_slices, const uint8_t *out, const uint64_t *out_off,
                                   const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
-    return cabac_verify_device(avr::cabac_verify::kCodes, device, stream, codes, res_off, n_bins, order, n_slices, nullptr, 0,
-                               out, out_off, out_len, nullptr, status, first_bad, true);
+    return cabac_verify_device(device, stream, Slices{codes, res_off, n_bins, order, uint32_t(n_slices), false, avr::cabac_verify::kCodes}, n_slices,
+                               StatesView{}, 0, OutputView{out, out_off, out_len, status}, first_bad, true);
 }
 
 // The restore check (avr_restore.hip): the checks that need no device, then the launch.
@@ -1622,8 +1596,7 @@ int avr_restore_check_device(int device, void *stream, const uint8_t *out, const
         return fail(AVR_ERR_INVALID, "null device pointer");
     if (reinterpret_cast<uintptr_t>(expect) & 7) return fail(AVR_ERR_INVALID, "expect is not 8-byte aligned");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_restore_check(static_cast<hipStream_t>(stream), out, out_off, out_len, uint32_t(n_slices), expect, expect_off,
-                                      expect_len, status, first_diff));
+    AVR_HIP(avr::launch_restore_check(hip(stream), OutputView{out, out_off, out_len, status}, uint32_t(n_slices), expect, expect_off, expect_len, first_diff));
     return AVR_OK;
 }
 
@@ -1632,14 +1605,14 @@ int avr_restore_check_device(int device, void *stream, const uint8_t *out, const
 int avr_context_census_device(int device, void *stream, const uint16_t *recs, uint64_t n_records, uint32_t *bitmap) {
     if ((n_records && !recs) || !bitmap || (n_records & 7)) return fail(AVR_ERR_INVALID, "bad argument (n_records must be a multiple of 8)");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_context_census(static_cast<hipStream_t>(stream), recs, n_records, bitmap));
+    AVR_HIP(avr::launch_context_census(hip(stream), recs, n_records, bitmap));
     return AVR_OK;
 }
 
 int avr_context_remap_device(int device, void *stream, uint16_t *recs, uint64_t n_records, const uint16_t *table) {
     if ((n_records && !recs) || !table || (n_records & 7)) return fail(AVR_ERR_INVALID, "bad argument (n_records must be a multiple of 8)");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_context_remap(static_cast<hipStream_t>(stream), recs, n_records, table));
+    AVR_HIP(avr::launch_context_remap(hip(stream), recs, n_records, table));
     return AVR_OK;
 }
 
@@ -1648,7 +1621,7 @@ int avr_states_permute_device(int device, void *stream, const uint8_t *src, size
     if (n_slices && n_index && (!src || !dst || !index)) return fail(AVR_ERR_INVALID, "null pointer");
     if (n_src > AVR_MAX_STATES || n_dst > AVR_MAX_STATES || n_index > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "more than %d states", AVR_MAX_STATES);
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_states_permute(static_cast<hipStream_t>(stream), src, uint32_t(n_src), dst, uint32_t(n_dst), index,
+    AVR_HIP(avr::launch_states_permute(hip(stream), src, uint32_t(n_src), dst, uint32_t(n_dst), index,
                                        uint32_t(n_index), n_slices, scatter));
     return AVR_OK;
 }
@@ -1709,7 +1682,7 @@ int avr_synth_generate_host(const avr_synth_config *cfg, int kind, size_t n_slic
 int avr_synth_count_device(int device, void *stream, const avr_synth_config *cfg, int kind, size_t n_slices, uint32_t *n_bins) {
     if (!cfg || (!n_bins && n_slices) || n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "bad argument");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_synth_count(static_cast<hipStream_t>(stream), cfg->workload, cfg->scale_permille, cfg->seed, cfg->first_slice,
+    AVR_HIP(avr::launch_synth_count(hip(stream), cfg->workload, cfg->scale_permille, cfg->seed, cfg->first_slice,
                                     kind, uint32_t(n_slices), n_bins));
     return AVR_OK;
 }
@@ -1718,7 +1691,7 @@ int avr_synth_generate_slices_device(int device, void *stream, const avr_synth_c
                                      const uint64_t *rec_off, uint16_t *recs, uint8_t *init_states) {
     if (!cfg || ((!rec_off || !recs) && n_slices) || n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "bad argument");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_synth_slices(static_cast<hipStream_t>(stream), cfg->workload, cfg->scale_permille, cfg->seed, cfg->first_slice,
+    AVR_HIP(avr::launch_synth_slices(hip(stream), cfg->workload, cfg->scale_permille, cfg->seed, cfg->first_slice,
                                      kind, uint32_t(n_slices), rec_off, recs, init_states, cfg->n_states));
     return AVR_OK;
 }
@@ -1727,7 +1700,7 @@ int avr_synth_generate_tiles_device(int device, void *stream, const avr_synth_co
                                     const uint32_t *order, const uint64_t *tile_off, void *tiles, uint8_t *init_states) {
     if (!cfg || ((!tile_off || !tiles) && n_slices) || n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "bad argument");
     if (int rc = select_device(device)) return rc;
-    AVR_HIP(avr::launch_synth_tiles(static_cast<hipStream_t>(stream), cfg->workload, cfg->scale_permille, cfg->seed, cfg->first_slice,
+    AVR_HIP(avr::launch_synth_tiles(hip(stream), cfg->workload, cfg->scale_permille, cfg->seed, cfg->first_slice,
                                     kind, uint32_t(n_slices), order, tile_off, tiles, init_states, cfg->n_states));
     return AVR_OK;
 }

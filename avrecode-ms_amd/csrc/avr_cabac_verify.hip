@@ -131,10 +131,9 @@ __global__ __launch_bounds__(64) void k_cabac_verify(
     }
 }
 
-hipError_t launch_cabac_verify(int form, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
-                               const uint32_t *order, uint32_t n_slices, const uint8_t *init_states, uint32_t n_states,
-                               const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
-                               int32_t *status, uint32_t *first_bad) {
+hipError_t launch_cabac_verify(hipStream_t s, const Slices &in, const StatesView &st, const OutputView &o, uint32_t *first_bad) {
+    const uint32_t n_slices = in.n_slices, n_states = st.n_states;
+    const cabac_verify::Form form = in.form;
     if (n_slices == 0) return hipSuccess;
     // launch_range_verify's rule: tiles are laid out for 64 slices a wave; slice-major batches of few slices (K1p's shape) leave most of
     // the chip idle anyway, so there a wave takes as few slices as still give every SIMD of the chip (1 024) a wave.
@@ -149,8 +148,8 @@ hipError_t launch_cabac_verify(int form, hipStream_t s, const void *recs, const 
         if (e != hipSuccess) return e;
     }
     const dim3 grid((n_slices + per_wave - 1) / per_wave), block(64);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, recs, off, n_bins, order, n_slices, init_states, n_states, out, out_off, out_len,
-                       final_states, status, first_bad, per_wave);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, in.recs, in.off, in.n_bins, in.order, n_slices, st.init_states, n_states, o.out, o.out_off,
+                       o.out_len, st.final_states, o.status, first_bad, per_wave);
     return hipGetLastError();
 }
 

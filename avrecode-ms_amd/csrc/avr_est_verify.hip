@@ -233,16 +233,16 @@ __global__ void k_est_flip(uint16_t *recs, const uint64_t *rec_off, const uint32
 
 }  // namespace
 
-hipError_t launch_est_verify(hipStream_t s, const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                             uint32_t n_slices, const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in,
-                             const uint8_t *est_out, const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks,
-                             void *workspace, int32_t *status, uint32_t *first_bad) {
+hipError_t launch_est_verify(hipStream_t s, const Slices &keys, const uint16_t *recs, const uint32_t *group_first, uint32_t n_groups,
+                             const uint8_t *est_in, const uint8_t *est_out, const avr_chunk_plan *pl, void *workspace, int32_t *status,
+                             uint32_t *first_bad) {
+    const uint32_t n_slices = keys.n_slices, total_chunks = pl->total_chunks;
     if (n_slices == 0 || n_groups == 0) return hipSuccess;
     EstvParams p{};
-    p.keys = keys; p.recs = recs; p.rec_off = rec_off; p.n_bins = n_bins; p.group_first = group_first;
+    p.keys = keys.as<uint16_t>(); p.recs = recs; p.rec_off = keys.off; p.n_bins = keys.n_bins; p.group_first = group_first;
     p.est_in = reinterpret_cast<const uint16_t *>(est_in);
     p.est_out = reinterpret_cast<const uint16_t *>(est_out);
-    p.chunk_base = chunk_base; p.chunk_slice = chunk_slice;
+    p.chunk_base = pl->chunk_base; p.chunk_slice = pl->chunk_slice;
     const EstVerifyLayout L = est_verify_layout(n_slices, total_chunks);
     uint8_t *ws = static_cast<uint8_t *>(workspace);
     p.slice_group = reinterpret_cast<uint32_t *>(ws + L.slice_group);

@@ -120,40 +120,52 @@ public:
 void forget_stream(hipStream_t s);
 void forget_part_streams(hipStream_t s);                      // avr_api.cpp: the streams of avr_cabac_encode_chunked_device_parts kept for s
 
-hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, const uint64_t *off,
-                               const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices,
-                               const uint8_t *init_states, uint32_t n_states, uint8_t *out,
-                               const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                               uint8_t *final_states, int32_t want_status = AVR_SLICE_OK, bool dense = true,
-                               const DenseHint *hint = nullptr);
+// One run's arrays as they travel from the C ABI and the batch to the launchers: one type per role, so that a misplaced array does
+// not compile.  The launchers unpack them where they launch; no kernel takes one.
+namespace cabac_verify { enum Form : int; }                      // avr_cabac_verify.h
+// What an encoder reads, and the verifier behind it reads again: the records (tiles, codes) of n_slices slices.
+struct Slices {
+    const void *recs = nullptr;              // the records (tiles, codes) ...
+    const uint64_t *off = nullptr;           // ... and where each slice's (tile's) begin
+    const uint32_t *n_bins = nullptr;
+    const uint32_t *order = nullptr;         // the slices' order, where the path has one
+    uint32_t n_slices = 0;
+    bool tiled = false;                      // in tiles (one lane per slice), not slice-major
+    cabac_verify::Form form{};               // K1: which of the verifier's forms that is (K2 records are two bytes wide: tiled says it all)
+    template <class T> const T *as() const { return static_cast<const T *>(recs); }
+};
+// The context states of a K1 run, before and after; what only reads them (the verifier) takes the view.
+struct StatesView { const uint8_t *init_states = nullptr; uint32_t n_states = 0; const uint8_t *final_states = nullptr; };
+struct States {
+    const uint8_t *init_states = nullptr; uint32_t n_states = 0; uint8_t *final_states = nullptr;
+    operator StatesView() const { return {init_states, n_states, final_states}; }
+};
+// The coded bytes with their regions, lengths and statuses; the verifiers and the restore check read the bytes and write statuses only.
+struct OutputView { const uint8_t *out = nullptr; const uint64_t *out_off = nullptr; const uint32_t *out_len = nullptr; int32_t *status = nullptr; };
+struct Output {
+    uint8_t *out = nullptr; const uint64_t *out_off = nullptr; uint32_t *out_len = nullptr; int32_t *status = nullptr;
+    operator OutputView() const { return {out, out_off, out_len, status}; }
+};
+
+hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st, const Output &o, int32_t want_status = AVR_SLICE_OK,
+                               bool dense = true, const DenseHint *hint = nullptr);
 // used (1024 bits) -> table[caller's context number] = dense id (0xffff: unused), index[dense id] = caller's number, *n_dense
 hipError_t launch_densemap(hipStream_t s, const uint32_t *used, uint16_t *table, uint16_t *index, uint32_t *n_dense);
-hipError_t launch_range_encode(bool tiled, hipStream_t s, const void *recs, const uint64_t *off,
-                               const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices,
-                               uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
-                               int32_t *status);
+hipError_t launch_range_encode(hipStream_t s, const Slices &in, const Output &o);
 // the K2 verifier (avr_verify.hip): decodes every AVR_SLICE_OK slice back against its records; writes status and first_bad only
-hipError_t launch_range_verify(bool tiled, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
-                               const uint32_t *order, uint32_t n_slices, const uint8_t *out, const uint64_t *out_off,
-                               const uint32_t *out_len, int32_t *status, uint32_t *first_bad);
-// the K1 verifier (avr_cabac_verify.hip): the CABAC decoder of H.264 9.3.3.2 over every AVR_SLICE_OK slice and its records; `form` is a
-// cabac_verify::Form (avr_cabac_verify.h: 0 / 1 two-byte tiles / slices, 2 / 3 one-byte tiles / slices, 4 codes -- no states);
-// final_states may be null; writes status and first_bad only
-hipError_t launch_cabac_verify(int form, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
-                               const uint32_t *order, uint32_t n_slices, const uint8_t *init_states, uint32_t n_states,
-                               const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const uint8_t *final_states,
-                               int32_t *status, uint32_t *first_bad);
+hipError_t launch_range_verify(hipStream_t s, const Slices &in, const OutputView &o, uint32_t *first_bad);
+// the K1 verifier (avr_cabac_verify.hip): the CABAC decoder of H.264 9.3.3.2 over every AVR_SLICE_OK slice and its records, in.form
+// saying which of avr_cabac_verify.h's (kCodes: no states); st.final_states may be null; writes status and first_bad only
+hipError_t launch_cabac_verify(hipStream_t s, const Slices &in, const StatesView &st, const OutputView &o, uint32_t *first_bad);
 // the restore check (avr_restore.hip): every slice that is AVR_SLICE_OK or AVR_SLICE_VERIFY_FAILED and has an expectation, its coded
 // bytes through the decompressor's epilogue rule against the expected payload, a wave per slice; writes status and first_diff only
-hipError_t launch_restore_check(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, uint32_t n_slices,
-                                const uint8_t *expect, const uint64_t *expect_off, const uint32_t *expect_len, int32_t *status,
-                                uint32_t *first_diff);
+hipError_t launch_restore_check(hipStream_t s, const OutputView &o, uint32_t n_slices, const uint8_t *expect, const uint64_t *expect_off,
+                                const uint32_t *expect_len, uint32_t *first_diff);
 #ifdef AVR_TEST_HOOKS
-hipError_t launch_verify_flip(hipStream_t s, uint8_t *out, const uint64_t *out_off, uint32_t slice);
+hipError_t launch_verify_flip(hipStream_t s, const Output &o, uint32_t slice);
 #endif
-hipError_t launch_pack_tiles(hipStream_t s, int kind, uint32_t n_states, const uint16_t *recs,
-                             const uint64_t *rec_off, const uint32_t *n_bins, const uint32_t *order,
-                             uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);
+// slice-major records (in.order: the slices' order in the tiles) -> tiles; in.recs: const uint16_t *
+hipError_t launch_pack_tiles(hipStream_t s, int kind, uint32_t n_states, const Slices &in, const uint64_t *tile_off, void *tiles, int32_t *status);
 hipError_t launch_synth_count(hipStream_t s, int workload, uint32_t scale, uint64_t seed,
                               uint64_t first_slice, int kind, uint32_t n_slices, uint32_t *n_bins);
 hipError_t launch_synth_tiles(hipStream_t s, int workload, uint32_t scale, uint64_t seed,
@@ -161,56 +173,39 @@ hipError_t launch_synth_tiles(hipStream_t s, int workload, uint32_t scale, uint6
                               const uint64_t *tile_off, void *tiles, uint8_t *init_states,
                               uint32_t n_states);
 
-// one-byte K1 records (AVR_KIND_CABAC8, slice i at byte rec_off[i], a multiple of 16) -> the two-byte tiles of launch_pack_tiles
-hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
-                              const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);
+// one-byte K1 records (AVR_KIND_CABAC8, slice i at byte in.off[i], a multiple of 16) -> the two-byte tiles of launch_pack_tiles
+hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const Slices &in, const uint64_t *tile_off, void *tiles, int32_t *status);
 // the same records -> ONE-BYTE tiles (16 records a chunk), and the one-lane-per-slice coder on them: no census, no wait
-hipError_t launch_pack_tiles8_narrow(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
-                                     const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status);
-hipError_t launch_cabac8_encode(hipStream_t s, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins, const uint32_t *order,
-                                uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, uint8_t *out, const uint64_t *out_off,
-                                uint32_t *out_len, int32_t *status, uint8_t *final_states);
+hipError_t launch_pack_tiles8_narrow(hipStream_t s, uint32_t n_states, const Slices &in, const uint64_t *tile_off, void *tiles, int32_t *status);
+hipError_t launch_cabac8_encode(hipStream_t s, const Slices &in, const States &st, const Output &o);
 hipError_t launch_context_census(hipStream_t s, const uint16_t *recs, uint64_t n, uint32_t *bitmap);
 hipError_t launch_context_remap(hipStream_t s, uint16_t *recs, uint64_t n, const uint16_t *table);
 hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_src, uint8_t *dst, uint32_t n_dst,
                                  const uint16_t *index, uint32_t n_index, uint64_t n_slices, int scatter);
-hipError_t launch_compact(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
-                          const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense);
+hipError_t launch_compact(hipStream_t s, const OutputView &o, const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense);
 
-// workspace of the three whole-path launchers below: k1p_layout(n_slices, n_states, pl).total bytes (avr_layout.h, as every workspace here)
-// the caller's arrays of a K1p job, which travel through the launchers together
-struct K1pIo { const uint8_t *init_states; uint8_t *out; const uint64_t *out_off; uint32_t *out_len; int32_t *status; uint8_t *final_states; };
-hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                      uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io, const DenseHint *hint = nullptr);
-hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                            uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io);
-// the same from one-byte records (rec_off in bytes, multiples of 16; n_states <= AVR_MAX_STATES8): no census, no wait; workspace as above
-hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                       uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io);
-hipError_t launch_k1p_resolve(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                              uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                              void *workspace, uint8_t *codes, int32_t *status, uint8_t *final_states);
-hipError_t launch_k1p_code(hipStream_t s, const uint8_t *codes, const uint32_t *n_bins, uint32_t n_slices,
-                           const avr_chunk_plan *pl, void *workspace, uint8_t *out, const uint64_t *out_off,
-                           uint32_t *out_len, int32_t *status);
-hipError_t launch_cabac_encode_codes(hipStream_t s, const uint8_t *codes, const uint64_t *res_off, const uint32_t *n_bins,
-                                     const uint32_t *order, uint32_t n_slices, uint8_t *out, const uint64_t *out_off,
-                                     uint32_t *out_len, int32_t *status, int32_t want_status = AVR_SLICE_OK);
+// The intra-slice parallel K1 path (avr_k1p.hip), slice-major records.  Workspace of the three whole-path launchers:
+// k1p_layout(n_slices, n_states, pl).total bytes (avr_layout.h, as every workspace here)
+hipError_t launch_k1p(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o,
+                      const DenseHint *hint = nullptr);
+hipError_t launch_k1p_retry(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o);
+// the same from one-byte records (in.off in bytes, multiples of 16; n_states <= AVR_MAX_STATES8): no census, no wait; workspace as above
+hipError_t launch_k1p8(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o);
+hipError_t launch_k1p_resolve(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, uint8_t *codes,
+                              int32_t *status);
+// resolved codes (in.recs), slice i at pl->res_off[i]
+hipError_t launch_k1p_code(hipStream_t s, const Slices &in, const avr_chunk_plan *pl, void *workspace, const Output &o);
+hipError_t launch_cabac_encode_codes(hipStream_t s, const Slices &in, const Output &o, int32_t want_status = AVR_SLICE_OK);
 // K2 for few, long slices (avr_k2p.hip): range recurrence per slice, coding per chunk into byte sums, carries + finish
-hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                      const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, uint64_t out_total,
-                      void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);
+hipError_t launch_k2p(hipStream_t s, const Slices &in, const avr_chunk_plan *pl, uint64_t out_total, void *workspace, const Output &o);
 // the compress direction's estimators (avr_est.hip): key records -> K2 range records, per group of slices; never waits
-hipError_t launch_est_resolve(hipStream_t s, const uint16_t *keys, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                              const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in, uint8_t *est_out,
-                              const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, void *workspace,
-                              uint16_t *recs_out, int32_t *status);
+hipError_t launch_est_resolve(hipStream_t s, const Slices &keys, const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in,
+                              uint8_t *est_out, const avr_chunk_plan *pl, void *workspace, uint16_t *recs_out, int32_t *status);
 // the estimator checker (avr_est_verify.hip): resolved records held to their key records and to each other (avr_est_verify.h);
 // workspace est_verify_layout(n_slices, total_chunks).total bytes; writes status and first_bad only; never waits
-hipError_t launch_est_verify(hipStream_t s, const uint16_t *keys, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                             uint32_t n_slices, const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in,
-                             const uint8_t *est_out, const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks,
-                             void *workspace, int32_t *status, uint32_t *first_bad);
+hipError_t launch_est_verify(hipStream_t s, const Slices &keys, const uint16_t *recs, const uint32_t *group_first, uint32_t n_groups,
+                             const uint8_t *est_in, const uint8_t *est_out, const avr_chunk_plan *pl, void *workspace, int32_t *status,
+                             uint32_t *first_bad);
 #ifdef AVR_TEST_HOOKS
 hipError_t launch_est_flip(hipStream_t s, uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t slice, uint32_t bin);
 #endif

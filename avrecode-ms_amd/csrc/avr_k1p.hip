@@ -1508,12 +1508,12 @@ __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_
 
 // What kind of input a job has, and the one place a Plan is made from the caller's pointers.
 enum class Records { kTwoByte, kOneByte, kNone };                // kNone: resolved codes only (phases B-D)
-static Plan make_plan(Records kind, const void *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_states,
-                      const avr_chunk_plan *pl) {
+static Plan make_plan(Records kind, const Slices &in, uint32_t n_states, const avr_chunk_plan *pl) {
     Plan p{};
-    if (kind == Records::kTwoByte) p.recs = static_cast<const uint16_t *>(recs);
-    if (kind == Records::kOneByte) p.recs8 = static_cast<const uint8_t *>(recs);
-    p.rec_off = rec_off; p.n_bins = n_bins;
+    if (kind == Records::kTwoByte) p.recs = in.as<uint16_t>();
+    if (kind == Records::kOneByte) p.recs8 = in.as<uint8_t>();
+    if (kind != Records::kNone) p.rec_off = in.off;              // (codes lie at pl->res_off)
+    p.n_bins = in.n_bins;
     p.res_off = pl->res_off; p.dig_off = pl->dig_off;
     p.chunk_base = pl->chunk_base; p.chunk_slice = pl->chunk_slice; p.blk_base = pl->blk_base; p.blk_slice = pl->blk_slice;
     p.n_states = kind == Records::kOneByte ? n_states : 0;       // one-byte selectors are dense already; two-byte: known after the census
@@ -1557,8 +1557,8 @@ static hipError_t tn_table(hipStream_t s, const uint8_t **out) {
 // `w` is a ResolveLayout for the caller's context count; the kernels index it by the dense count, which is known after the
 // census (the one host round trip of the path: four bytes, to size the later launches).
 static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const avr_chunk_plan *pl, uint8_t *w, uint8_t *res,
-                                 const K1pIo &io, uint32_t max_stretch, const Stretch **stretch_out, const ResolveMode &mode) {
-    const uint8_t *init_states = io.init_states; int32_t *status = io.status; uint8_t *final_states = io.final_states;
+                                 const States &st, int32_t *status, uint32_t max_stretch, const Stretch **stretch_out, const ResolveMode &mode) {
+    const uint8_t *init_states = st.init_states; uint8_t *final_states = st.final_states;
     const DenseHint *hint = mode.hint;
     const bool r8 = p.recs8 != nullptr;
     const uint32_t ns = p.ns_full;
@@ -1693,7 +1693,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
 // Phases B-D: resolved codes -> bytes.  `w` is a CodeLayout.
 // `have` != nullptr: the stretch summaries (phase B1) have been made already, by k_k1p_replay.
 static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, const avr_chunk_plan *pl, uint8_t *w,
-                              const uint8_t *res, uint32_t max_stretch, const K1pIo &io, const Stretch *have = nullptr,
+                              const uint8_t *res, uint32_t max_stretch, const Output &o, const Stretch *have = nullptr,
                               bool tile_codes = false) {
     const CodeLayout L = code_layout(n_slices, pl);
     Stretch *st_own = reinterpret_cast<Stretch *>(w + L.stretch);
@@ -1705,15 +1705,15 @@ static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, c
     if (!have) {
         // codes from the caller, slice-major: B1 reads them lane by lane once and leaves a wave-interleaved copy for phase C
         uint8_t *tile = w + L.tile;
-        hipLaunchKernelGGL(k_k1p_b1, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, io.status, st_own, max_stretch, tile);
+        hipLaunchKernelGGL(k_k1p_b1, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, o.status, st_own, max_stretch, tile);
         res = tile;
         tile_codes = true;
     }
-    hipLaunchKernelGGL(k_k1p_b2, dim3(n_slices), dim3(256), 0, s, p, io.status, st, en, tot, S);
+    hipLaunchKernelGGL(k_k1p_b2, dim3(n_slices), dim3(256), 0, s, p, o.status, st, en, tot, S);
     if (tile_codes) hipLaunchKernelGGL(k_k1p_c<true>, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
     else hipLaunchKernelGGL(k_k1p_c<false>, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
     const uint32_t force_retry_every = test_hooks().k1p_force_retry_every;   // test build only, see k_k1p_d
-    hipLaunchKernelGGL(k_k1p_d, dim3(n_slices), dim3(256), 0, s, p, tot, S, io.out, io.out_off, io.out_len, io.status, force_retry_every);
+    hipLaunchKernelGGL(k_k1p_d, dim3(n_slices), dim3(256), 0, s, p, tot, S, o.out, o.out_off, o.out_len, o.status, force_retry_every);
     return hipGetLastError();
 }
 
@@ -1722,12 +1722,10 @@ hipError_t launch_densemap(hipStream_t s, const uint32_t *used, uint16_t *table,
     return hipGetLastError();
 }
 
-hipError_t launch_cabac_encode_codes(hipStream_t s, const uint8_t *codes, const uint64_t *res_off, const uint32_t *n_bins,
-                                     const uint32_t *order, uint32_t n_slices, uint8_t *out, const uint64_t *out_off,
-                                     uint32_t *out_len, int32_t *status, int32_t want_status) {
-    if (n_slices == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cabac_encode_codes<false>, dim3((n_slices + 63) / 64), dim3(64), 0, s, codes, res_off, nullptr, n_bins, order,
-                       n_slices, out, out_off, out_len, status, want_status);
+hipError_t launch_cabac_encode_codes(hipStream_t s, const Slices &in, const Output &o, int32_t want_status) {
+    if (in.n_slices == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_cabac_encode_codes<false>, dim3((in.n_slices + 63) / 64), dim3(64), 0, s, in.as<uint8_t>(), in.off, nullptr, in.n_bins,
+                       in.order, in.n_slices, o.out, o.out_off, o.out_len, o.status, want_status);
     return hipGetLastError();
 }
 
@@ -1737,32 +1735,31 @@ static uint32_t census_stride() {
     return test_hooks().census_stride ? test_hooks().census_stride : kK1pCensusStride;
 }
 
-// A job of the whole path (launch_k1p, launch_k1p_retry, launch_k1p8): its plan, and its K1pLayout in the caller's workspace.
+// A job of the whole path (launch_k1p, launch_k1p_retry, launch_k1p8): its slices, its plan, and its K1pLayout in the caller's workspace.
 // The codes between the two stages stay inside the call: wave-interleaved (TileCodes).
-struct K1pJob { Plan p; uint32_t n_slices; const avr_chunk_plan *pl; uint8_t *codes, *resolve_ws, *code_ws; };
-static K1pJob k1p_job(Records kind, const void *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                      uint32_t n_states, const avr_chunk_plan *pl, void *workspace) {
-    const K1pLayout L = k1p_layout(n_slices, n_states, pl);
+struct K1pJob { Slices in; Plan p; const avr_chunk_plan *pl; uint8_t *codes, *resolve_ws, *code_ws; };
+static K1pJob k1p_job(Records kind, const Slices &in, uint32_t n_states, const avr_chunk_plan *pl, void *workspace) {
+    const K1pLayout L = k1p_layout(in.n_slices, n_states, pl);
     uint8_t *w = static_cast<uint8_t *>(workspace);
-    return K1pJob{make_plan(kind, recs, rec_off, n_bins, n_states, pl), n_slices, pl, w + L.codes, w + L.resolve, w + L.code};
+    return K1pJob{in, make_plan(kind, in, n_states, pl), pl, w + L.codes, w + L.resolve, w + L.code};
 }
 
 // Both stages of a job over the slices whose status is AVR_SLICE_OK; what comes after them is the caller's.
-static hipError_t k1p_stages(hipStream_t s, const K1pJob &j, const K1pIo &io, ResolveMode mode) {
-    const Stretch *st = nullptr;
+static hipError_t k1p_stages(hipStream_t s, const K1pJob &j, const States &st, const Output &o, ResolveMode mode) {
+    const Stretch *stretch = nullptr;
     mode.tile_codes = true;
-    hipError_t e = launch_resolve(s, j.p, j.n_slices, j.pl, j.resolve_ws, j.codes, io, kMaxStretch, &st, mode);
+    hipError_t e = launch_resolve(s, j.p, j.in.n_slices, j.pl, j.resolve_ws, j.codes, st, o.status, kMaxStretch, &stretch, mode);
     if (e != hipSuccess) return e;
-    return launch_code(s, j.p, j.n_slices, j.pl, j.code_ws, j.codes, kMaxStretch, io, st, true);
+    return launch_code(s, j.p, j.in.n_slices, j.pl, j.code_ws, j.codes, kMaxStretch, o, stretch, true);
 }
 
 // One pass of the whole path from two-byte records.
-static hipError_t k1p_pass(hipStream_t s, const K1pJob &j, const K1pIo &io, const ResolveMode &mode) {
-    const hipError_t e = k1p_stages(s, j, io, mode);
+static hipError_t k1p_pass(hipStream_t s, const K1pJob &j, const States &st, const Output &o, const ResolveMode &mode) {
+    const hipError_t e = k1p_stages(s, j, st, o, mode);
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;    // (test hook: the hand-overs stay visible, uncoded)
-    // slices the scheme declined (status AVR_SLICE_RETRY_SERIAL) are coded by the serial kernel
-    return launch_cabac_encode(false, s, j.p.recs, j.p.rec_off, j.p.n_bins, nullptr, j.n_slices, io.init_states, j.p.ns_full, io.out,
-                               io.out_off, io.out_len, io.status, nullptr, AVR_SLICE_RETRY_SERIAL);
+    // slices the scheme declined (status AVR_SLICE_RETRY_SERIAL) are coded by the serial kernel, from the same slice-major records
+    return launch_cabac_encode(s, Slices{j.p.recs, j.p.rec_off, j.p.n_bins, nullptr, j.in.n_slices}, States{st.init_states, st.n_states, nullptr}, o,
+                               AVR_SLICE_RETRY_SERIAL);
 }
 
 // The second pass: the slices k_k1p_local set aside (a bin in a context the sampled census missed) once more, with every
@@ -1780,11 +1777,11 @@ static hipError_t k1p_second_pass(hipStream_t s, uint32_t n_slices, int32_t *sta
     return hipGetLastError();
 }
 
-hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                      uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io, const DenseHint *hint) {
-    if (n_slices == 0) return hipSuccess;
-    const K1pJob j = k1p_job(Records::kTwoByte, recs, rec_off, n_bins, n_slices, n_states, pl, workspace);
-    auto pass = [&](const ResolveMode &mode) { return k1p_pass(s, j, io, mode); };
+hipError_t launch_k1p(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o,
+                      const DenseHint *hint) {
+    if (in.n_slices == 0) return hipSuccess;
+    const K1pJob j = k1p_job(Records::kTwoByte, in, st.n_states, pl, workspace);
+    auto pass = [&](const ResolveMode &mode) { return k1p_pass(s, j, st, o, mode); };
     uint32_t retry = 0;
     if (hint && hint->host_retry) *hint->host_retry = 0;
     ResolveMode mode;
@@ -1793,60 +1790,52 @@ hipError_t launch_k1p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_o
     mode.retry_count = &retry;
     const hipError_t e = pass(mode);
     if (e != hipSuccess || !retry) return e;
-    return k1p_second_pass(s, n_slices, io.status, pass);
+    return k1p_second_pass(s, in.n_slices, o.status, pass);
 }
 
-hipError_t launch_k1p_retry(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                            uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io) {
-    if (n_slices == 0) return hipSuccess;
-    const K1pJob j = k1p_job(Records::kTwoByte, recs, rec_off, n_bins, n_slices, n_states, pl, workspace);
-    return k1p_second_pass(s, n_slices, io.status, [&](const ResolveMode &mode) { return k1p_pass(s, j, io, mode); });
+hipError_t launch_k1p_retry(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o) {
+    if (in.n_slices == 0) return hipSuccess;
+    const K1pJob j = k1p_job(Records::kTwoByte, in, st.n_states, pl, workspace);
+    return k1p_second_pass(s, in.n_slices, o.status, [&](const ResolveMode &mode) { return k1p_pass(s, j, st, o, mode); });
 }
 
 // The two stages on their own: phase A into a caller-owned code buffer (workspace: a ResolveLayout) ...
-hipError_t launch_k1p_resolve(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins,
-                              uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const avr_chunk_plan *pl,
-                              void *workspace, uint8_t *codes, int32_t *status, uint8_t *final_states) {
-    if (n_slices == 0) return hipSuccess;
-    const Plan p = make_plan(Records::kTwoByte, recs, rec_off, n_bins, n_states, pl);
-    const K1pIo io{init_states, nullptr, nullptr, nullptr, status, final_states};       // no bytes come out of phase A
+hipError_t launch_k1p_resolve(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, uint8_t *codes,
+                              int32_t *status) {
+    if (in.n_slices == 0) return hipSuccess;
+    const Plan p = make_plan(Records::kTwoByte, in, st.n_states, pl);
     uint8_t *w = static_cast<uint8_t *>(workspace);
-    auto resolve = [&](const ResolveMode &mode) { return launch_resolve(s, p, n_slices, pl, w, codes, io, kMaxStretch, nullptr, mode); };
+    auto resolve = [&](const ResolveMode &mode) { return launch_resolve(s, p, in.n_slices, pl, w, codes, st, status, kMaxStretch, nullptr, mode); };
     uint32_t retry = 0;
     ResolveMode mode;
     mode.census_stride = census_stride();
     mode.retry_count = &retry;
     const hipError_t e = resolve(mode);
     if (e != hipSuccess || !retry) return e;
-    return k1p_second_pass(s, n_slices, status, resolve);
+    return k1p_second_pass(s, in.n_slices, status, resolve);
 }
 // The one-byte form (AVR_KIND_CABAC8, avr_cabac8_encode_chunked_device): the same phases on p.recs8, without the census, the
 // renumbering, the second pass and the host round trip (the selectors are dense ids below n_states <= AVR_MAX_STATES8 already):
 // everything is enqueued, nothing waits.  The slices phase D hands over are coded by the serial coder from the resolved codes this
 // call made (k_cabac_encode_codes on the wave-interleaved buffer): same bytes as from the records, and no two-byte copy of them.
-hipError_t launch_k1p8(hipStream_t s, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                       uint32_t n_states, const avr_chunk_plan *pl, void *workspace, const K1pIo &io) {
-    if (n_slices == 0) return hipSuccess;
-    const K1pJob j = k1p_job(Records::kOneByte, recs8, rec_off, n_bins, n_slices, n_states, pl, workspace);
-    const hipError_t e = k1p_stages(s, j, io, ResolveMode{});
+hipError_t launch_k1p8(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o) {
+    if (in.n_slices == 0) return hipSuccess;
+    const K1pJob j = k1p_job(Records::kOneByte, in, st.n_states, pl, workspace);
+    const hipError_t e = k1p_stages(s, j, st, o, ResolveMode{});
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
-    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((n_slices + 63) / 64), dim3(64), 0, s, j.codes, nullptr, pl->chunk_base, n_bins,
-                       nullptr, n_slices, io.out, io.out_off, io.out_len, io.status, int32_t(AVR_SLICE_RETRY_SERIAL));
+    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((in.n_slices + 63) / 64), dim3(64), 0, s, j.codes, nullptr, pl->chunk_base, in.n_bins,
+                       nullptr, in.n_slices, o.out, o.out_off, o.out_len, o.status, int32_t(AVR_SLICE_RETRY_SERIAL));
     return hipGetLastError();
 }
 
 // ... and phases B-D from resolved codes (no stretch is declined for its length here: a stretch without an
 // LPS is simply walked to its end by one lane); a slice phase D hands back is coded by k_cabac_encode_codes (workspace: a CodeLayout)
-hipError_t launch_k1p_code(hipStream_t s, const uint8_t *codes, const uint32_t *n_bins, uint32_t n_slices,
-                           const avr_chunk_plan *pl, void *workspace, uint8_t *out, const uint64_t *out_off,
-                           uint32_t *out_len, int32_t *status) {
-    if (n_slices == 0) return hipSuccess;
-    const Plan p = make_plan(Records::kNone, nullptr, nullptr, n_bins, 0, pl);
-    const K1pIo io{nullptr, out, out_off, out_len, status, nullptr};
-    hipError_t e = launch_code(s, p, n_slices, pl, static_cast<uint8_t *>(workspace), codes, 0xffffffffu, io);
+hipError_t launch_k1p_code(hipStream_t s, const Slices &in, const avr_chunk_plan *pl, void *workspace, const Output &o) {
+    if (in.n_slices == 0) return hipSuccess;
+    const Plan p = make_plan(Records::kNone, in, 0, pl);
+    hipError_t e = launch_code(s, p, in.n_slices, pl, static_cast<uint8_t *>(workspace), in.as<uint8_t>(), 0xffffffffu, o);
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
-    return launch_cabac_encode_codes(s, codes, pl->res_off, n_bins, nullptr, n_slices, out, out_off, out_len, status,
-                                     AVR_SLICE_RETRY_SERIAL);
+    return launch_cabac_encode_codes(s, Slices{in.recs, pl->res_off, in.n_bins, nullptr, in.n_slices}, o, AVR_SLICE_RETRY_SERIAL);
 }
 
 }  // namespace avr

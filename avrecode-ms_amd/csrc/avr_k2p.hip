@@ -623,9 +623,9 @@ void forget_side_stream(hipStream_t s) {
     });
 }
 
-hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_off, const uint32_t *n_bins, uint32_t n_slices,
-                      const uint32_t *chunk_base, const uint32_t *chunk_slice, uint32_t total_chunks, uint64_t out_total,
-                      void *workspace, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status) {
+hipError_t launch_k2p(hipStream_t s, const Slices &in, const avr_chunk_plan *pl, uint64_t out_total, void *workspace, const Output &o) {
+    const uint32_t n_slices = in.n_slices, total_chunks = pl->total_chunks;
+    int32_t *status = o.status;
     if (n_slices == 0) return hipSuccess;
     // the workspace is avr_layout.h's K2pLayout
     const K2pLayout L = k2p_layout(n_slices, total_chunks, out_total);
@@ -636,7 +636,7 @@ hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_o
     uint32_t *fin_pos = reinterpret_cast<uint32_t *>(w + L.fin_pos);
     uint32_t *long_chunks = reinterpret_cast<uint32_t *>(w + L.long_chunks);    // the hybrid pass 1's threshold, count and list of long slices
     uint32_t *S = reinterpret_cast<uint32_t *>(w + L.sums);
-    const K2Plan p{recs, rec_off, n_bins, chunk_base, chunk_slice, out_off};
+    const K2Plan p{in.as<uint16_t>(), in.off, in.n_bins, pl->chunk_base, pl->chunk_slice, o.out_off};
     const dim3 slice_grid((n_slices + 63) / 64), chunk_grid((total_chunks + 255) / 256);
     // Segments: an eighth of the average slice each, the last one open-ended (it takes whatever the longer slices have left).
     const uint32_t avg = total_chunks / n_slices;
@@ -651,7 +651,7 @@ hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_o
     // lanes' waves leave SIMDs over -- a wave each for the longest slices (test hook k2p_wave: 1 / 2 = the one / the other for all)
     constexpr uint32_t kSimds = 1024;
     const uint32_t form = test_hooks().k2p_wave ? test_hooks().k2p_wave : n_slices <= kSimds ? 1u : slice_grid.x + 64 <= kSimds ? 3u : 2u;
-    if (form == 3) hipLaunchKernelGGL(k_k2p_threshold, dim3(1), dim3(1024), 0, s, chunk_base, n_slices, kSimds - slice_grid.x, long_chunks);
+    if (form == 3) hipLaunchKernelGGL(k_k2p_threshold, dim3(1), dim3(1024), 0, s, pl->chunk_base, n_slices, kSimds - slice_grid.x, long_chunks);
     for (uint32_t k = 0; k < n_seg; k++) {
         const bool open = k + 1 == n_seg;
         const uint32_t begin = k * seg_len, end = open ? 0xffffffffu / kChunk : begin + seg_len;
@@ -679,13 +679,13 @@ hipError_t launch_k2p(hipStream_t s, const uint16_t *recs, const uint64_t *rec_o
             return e;
         }
     }
-    hipLaunchKernelGGL(k_k2p_finish, dim3(n_slices), dim3(64), 0, s, p, fin_range, fin_pos, S, out, out_len, status, AVR_SLICE_OK);
+    hipLaunchKernelGGL(k_k2p_finish, dim3(n_slices), dim3(64), 0, s, p, fin_range, fin_pos, S, o.out, o.out_len, status, AVR_SLICE_OK);
     // The slices the double-precision walk handed over (AVR_SLICE_RETRY_SERIAL: a range below 2^39 somewhere), start to end in the
     // integer form; a workgroup without any leaves at once, so these four launches cost microseconds when there is none.
     hipLaunchKernelGGL(k_k2p_ranges, slice_grid, dim3(64), 0, s, p, n_slices, ck_range, ck_pos, fin_range, fin_pos, status, AVR_SLICE_RETRY_SERIAL);
     hipLaunchKernelGGL(k_k2p_zero, chunk_grid, dim3(256), 0, s, p, n_slices, total_chunks, ck_pos, fin_pos, status, S, AVR_SLICE_DONE, 0u, 0u);
     hipLaunchKernelGGL(k_k2p_code, chunk_grid, dim3(256), 0, s, p, n_slices, total_chunks, ck_range, ck_pos, fin_pos, status, S, AVR_SLICE_DONE, 0u, 0u);
-    hipLaunchKernelGGL(k_k2p_finish, dim3(n_slices), dim3(64), 0, s, p, fin_range, fin_pos, S, out, out_len, status, AVR_SLICE_DONE);
+    hipLaunchKernelGGL(k_k2p_finish, dim3(n_slices), dim3(64), 0, s, p, fin_range, fin_pos, S, o.out, o.out_len, status, AVR_SLICE_DONE);
     return hipGetLastError();
 }
 

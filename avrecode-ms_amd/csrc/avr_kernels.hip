@@ -976,11 +976,9 @@ void forget_stream(hipStream_t s) {
 // contexts its records use (census -> k_k1p_densemap -> one 4-byte read-back to size the launch), applied to the
 // records as they are loaded (sel_off): nothing is rewritten, init_states / final_states stay in the caller's numbering.
 // dense = false (and every hand-over from K1p, want_status != OK): the caller's numbering as it is.
-hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, const uint64_t *off,
-                               const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices,
-                               const uint8_t *init_states, uint32_t n_states, uint8_t *out,
-                               const uint64_t *out_off, uint32_t *out_len, int32_t *status,
-                               uint8_t *final_states, int32_t want_status, bool dense, const DenseHint *hint) {
+hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st, const Output &o, int32_t want_status, bool dense,
+                               const DenseHint *hint) {
+    const uint32_t n_slices = in.n_slices, n_states = st.n_states;
     if (n_slices == 0) return hipSuccess;
     hipError_t err;
     uint32_t n_rows = n_states;
@@ -996,8 +994,8 @@ hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, cons
         const dim3 cgrid(((n_slices + 63) / 64 + kCensusTiles - 1) / kCensusTiles);
         const uint32_t stride = test_hooks().census_stride ? test_hooks().census_stride : kCensusStride;
         retry = stride > 1;
-        if (tiled) hipLaunchKernelGGL(k_k1_census<true>, cgrid, dim3(256), 0, s, recs, off, n_bins, order, n_slices, used, stride);
-        else hipLaunchKernelGGL(k_k1_census<false>, cgrid, dim3(256), 0, s, recs, off, n_bins, order, n_slices, used, stride);
+        if (in.tiled) hipLaunchKernelGGL(k_k1_census<true>, cgrid, dim3(256), 0, s, in.recs, in.off, in.n_bins, in.order, n_slices, used, stride);
+        else hipLaunchKernelGGL(k_k1_census<false>, cgrid, dim3(256), 0, s, in.recs, in.off, in.n_bins, in.order, n_slices, used, stride);
         if ((err = launch_densemap(s, used, t, t + 1024, used + 32)) != hipSuccess) return err;
         uint32_t nd = 0;
         if (hint && hint->rows) {                                // sized by the caller's guess: nothing waits (see DenseHint)
@@ -1014,7 +1012,7 @@ hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, cons
         n_rows = nd < n_states ? nd : n_states;
         table = t;
         index = t + 1024;
-        if (final_states && (err = hipMemcpyAsync(final_states, init_states, size_t(n_slices) * n_states, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        if (st.final_states && (err = hipMemcpyAsync(st.final_states, st.init_states, size_t(n_slices) * n_states, hipMemcpyDeviceToDevice, s)) != hipSuccess)
             return err;                                          // contexts without bins keep their state
     }
     auto launch = [&](uint32_t rows, const uint16_t *tb, const uint16_t *ix, int32_t want) -> hipError_t {
@@ -1029,14 +1027,14 @@ hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, cons
         // like cabac_code.h, and 2.44 against 2.55 ms per step on config 5.  Test hooks: k1_form_ref = that form (CabacLane),
         // k1_emit_lds = 1: it with the digits staged in LDS (CabacLaneS), 2: the shipped form with them (CabacLaneNS); same bytes all.
         const int form = test_hooks().k1_emit_lds ? (test_hooks().k1_emit_lds == 2 ? 3 : 2) : test_hooks().k1_form_ref ? 0 : test_hooks().k1_fwd ? 4 : test_hooks().k1_words8 ? 5 : 1;
-        auto kern = tiled ? (form == 5 ? k_cabac_encode<true, 5> : form == 4 ? k_cabac_encode<true, 4> : form == 1 ? k_cabac_encode<true, 1> : form == 2 ? k_cabac_encode<true, 2> : form == 3 ? k_cabac_encode<true, 3> : k_cabac_encode<true, 0>)
+        auto kern = in.tiled ? (form == 5 ? k_cabac_encode<true, 5> : form == 4 ? k_cabac_encode<true, 4> : form == 1 ? k_cabac_encode<true, 1> : form == 2 ? k_cabac_encode<true, 2> : form == 3 ? k_cabac_encode<true, 3> : k_cabac_encode<true, 0>)
                           : (form == 5 ? k_cabac_encode<false, 5> : form == 4 ? k_cabac_encode<false, 4> : form == 1 ? k_cabac_encode<false, 1> : form == 2 ? k_cabac_encode<false, 2> : form == 3 ? k_cabac_encode<false, 3> : k_cabac_encode<false, 0>);
         if (lds > 48 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(kern, grid, block, lds, s, recs, off, n_bins, order, n_slices, init_states, n_states, tb, ix, rows, out,
-                           out_off, out_len, status, final_states, want);
+        hipLaunchKernelGGL(kern, grid, block, lds, s, in.recs, in.off, in.n_bins, in.order, n_slices, st.init_states, n_states, tb, ix, rows, o.out,
+                           o.out_off, o.out_len, o.status, st.final_states, want);
         return hipGetLastError();
     };
     err = launch(n_rows, table, index, want_status);
@@ -1046,52 +1044,44 @@ hipError_t launch_cabac_encode(bool tiled, hipStream_t s, const void *recs, cons
 
 // The one-lane-per-slice kernel on one-byte tiles: the selectors are dense ids below n_states <= AVR_MAX_STATES8 already, so there
 // is nothing to count or renumber -- one launch, kK1Waves waves a workgroup (at most 33 dwords of states a lane: 33.8 KiB of LDS for four waves).
-hipError_t launch_cabac8_encode(hipStream_t s, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins, const uint32_t *order,
-                                uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, uint8_t *out, const uint64_t *out_off,
-                                uint32_t *out_len, int32_t *status, uint8_t *final_states) {
+hipError_t launch_cabac8_encode(hipStream_t s, const Slices &in, const States &st, const Output &o) {
+    const uint32_t n_slices = in.n_slices, n_states = st.n_states;
     if (n_slices == 0) return hipSuccess;
     const uint32_t lds = kK1Waves * ((n_states + 4 + 3) / 4) * 256;
     const dim3 grid((n_slices + 64 * kK1Waves - 1) / (64 * kK1Waves)), block(64 * kK1Waves);
-    hipLaunchKernelGGL((k_cabac_encode<true, 1, 1>), grid, block, lds, s, tiles, tile_off, n_bins, order, n_slices, init_states,
-                       n_states, nullptr, nullptr, n_states, out, out_off, out_len, status, final_states, int32_t(AVR_SLICE_OK));
+    hipLaunchKernelGGL((k_cabac_encode<true, 1, 1>), grid, block, lds, s, in.recs, in.off, in.n_bins, in.order, n_slices, st.init_states,
+                       n_states, nullptr, nullptr, n_states, o.out, o.out_off, o.out_len, o.status, st.final_states, int32_t(AVR_SLICE_OK));
     return hipGetLastError();
 }
 
-hipError_t launch_range_encode(bool tiled, hipStream_t s, const void *recs, const uint64_t *off,
-                               const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices,
-                               uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
-                               int32_t *status) {
-    if (n_slices == 0) return hipSuccess;
-    const dim3 grid((n_slices + 63) / 64), block(64);
-    if (tiled) hipLaunchKernelGGL(k_range_encode<true>, grid, block, 0, s, recs, off, n_bins, order, n_slices, out, out_off, out_len, status);
-    else hipLaunchKernelGGL(k_range_encode<false>, grid, block, 0, s, recs, off, n_bins, order, n_slices, out, out_off, out_len, status);
+hipError_t launch_range_encode(hipStream_t s, const Slices &in, const Output &o) {
+    if (in.n_slices == 0) return hipSuccess;
+    const dim3 grid((in.n_slices + 63) / 64), block(64);
+    auto kern = in.tiled ? k_range_encode<true> : k_range_encode<false>;
+    hipLaunchKernelGGL(kern, grid, block, 0, s, in.recs, in.off, in.n_bins, in.order, in.n_slices, o.out, o.out_off, o.out_len, o.status);
     return hipGetLastError();
 }
 
-hipError_t launch_pack_tiles(hipStream_t s, int kind, uint32_t n_states, const uint16_t *recs,
-                             const uint64_t *rec_off, const uint32_t *n_bins, const uint32_t *order,
-                             uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status) {
-    if (n_slices == 0) return hipSuccess;
-    const dim3 grid((n_slices + 63) / 64), block(64);
-    hipLaunchKernelGGL(k_pack_tiles, grid, block, 0, s, kind, n_states, recs, rec_off, n_bins, order, n_slices,
+hipError_t launch_pack_tiles(hipStream_t s, int kind, uint32_t n_states, const Slices &in, const uint64_t *tile_off, void *tiles, int32_t *status) {
+    if (in.n_slices == 0) return hipSuccess;
+    const dim3 grid((in.n_slices + 63) / 64), block(64);
+    hipLaunchKernelGGL(k_pack_tiles, grid, block, 0, s, kind, n_states, in.as<uint16_t>(), in.off, in.n_bins, in.order, in.n_slices,
                        tile_off, reinterpret_cast<uint4 *>(tiles), status);
     return hipGetLastError();
 }
 
-hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
-                              const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status) {
-    if (n_slices == 0) return hipSuccess;
-    const dim3 grid((n_slices + 63) / 64), block(64);
-    hipLaunchKernelGGL(k_pack_tiles8, grid, block, 0, s, n_states, recs8, rec_off, n_bins, order, n_slices, tile_off,
+hipError_t launch_pack_tiles8(hipStream_t s, uint32_t n_states, const Slices &in, const uint64_t *tile_off, void *tiles, int32_t *status) {
+    if (in.n_slices == 0) return hipSuccess;
+    const dim3 grid((in.n_slices + 63) / 64), block(64);
+    hipLaunchKernelGGL(k_pack_tiles8, grid, block, 0, s, n_states, in.as<uint8_t>(), in.off, in.n_bins, in.order, in.n_slices, tile_off,
                        reinterpret_cast<uint4 *>(tiles), status);
     return hipGetLastError();
 }
 
-hipError_t launch_pack_tiles8_narrow(hipStream_t s, uint32_t n_states, const uint8_t *recs8, const uint64_t *rec_off, const uint32_t *n_bins,
-                                     const uint32_t *order, uint32_t n_slices, const uint64_t *tile_off, void *tiles, int32_t *status) {
-    if (n_slices == 0) return hipSuccess;
-    const dim3 grid((n_slices + 63) / 64), block(64);
-    hipLaunchKernelGGL(k_pack_tiles8_narrow, grid, block, 0, s, n_states, recs8, rec_off, n_bins, order, n_slices, tile_off,
+hipError_t launch_pack_tiles8_narrow(hipStream_t s, uint32_t n_states, const Slices &in, const uint64_t *tile_off, void *tiles, int32_t *status) {
+    if (in.n_slices == 0) return hipSuccess;
+    const dim3 grid((in.n_slices + 63) / 64), block(64);
+    hipLaunchKernelGGL(k_pack_tiles8_narrow, grid, block, 0, s, n_states, in.as<uint8_t>(), in.off, in.n_bins, in.order, in.n_slices, tile_off,
                        reinterpret_cast<uint4 *>(tiles), status);
     return hipGetLastError();
 }
@@ -1119,11 +1109,9 @@ hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_s
     return hipGetLastError();
 }
 
-hipError_t launch_compact(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
-                          const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense) {
-    (void)out_len;
+hipError_t launch_compact(hipStream_t s, const OutputView &o, const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense) {
     if (n_slices == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_compact, dim3(n_slices), dim3(64), 0, s, out, out_off, dense_off, n_slices, dense);
+    hipLaunchKernelGGL(k_compact, dim3(n_slices), dim3(64), 0, s, o.out, o.out_off, dense_off, n_slices, dense);
     return hipGetLastError();
 }
 

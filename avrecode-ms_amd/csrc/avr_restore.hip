@@ -50,12 +50,11 @@ __global__ __launch_bounds__(256) void k_restore_check(
     }
 }
 
-hipError_t launch_restore_check(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, uint32_t n_slices,
-                                const uint8_t *expect, const uint64_t *expect_off, const uint32_t *expect_len, int32_t *status,
-                                uint32_t *first_diff) {
+hipError_t launch_restore_check(hipStream_t s, const OutputView &o, uint32_t n_slices, const uint8_t *expect, const uint64_t *expect_off,
+                                const uint32_t *expect_len, uint32_t *first_diff) {
     if (n_slices == 0) return hipSuccess;
     const dim3 grid((n_slices + 3u) / 4u), block(256);
-    hipLaunchKernelGGL(k_restore_check, grid, block, 0, s, out, out_off, out_len, n_slices, expect, expect_off, expect_len, status, first_diff);
+    hipLaunchKernelGGL(k_restore_check, grid, block, 0, s, o.out, o.out_off, o.out_len, n_slices, expect, expect_off, expect_len, o.status, first_diff);
     return hipGetLastError();
 }
 

@@ -56,17 +56,16 @@ __global__ __launch_bounds__(64) void k_range_verify(
     if (first_bad) first_bad[slice] = bad;
 }
 
-hipError_t launch_range_verify(bool tiled, hipStream_t s, const void *recs, const uint64_t *off, const uint32_t *n_bins,
-                               const uint32_t *order, uint32_t n_slices, const uint8_t *out, const uint64_t *out_off,
-                               const uint32_t *out_len, int32_t *status, uint32_t *first_bad) {
+hipError_t launch_range_verify(hipStream_t s, const Slices &in, const OutputView &o, uint32_t *first_bad) {
+    const uint32_t n_slices = in.n_slices;
     if (n_slices == 0) return hipSuccess;
     // The lanes of a wave renormalise at different bins, and the wave walks that path whenever one of them does.  Slice-major batches of few
     // slices (K2p's shape) leave most of the chip idle anyway: there a wave takes as few slices as still give every SIMD of the chip
     // (1 024) a wave -- one slice up to 1 024 slices, 64 from 64 Ki on.  Tiles are laid out for 64 slices a wave.
-    const uint32_t per_wave = tiled ? 64u : std::min(64u, (n_slices + 1023u) / 1024u);
+    const uint32_t per_wave = in.tiled ? 64u : std::min(64u, (n_slices + 1023u) / 1024u);
     const dim3 grid((n_slices + per_wave - 1) / per_wave), block(64);
-    if (tiled) hipLaunchKernelGGL(k_range_verify<true>, grid, block, 0, s, recs, off, n_bins, order, n_slices, out, out_off, out_len, status, first_bad, per_wave);
-    else hipLaunchKernelGGL(k_range_verify<false>, grid, block, 0, s, recs, off, n_bins, order, n_slices, out, out_off, out_len, status, first_bad, per_wave);
+    auto kern = in.tiled ? k_range_verify<true> : k_range_verify<false>;
+    hipLaunchKernelGGL(kern, grid, block, 0, s, in.recs, in.off, in.n_bins, in.order, n_slices, o.out, o.out_off, o.out_len, o.status, first_bad, per_wave);
     return hipGetLastError();
 }
 
@@ -76,8 +75,8 @@ hipError_t launch_range_verify(bool tiled, hipStream_t s, const void *recs, cons
 __global__ void k_verify_flip(uint8_t *out, const uint64_t *out_off, uint32_t slice) {
     if (blockIdx.x == 0 && threadIdx.x == 0) out[out_off[slice]] ^= 0x80u;
 }
-hipError_t launch_verify_flip(hipStream_t s, uint8_t *out, const uint64_t *out_off, uint32_t slice) {
-    hipLaunchKernelGGL(k_verify_flip, dim3(1), dim3(64), 0, s, out, out_off, slice);
+hipError_t launch_verify_flip(hipStream_t s, const Output &o, uint32_t slice) {
+    hipLaunchKernelGGL(k_verify_flip, dim3(1), dim3(64), 0, s, o.out, o.out_off, slice);
     return hipGetLastError();
 }
 #endif
