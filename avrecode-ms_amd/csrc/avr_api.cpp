@@ -328,9 +328,9 @@ extern "C" {
 int avr_test_hook_set(const char *name, uint32_t value) {
     static const struct { const char *name; uint32_t avr::TestHooks::*field; } kHooks[] = {
 #define AVR_HOOK(f) {#f, &avr::TestHooks::f}
-        AVR_HOOK(k1p_force_retry_every), AVR_HOOK(census_stride), AVR_HOOK(chain_lanes), AVR_HOOK(k1_form_ref), AVR_HOOK(k1_emit_lds),
+        AVR_HOOK(k1p_force_retry_every), AVR_HOOK(census_stride), AVR_HOOK(chain_lanes),
         AVR_HOOK(k1_path), AVR_HOOK(no_dense), AVR_HOOK(no_hint), AVR_HOOK(k2p_seg_len), AVR_HOOK(local_waves), AVR_HOOK(k2p_wave),
-        AVR_HOOK(k1p_keep_retry), AVR_HOOK(k1_waves), AVR_HOOK(k1_fwd), AVR_HOOK(k1_words8), AVR_HOOK(chain_nsegs), AVR_HOOK(chain_whole),
+        AVR_HOOK(k1p_keep_retry), AVR_HOOK(k1_waves), AVR_HOOK(chain_nsegs), AVR_HOOK(chain_whole),
         AVR_HOOK(chain_segments), AVR_HOOK(chain_force_redo), AVR_HOOK(verify_flip), AVR_HOOK(est_flip), AVR_HOOK(est_flip_bin),
         AVR_HOOK(restore_flip),
 #undef AVR_HOOK

@@ -40,8 +40,6 @@ struct TestHooks {
     uint32_t k1p_force_retry_every;  // k_k1p_d hands every n-th slice to the serial kernel (0 = off)
     uint32_t census_stride;          // sampling stride of both census kernels (0 = the built-in 16)
     uint32_t chain_lanes;            // lanes per wave of k_k1p_ctxchain (0 = by batch shape)
-    uint32_t k1_form_ref;           // one-lane-per-slice K1 as cabac_code.h writes the coder (CabacLane) instead of the shipped normalised form
-    uint32_t k1_emit_lds;            // one-lane-per-slice K1 with its digits staged in LDS and stored in 16-byte rows: 1 = on the reference-style form (CabacLaneS), 2 = on the shipped one (CabacLaneNS)
     uint32_t k1_path, no_dense, no_hint;   // the environment switches above, settable per test (non-zero wins over env())
     uint32_t chain_segments;         // K1p: the context chains in segments whatever the batch's size
     uint32_t chain_whole;            // K1p: every context chain start to end (k_k1p_ctxchain alone), no segments
@@ -49,8 +47,6 @@ struct TestHooks {
     uint32_t k2p_seg_len;            // chunks per segment of K2p's overlapped passes (0 = by batch shape): short slices through many segments
     uint32_t local_waves;            // K1p: waves to a workgroup of k_k1p_local (0 = as many waves to a CU as its LDS takes)
     uint32_t chain_nsegs;            // K1p: segments the context chains are cut in (0 = as many as keep the launch in one round of workgroups)
-    uint32_t k1_fwd;                 // one-lane-per-slice K1: four state bytes read ahead with forwarding (CabacLaneN::bin4: a measured variant), not one per bin
-    uint32_t k1_words8;              // one-lane-per-slice K1: the output in 8-byte stores (rounds 1-3), not 16-byte ones
     uint32_t k1_waves;               // one-lane-per-slice K1: waves to a workgroup (0 = the built-in count)
     uint32_t k2p_wave;               // K2p pass 1: 1 = a wave per slice, 2 = a lane per slice, 3 = a lane per slice and a wave each for the longest (0 = by slice count)
     uint32_t verify_flip;            // batch API with verify on: k > 0 complements bit 7 of byte 0 of slice k - 1's output region between the encode and the verifier

@@ -10,19 +10,21 @@
 //
 // Mapping: one lane per slice (each slice has its own coder object in the reference,
 // recode.cpp:1270, 1525, so slices are independent and a slice is strictly serial).
-// One wave (64 slices) per workgroup.  Integer work only; no MFMA.
+// K2: one wave (64 slices) per workgroup; K1: up to kK1Waves waves, which share its tables.  Integer work only; no MFMA.
 //
-// LDS per workgroup (K1):
-//   [0, 1 KiB)          packed CABAC table, 128 x 8 B (avr_tables.h)
-//   [1 KiB, ...)        context states, dword (k, lane) at 4*(k*64 + lane) holds the four
+// LDS per workgroup (K1, k_cabac_encode):
+//   static              tabn, 272 x 16 B: the coder's table by (state or pseudo state, bin) (CabacLaneN::norm_entry);
+//                       sel_off, 2048 x 4 B (one-byte records: 128 x 4 B): selector -> where its state byte lives in a
+//                       lane's column
+//   dynamic, per wave   context states, dword (k, lane) at 4*(k*64 + lane) holds the four
 //                       state bytes 4k..4k+3 of the lane's slice: the bank is lane % 32 for
 //                       every context, so the data-dependent state read and write of a bin
-//                       never conflict across lanes.
+//                       never conflict across lanes.  (n_rows + 4 + 3) / 4 dwords a lane: the
+//                       contexts, then four pseudo contexts.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <mutex>
-#include <type_traits>
 #include <vector>
 #include <stdint.h>
 #include <stdlib.h>
@@ -42,49 +44,12 @@ static __device__ const CabacTables d_tables = make_cabac_tables();
 
 // ------------------------------------------------------------------ K1
 
-// One CABAC bin (cabac_code.h:33-67 on arithmetic_code.h:106-126), written branch-free up to
-// the renormalisation: every lane does the same LDS read / table read / LDS write whatever
-// kind of bin it holds, so a wave never splits on context-vs-bypass.
-//   * where a bin's state byte lives comes from one look-up, sel_off[selector]: contexts have their
-//     byte in the lane's column of the state rows; bypass, terminate and everything else (padding,
-//     selectors that are no context of the batch) go to pseudo contexts whose pseudo states never move;
-//   * the pseudo states are table rows of their own: 128 bypass (flag in .y: the coded range is
-//     range / 2), 130 terminate (LPS range 2 in every range quarter, valMPS 0), 132 no-op (LPS range 0,
-//     and a flag in .y that forces symbol 0, so such a record changes nothing whatever its bin);
-//   * 134 / 135 are the no-op again, but 134's successor is 135 and 135 is its own: the pseudo context that
-//     starts in 134 reads 135 once any bin has gone through it.  That is where a context goes that the slice
-//     declares but the (sampled) census of the batch did not see -- the lane finds out at the end, at no cost
-//     per bin, and hands its slice back (AVR_SLICE_RETRY_SERIAL: coded by a second launch without renumbering).
-//   * 131 / 133 remember put_terminate(1): the terminate context goes 130 -> 131 at the first one and 131 -> 133 at any terminate bin
-//     after it (both rows are no-ops); the caller reads the byte once, at the end of the slice (k_cabac_encode).
-struct CabacLane {
-    CabacEncoder e;
-
-    __device__ __forceinline__ void bin(uint32_t rec, uint32_t off, const uint2 *tab, uint8_t *st_lane) {
-        uint8_t *sp = st_lane + off;                             // state byte of (context, lane): dword (k >> 2, lane), byte k & 3
-        uint32_t s = *sp;
-        // The empty asm statements pin the two LDS reads where they are written: without them
-        // hipcc sinks each read into a branch on the bin kind (it is only "needed" on one side of
-        // a select), which splits the wave and exposes the full LDS latency behind every branch.
-        asm volatile("" : "+v"(s));
-        uint2 ent = tab[s];
-        asm volatile("" : "+v"(ent.x), "+v"(ent.y));
-        // normalize = floor(log2(range / 0x100)) (cabac_code.h:37,59,70-79); range != 0 here
-        const int norm = 23 - __builtin_clz(e.range);
-        const uint32_t q = (e.range >> (norm + 6)) & 3;          // (range_approx & 0x180) >> 7, :39-40
-        const uint32_t r_tab = ((ent.x >> (q * 8)) & 0xffu) << norm;              // :40-41, :60
-        // bypass (:53): its table row is 0 and the top bit of ent.y is set, so this is an OR, not a branch
-        const uint32_t r1 = r_tab | ((e.range >> 1) & uint32_t(int32_t(ent.y) >> 31));
-        const uint32_t sym = (rec ^ s) & 1 & ~(ent.y >> 30);     // :34 (pseudo-states have valMPS 0; the no-op row forces 0)
-        const uint32_t r0 = e.range - r1;                        // arithmetic_code.h:107-114
-        e.low += sym ? r0 : 0u;
-        e.range = sym ? r1 : r0;
-        *sp = uint8_t(ent.y >> (8 * sym));                       // cabac_code.h:43-47
-        if (e.range < 0x200u) e.emit_digit();                    // arithmetic_code.h:115-122 (one digit)
-    }
-};
-
-// The same bin in NORMALISED form (the form of K1p's phase C, avr_k1p.h: c_stretch): the range as 9 bits R in [256, 511]
+// One CABAC bin (cabac_code.h:33-67 on arithmetic_code.h:106-126), written branch-free: every lane does the same LDS
+// read / table read / LDS write whatever kind of bin it holds, so a wave never splits on context-vs-bypass.  Where a
+// bin's state byte lives comes from one look-up, sel_off[selector]: contexts have their byte in the lane's column of
+// the state rows; bypass, terminate and everything else (padding, selectors that are no context of the batch) go to
+// pseudo contexts whose pseudo states never move (norm_entry() below).
+// The coder is in NORMALISED form (the form of K1p's phase C, avr_k1p.h: c_stretch): the range as 9 bits R in [256, 511]
 // with the reference's range = R << e (cabac_code.h:37-41), low as the 64-bit integer L2 = 2 low >> e, and sp = 15 - e the
 // bit of L2 / 2 where the next 16-bit digit of the code string begins.  A digit is due when e drops to 0 (sp >= 15,
 // arithmetic_code.h:115-122) -- but nothing forces it out at that very bin: L2 has room for four more bins (28 shifts at
@@ -107,7 +72,10 @@ struct CabacLaneN {
     __device__ __forceinline__ void bin(uint32_t rec, uint32_t off, const uint4 *tabn, uint8_t *st_lane) {
         uint8_t *spb = st_lane + off;
         uint32_t s = *spb;
-        asm volatile("" : "+v"(s));                              // see CabacLane::bin
+        // The empty asm statements pin the two LDS reads where they are written: without them
+        // hipcc sinks each read into a branch on the bin kind (it is only "needed" on one side of
+        // a select), which splits the wave and exposes the full LDS latency behind every branch.
+        asm volatile("" : "+v"(s));
         uint4 ent = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(tabn) + ((s << 5) | ((rec & 1u) << 4)));
         asm volatile("" : "+v"(ent.x), "+v"(ent.y));
         uint32_t v;
@@ -116,32 +84,17 @@ struct CabacLaneN {
         sp += int32_t(sh);
         *spb = uint8_t(ent.z >> 24);                                             // cabac_code.h:43-47
     }
-    // Four bins with their four state bytes read TOGETHER, before the first is coded: a bin's state is then one LDS round trip (its
-    // table entry) behind the previous bin's instead of two.  A bin whose context one of the group's earlier bins has just moved
-    // takes that bin's successor state instead of the byte read (the latest wins; where the states live does not depend on them,
-    // so the comparisons are off the chain); the four writes follow in order.  Measured variant: k_cabac_encode FORM 4.
-    __device__ __forceinline__ void bin4(const uint32_t (&rec)[4], const uint32_t (&off)[4], const uint4 *tabn, uint8_t *st_lane) {
-        uint32_t s[4], next[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) s[j] = st_lane[off[j]];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint32_t sj = s[j];
-#pragma unroll
-            for (int i = 0; i < j; i++) sj = off[j] == off[i] ? next[i] : sj;
-            asm volatile("" : "+v"(sj));
-            uint4 ent = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(tabn) + ((sj << 5) | ((rec[j] & 1u) << 4)));
-            asm volatile("" : "+v"(ent.x), "+v"(ent.y));
-            uint32_t v;
-            const uint32_t sh = k1p::step_range_c(k1p::CodeEntryC{ent.x, ent.y, ent.z, ent.w}, &R, &v);
-            L2 = (L2 + v) << sh;
-            sp += int32_t(sh);
-            next[j] = ent.z >> 24;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) st_lane[off[j]] = uint8_t(next[j]);
-    }
-    // the table entry of (state or pseudo state s, bin): see k_cabac_encode for the pseudo states
+    // The table entry of (state or pseudo state s, bin).  The pseudo states 128..135 are rows of their own, (s, 0) and (s, 1):
+    //   * 128 bypass: no LPS range, the bin itself is what low gains (the last field says so: the coded range is range / 2);
+    //   * 130 terminate: LPS range 2 in every range quarter, valMPS 0;
+    //   * 132 no-op: LPS range 0 and the MPS side for either bin, so such a record changes nothing whatever its bin;
+    //   * 134 / 135 are the no-op again, but 134's successor is 135 and 135 is its own: the pseudo context that starts in 134
+    //     reads 135 once any bin has gone through it.  That is where a context goes that the slice declares but the (sampled)
+    //     census of the batch did not see -- the lane finds out at the end, at no cost per bin, and hands its slice back
+    //     (AVR_SLICE_RETRY_SERIAL: coded by a second launch without renumbering);
+    //   * 131 / 133 remember put_terminate(1): the terminate context goes 130 -> 131 at the first one, by the entry (130, 1), and
+    //     131 -> 133 at any terminate bin after it (both are no-ops); the caller reads the byte once, at the end of the slice
+    //     (k_cabac_encode).
     static __device__ uint4 norm_entry(uint32_t s, uint32_t bin) {
         uint32_t row, sym, next, byp = 0;
         if (s < 128) {
@@ -158,169 +111,23 @@ struct CabacLaneN {
         const uint32_t k = byp ? bin : 2u * sym;
         return make_uint4(row, sym ? ~0u : 0u, k | next << 24, byp - 23u);
     }
-    template <bool PAIR = false>                                 // PAIR: the output in 16-byte stores (ByteWriter::put16_even_pair)
-    __device__ __forceinline__ void digits() {                   // every digit that is due, oldest first
+    __device__ __forceinline__ void digits() {                   // every digit that is due, oldest first; the output in 16-byte stores (ByteWriter::put16_even_pair)
         while (sp >= 15) {
             uint32_t d = uint32_t(L2 >> (sp + 1));
             L2 &= (uint64_t(2) << sp) - 1;
-            if (__builtin_expect(d >> 16, 0)) { if constexpr (PAIR) e.carry_back_pair(); else e.carry_back(); d &= 0xffffu; }
-            if constexpr (PAIR) e.w.put16_even_pair(d); else e.w.put16_even(d);
+            if (__builtin_expect(d >> 16, 0)) { e.carry_back_pair(); d &= 0xffffu; }
+            e.w.put16_even_pair(d);
             sp -= 16;
         }
     }
-    template <bool PAIR = false>
     __device__ void finish() {                                   // back to the reference's (low, range), then its finish()
-        digits<PAIR>();
-        if constexpr (PAIR) e.w.drain_pair();
+        digits();
+        e.w.drain_pair();
         const uint32_t ex = uint32_t(15 - sp);                   // 1 .. 22
         uint64_t low = L2 << (ex - 1);
         if (low >= CabacEncoder::kOne) { e.carry_back(); low -= CabacEncoder::kOne; }
         e.low = uint32_t(low);
         e.range = R << ex;
-        e.finish();
-    }
-};
-
-// The same bin with the emitter BASELINE.json's north star names -- "wavefront ballots used for output-bit packing": a digit is not
-// shifted into a register word but dropped into the lane's column of a staging area in LDS (16 slots of 64 lanes; slot-major, so
-// the data-dependent slot index never makes a bank conflict), and after every eight bins ONE ballot tells whether any lane has a
-// 16-byte row of eight digits ready; those lanes gather their row and store it whole.  Measured against the 8-byte register word
-// of CabacEncoder on config 5: kept as a test-build variant (hook k1_emit_lds), not shipped.
-struct alignas(8) Row16 { uint32_t x, y, z, w; };
-struct CabacLaneS {
-    CabacEncoder e;                                              // low / range; its byte writer takes over in finish()
-    uint32_t *stage;                                             // this lane's column: slot j at stage[64 j]
-    uint32_t cnt, flushed;                                       // digits produced / stored (flushed: a multiple of 8)
-
-    __device__ __forceinline__ void init(uint8_t *out, uint32_t capacity, uint32_t *column) {
-        e.init(0x7F800000u, out, capacity);
-        stage = column; cnt = flushed = 0;
-    }
-    __device__ void carry() {                                    // arithmetic_code.h:154-157: into the staged digits, then the stored bytes
-        for (uint32_t i = cnt; i > flushed;) {
-            i--;
-            const uint32_t d = (stage[64 * (i & 15u)] + 1u) & 0xffffu;
-            stage[64 * (i & 15u)] = d;
-            if (d) return;
-        }
-        uint32_t p = flushed * 2;
-        if (p > e.w.cap) return;
-        while (p > 0) {
-            p--;
-            const uint32_t b = uint32_t(e.w.base[p]) + 1u;
-            e.w.base[p] = uint8_t(b);
-            if (b <= 0xffu) break;
-        }
-    }
-    __device__ __forceinline__ void bin(uint32_t rec, uint32_t off, const uint2 *tab, uint8_t *st_lane) {
-        uint8_t *sp = st_lane + off;
-        uint32_t s = *sp;
-        asm volatile("" : "+v"(s));
-        uint2 ent = tab[s];
-        asm volatile("" : "+v"(ent.x), "+v"(ent.y));
-        const int norm = 23 - __builtin_clz(e.range);
-        const uint32_t q = (e.range >> (norm + 6)) & 3;
-        const uint32_t r_tab = ((ent.x >> (q * 8)) & 0xffu) << norm;
-        const uint32_t r1 = r_tab | ((e.range >> 1) & uint32_t(int32_t(ent.y) >> 31));
-        const uint32_t sym = (rec ^ s) & 1 & ~(ent.y >> 30);
-        const uint32_t r0 = e.range - r1;
-        e.low += sym ? r0 : 0u;
-        e.range = sym ? r1 : r0;
-        *sp = uint8_t(ent.y >> (8 * sym));
-        if (e.range < 0x200u) {                                  // arithmetic_code.h:115-122, the digit into the staging column
-            if (__builtin_expect(e.low >= CabacEncoder::kOne, 0)) { carry(); e.low -= CabacEncoder::kOne; }
-            stage[64 * (cnt & 15u)] = e.low >> 15;
-            cnt++;
-            e.low = (e.low & 0x7fffu) << 16;
-            e.range <<= 16;
-        }
-    }
-    __device__ __forceinline__ void rows() {                     // after every eight bins: at most 15 digits are staged at any time
-        const bool ready = cnt - flushed >= 8u;
-        if (__ballot(ready)) {
-            if (ready) {
-                uint32_t d[8];
-#pragma unroll
-                for (uint32_t j = 0; j < 8; j++) d[j] = stage[64 * ((flushed + j) & 15u)];
-                Row16 v;                                         // digits most significant byte first (arithmetic_code.h:184-190)
-                v.x = __builtin_bswap32(d[0] << 16 | d[1]); v.y = __builtin_bswap32(d[2] << 16 | d[3]);
-                v.z = __builtin_bswap32(d[4] << 16 | d[5]); v.w = __builtin_bswap32(d[6] << 16 | d[7]);
-                if (flushed * 2 + 16 <= e.w.cap) *reinterpret_cast<Row16 *>(e.w.base + flushed * 2) = v;
-                flushed += 8;
-            }
-        }
-    }
-    __device__ void finish() {                                   // what is still staged goes through the byte writer, then finish() as it stands
-        e.w.n = flushed * 2;
-        e.w.acc = 0;
-        for (uint32_t i = flushed; i < cnt; i++) e.w.put16_even(stage[64 * (i & 15u)]);
-        e.finish();
-    }
-};
-
-// The normalised form with CabacLaneS's emitter: the due digits go into the lane's staging column, whole 16-byte rows out
-// by one ballot per eight bins.  The normalised form waits where the other one computes (62 % of its wave-cycles on config 5);
-// if it waited for its own output -- 8-byte stores of a lane's own, ten times the bytes in 64-byte requests -- this would be
-// the faster kernel.  It is not: 2.88 against 2.49 ms on config 5.  A measured variant (test hook k1_emit_lds=2).
-struct CabacLaneNS : CabacLaneN {
-    uint32_t *stage;                                             // this lane's column: slot j at stage[64 j]
-    uint32_t cnt, flushed;                                       // digits produced / stored (flushed: a multiple of 8)
-
-    __device__ __forceinline__ void init(uint8_t *out, uint32_t capacity, uint32_t *column) {
-        CabacLaneN::init(out, capacity);
-        stage = column; cnt = flushed = 0;
-    }
-    __device__ void carry() {                                    // arithmetic_code.h:154-157: into the staged digits, then the stored bytes
-        for (uint32_t i = cnt; i > flushed;) {
-            i--;
-            const uint32_t d = (stage[64 * (i & 15u)] + 1u) & 0xffffu;
-            stage[64 * (i & 15u)] = d;
-            if (d) return;
-        }
-        uint32_t p = flushed * 2;
-        if (p > e.w.cap) return;
-        while (p > 0) {
-            p--;
-            const uint32_t b = uint32_t(e.w.base[p]) + 1u;
-            e.w.base[p] = uint8_t(b);
-            if (b <= 0xffu) break;
-        }
-    }
-    __device__ __forceinline__ void digits() {                   // every digit that is due, oldest first (at most 5 per eight bins: 16 slots do)
-        while (sp >= 15) {
-            uint32_t d = uint32_t(L2 >> (sp + 1));
-            L2 &= (uint64_t(2) << sp) - 1;
-            if (__builtin_expect(d >> 16, 0)) { carry(); d &= 0xffffu; }
-            stage[64 * (cnt & 15u)] = d;
-            cnt++;
-            sp -= 16;
-        }
-    }
-    __device__ __forceinline__ void rows() {                     // after every eight bins
-        const bool ready = cnt - flushed >= 8u;
-        if (__ballot(ready)) {
-            if (ready) {
-                uint32_t d[8];
-#pragma unroll
-                for (uint32_t j = 0; j < 8; j++) d[j] = stage[64 * ((flushed + j) & 15u)];
-                Row16 v;                                         // digits most significant byte first (arithmetic_code.h:184-190)
-                v.x = __builtin_bswap32(d[0] << 16 | d[1]); v.y = __builtin_bswap32(d[2] << 16 | d[3]);
-                v.z = __builtin_bswap32(d[4] << 16 | d[5]); v.w = __builtin_bswap32(d[6] << 16 | d[7]);
-                if (flushed * 2 + 16 <= e.w.cap) *reinterpret_cast<Row16 *>(e.w.base + flushed * 2) = v;
-                flushed += 8;
-            }
-        }
-    }
-    __device__ void finish() {                                   // back to the reference's (low, range); what is staged through the byte writer; its finish()
-        digits();
-        const uint32_t ex = uint32_t(15 - sp);                   // 1 .. 22
-        uint64_t low = L2 << (ex - 1);
-        if (low >= CabacEncoder::kOne) { carry(); low -= CabacEncoder::kOne; }
-        e.low = uint32_t(low);
-        e.range = R << ex;
-        e.w.n = flushed * 2;
-        e.w.acc = 0;
-        for (uint32_t i = flushed; i < cnt; i++) e.w.put16_even(stage[64 * (i & 15u)]);
         e.finish();
     }
 };
@@ -332,24 +139,20 @@ constexpr uint32_t kK1MaxWaves = 16;
 // table / index: the dense renumbering of the batch's contexts (k_k1p_densemap), or null: contexts as the caller
 // numbers them.  n_rows: contexts the kernel keeps states for (dense count, or n_states); init_states / final_states
 // rows are n_states wide, in the caller's numbering.
-// FORM: 1 = normalised form (CabacLaneN: shipped; its output in 16-byte stores), 5 = that with 8-byte stores, 4 = with four state bytes read ahead,
-// 0 = the coder as cabac_code.h writes it (CabacLane), 2 = that with its digits
-// staged in LDS (CabacLaneS), 3 = the normalised form with them (CabacLaneNS); 0, 2 and 3 are measured variants of the test build.
+// The coder is CabacLaneN; the forms it was measured against are gone from the library: their numbers are in DESIGN.md section 4.
 // REC_BYTES: 2 = two-byte records (AVR_KIND_CABAC, AVR_NOP_CABAC padding), 1 = ONE-BYTE tiles (AVR_KIND_CABAC8, 16 records a chunk:
-// k_pack_tiles8_narrow) -- FORM 1 only, no renumbering (table / index null, n_rows = n_states <= AVR_MAX_STATES8: the selectors are
+// k_pack_tiles8_narrow) -- no renumbering (table / index null, n_rows = n_states <= AVR_MAX_STATES8: the selectors are
 // dense ids already), at most kK1Waves waves: reading sixteen selectors ahead takes registers, and a 1024-thread bound caps a lane at 128.
-template <bool TILED, int FORM, int REC_BYTES = 2>
+template <bool TILED, int REC_BYTES = 2>
 __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) void k_cabac_encode(
     const void *recs, const uint64_t *off, const uint32_t *n_bins, const uint32_t *order,
     uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const uint16_t *table, const uint16_t *index, uint32_t n_rows,
     uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
     uint8_t *final_states, int32_t want_status) {
-    extern __shared__ uint32_t lds[];                            // per wave: state dwords [(n_rows + 4 + 3) / 4][64]; FORM 2: then 16 x 64 staging slots per wave
-    constexpr bool NORM = FORM == 1 || FORM == 3 || FORM == 4 || FORM == 5;           // 5: FORM 1 with 8-byte output stores (rounds 1-3)
+    extern __shared__ uint32_t lds[];                            // per wave: state dwords [(n_rows + 4 + 3) / 4][64]
     constexpr bool W8 = REC_BYTES == 1;
-    static_assert(REC_BYTES == 2 || (W8 && TILED && FORM == 1), "one-byte records: tiles, FORM 1");
-    __shared__ uint2 tab[136];                                   // 128 states + pseudo-states 128..135
-    __shared__ uint4 tabn[NORM ? 272 : 1];                       // the normalised form's: by (state, bin)
+    static_assert(REC_BYTES == 2 || (W8 && TILED), "one-byte records: tiles");
+    __shared__ uint4 tabn[272];                                  // the coder's table: by (state, bin)
     __shared__ uint32_t sel_off[W8 ? 128 : 2048];                // selector -> byte offset of its state in the lane's column (up to 256 rows of 256 bytes, + 3)
 
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -368,14 +171,7 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
         if (in_range && want_status == AVR_SLICE_OK) out_len[slice] = 0;
         return;
     }
-    for (uint32_t i = threadIdx.x; i < 128; i += blockDim.x)
-        tab[i] = make_uint2(d_tables.packed[i][0], d_tables.packed[i][1]);
-    if (threadIdx.x < 8) {                                       // 128: bypass, 130: terminate (LPS range 2), 131 / 133: after put_terminate(1), 132 / 134 / 135: no-op
-        const uint32_t t = threadIdx.x, ps = 128 + t, next = t == 6 ? 135u : (t == 3 || t == 5) ? 133u : ps, lps = t == 2 ? 131u : next;
-        tab[ps] = make_uint2(t == 2 ? 0x02020202u : 0u, (t == 0 ? 0x80000000u : t >= 3 ? 0x40000000u : 0u) | next | lps << 8);
-    }
-    if constexpr (NORM)
-        for (uint32_t i = threadIdx.x; i < 272; i += blockDim.x) tabn[i] = CabacLaneN::norm_entry(i >> 1, i & 1u);
+    for (uint32_t i = threadIdx.x; i < 272; i += blockDim.x) tabn[i] = CabacLaneN::norm_entry(i >> 1, i & 1u);
     if constexpr (W8) {                                          // a one-byte selector: a context's row as it is, 126 bypass, 127 terminate
         for (uint32_t sel = threadIdx.x; sel < 128; sel += blockDim.x) {
             const uint32_t k = sel < n_states ? sel : sel == AVR_SEL8_BYPASS ? n_rows : sel == AVR_SEL8_TERMINATE ? n_rows + 1 : n_rows + 2;
@@ -438,13 +234,10 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
     }
     __syncthreads();
 
-    typename std::conditional<FORM == 3, CabacLaneNS, typename std::conditional<FORM == 1 || FORM == 4 || FORM == 5, CabacLaneN,
-        typename std::conditional<FORM == 2, CabacLaneS, CabacLane>::type>::type>::type L;
+    CabacLaneN L;
     const uint64_t o0 = in_range ? out_off[slice] : 0;
     const uint32_t cap = in_range ? region_capacity(o0, out_off[slice + 1]) : 0;
-    if constexpr (FORM == 1 || FORM == 4 || FORM == 5) L.init(out + o0, cap);
-    else if constexpr (FORM == 2 || FORM == 3) L.init(out + o0, cap, lds + (blockDim.x >> 6) * rows4 * 64 + wv * 1024 + lane);
-    else L.e.init(0x7F800000u, out + o0, cap);                   // cabac_code.h:30
+    L.init(out + o0, cap);
 
     const ChunkSource<TILED> src(recs, off, in_range ? g : 0, slice);
     const uint32_t n_chunks = W8 ? (nb + 15) >> 4 : (nb + 7) >> 3;
@@ -465,18 +258,8 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
 #pragma unroll
         for (uint32_t k = 0; k < 8; k++) {
             const uint32_t rec = (w[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
-            if constexpr (FORM == 4) {
-                if ((k & 3) == 0) {
-                    const uint32_t r4[4] = {w[k >> 1] & 0xffffu, w[k >> 1] >> 16, w[(k >> 1) + 1] & 0xffffu, w[(k >> 1) + 1] >> 16};
-                    const uint32_t o4[4] = {offs[k], offs[k + 1], offs[k + 2], offs[k + 3]};
-                    L.bin4(r4, o4, tabn, st_lane);
-                }
-            } else
-            if constexpr (NORM) L.bin(rec, offs[k], tabn, st_lane);
-            else L.bin(rec, offs[k], tab, st_lane);
-            if constexpr (FORM == 1) { if ((k & 3) == 3) L.template digits<true>(); }
-            else if constexpr (NORM) { if ((k & 3) == 3) L.digits(); }
-            if constexpr (FORM == 2 || FORM == 3) { if (k == 7) L.rows(); }
+            L.bin(rec, offs[k], tabn, st_lane);
+            if ((k & 3) == 3) L.digits();
         }
     };
     // One-byte records: sixteen bins a chunk.  A byte has no no-op value (with n_states = 126 every selector means something), so the
@@ -492,7 +275,7 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
 #pragma unroll
             for (uint32_t k = 0; k < 16; k++) {
                 L.bin(w[k >> 2] >> (8 * (k & 3)), offs[k], tabn, st_lane);
-                if ((k & 3) == 3) L.template digits<true>();
+                if ((k & 3) == 3) L.digits();
             }
         }
     };
@@ -528,9 +311,7 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
         if (active) {
             const bool missed = st_lane[(((n_rows + 3) >> 2) << 8) + ((n_rows + 3) & 3)] == 135u;
             if (after_finish) st = AVR_SLICE_BAD_RECORD;
-            else if constexpr (FORM == 1) L.template finish<true>();
-            else if constexpr (FORM != 0) L.finish();
-            else L.e.finish();                                   // cabac_code.h:63-65 / ~encoder(), arithmetic_code.h:100
+            else L.finish();                                     // cabac_code.h:63-65 / ~encoder(), arithmetic_code.h:100
             L.e.w.flush();
             if (st == AVR_SLICE_OK && L.e.w.n > cap) st = AVR_SLICE_OVERFLOW;
             if (missed) { st = AVR_SLICE_RETRY_SERIAL; L.e.w.n = 0; }   // whatever else: the bytes are not the slice's
@@ -773,7 +554,7 @@ __global__ __launch_bounds__(64) void k_pack_tiles8(
     if (active && bad) status[slice] = AVR_SLICE_BAD_RECORD;
 }
 
-// The same records into ONE-BYTE tiles (include/avrecode_ms_amd.h: sixteen records a 16-byte chunk), what k_cabac_encode<true, 1, 1>
+// The same records into ONE-BYTE tiles (include/avrecode_ms_amd.h: sixteen records a 16-byte chunk), what k_cabac_encode<true, 1>
 // reads: validated (the rule of k_pack_tiles8) and transposed in one pass, every byte as it came -- the bytes past n_bins too, which
 // the coder tells apart by their index.  A lane writes its slice's own chunks only; the rest of its tile column is never read.
 __global__ __launch_bounds__(64) void k_pack_tiles8_narrow(
@@ -1016,7 +797,7 @@ hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st
             return err;                                          // contexts without bins keep their state
     }
     auto launch = [&](uint32_t rows, const uint16_t *tb, const uint16_t *ix, int32_t want) -> hipError_t {
-        const uint32_t per_wave = ((rows + 4 + 3) / 4) * 256 + (test_hooks().k1_emit_lds ? 4096u : 0u);     // (+ the staging slots of FORMs 2, 3)
+        const uint32_t per_wave = ((rows + 4 + 3) / 4) * 256;
         uint32_t want_waves = test_hooks().k1_waves ? test_hooks().k1_waves : kK1Waves;
         if (want_waves > kK1MaxWaves) want_waves = kK1MaxWaves;
         const uint32_t waves = per_wave * want_waves <= 60 * 1024 ? want_waves : per_wave * 4 <= 60 * 1024 ? 4 : per_wave * 2 <= 60 * 1024 ? 2 : 1;
@@ -1024,11 +805,8 @@ hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st
         const dim3 grid((n_slices + 64 * waves - 1) / (64 * waves)), block(64 * waves);
         // Shipped: the coder in normalised form with the digits taken every fourth bin, in step across the wave (CabacLaneN) --
         // since round 3's table entries (avr_k1p.h, CodeEntryC) 31 VALU instructions a bin against the 48 of the form that reads
-        // like cabac_code.h, and 2.44 against 2.55 ms per step on config 5.  Test hooks: k1_form_ref = that form (CabacLane),
-        // k1_emit_lds = 1: it with the digits staged in LDS (CabacLaneS), 2: the shipped form with them (CabacLaneNS); same bytes all.
-        const int form = test_hooks().k1_emit_lds ? (test_hooks().k1_emit_lds == 2 ? 3 : 2) : test_hooks().k1_form_ref ? 0 : test_hooks().k1_fwd ? 4 : test_hooks().k1_words8 ? 5 : 1;
-        auto kern = in.tiled ? (form == 5 ? k_cabac_encode<true, 5> : form == 4 ? k_cabac_encode<true, 4> : form == 1 ? k_cabac_encode<true, 1> : form == 2 ? k_cabac_encode<true, 2> : form == 3 ? k_cabac_encode<true, 3> : k_cabac_encode<true, 0>)
-                          : (form == 5 ? k_cabac_encode<false, 5> : form == 4 ? k_cabac_encode<false, 4> : form == 1 ? k_cabac_encode<false, 1> : form == 2 ? k_cabac_encode<false, 2> : form == 3 ? k_cabac_encode<false, 3> : k_cabac_encode<false, 0>);
+        // like cabac_code.h, and 2.44 against 2.55 ms per step on config 5.  The other forms that were measured: DESIGN.md section 4.
+        auto kern = in.tiled ? k_cabac_encode<true> : k_cabac_encode<false>;
         if (lds > 48 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
             if (e != hipSuccess) return e;
@@ -1049,7 +827,7 @@ hipError_t launch_cabac8_encode(hipStream_t s, const Slices &in, const States &s
     if (n_slices == 0) return hipSuccess;
     const uint32_t lds = kK1Waves * ((n_states + 4 + 3) / 4) * 256;
     const dim3 grid((n_slices + 64 * kK1Waves - 1) / (64 * kK1Waves)), block(64 * kK1Waves);
-    hipLaunchKernelGGL((k_cabac_encode<true, 1, 1>), grid, block, lds, s, in.recs, in.off, in.n_bins, in.order, n_slices, st.init_states,
+    hipLaunchKernelGGL((k_cabac_encode<true, 1>), grid, block, lds, s, in.recs, in.off, in.n_bins, in.order, n_slices, st.init_states,
                        n_states, nullptr, nullptr, n_states, o.out, o.out_off, o.out_len, o.status, st.final_states, int32_t(AVR_SLICE_OK));
     return hipGetLastError();
 }

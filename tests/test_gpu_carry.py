@@ -107,18 +107,6 @@ def test_serial_k1_tiles_and_slice_major(avr, cabac):
     check_cabac(w, wants, "slice major")
 
 
-@pytest.mark.parametrize("form", ["words8", "ref", "lds", "ref-lds", "fwd"])
-def test_serial_k1_forms(avr, cabac, hooks, form):
-    """The one-lane-per-slice coder's other forms (test hooks): 8-byte stores, the reference's own form, digits staged in LDS
-    rows (on both forms), state bytes read ahead.  (The shipped 16-byte pair form: test_serial_k1_tiles_and_slice_major.)"""
-    hooks(**{"words8": {"k1_words8": 1}, "ref": {"k1_form_ref": 1}, "lds": {"k1_emit_lds": 2},
-             "ref-lds": {"k1_emit_lds": 1}, "fwd": {"k1_fwd": 1}}[form])
-    slices, wants, _ = cabac
-    w = cabac_workload(avr, slices)
-    w.encode()
-    check_cabac(w, wants, form)
-
-
 # ------------------------------------------------------------------ K1p
 
 @pytest.mark.parametrize("mode", ["one-call", "parts2", "parts3", "census", "retry"])
