@@ -40,9 +40,9 @@ EXPECT_NONE = 0xFFFFFFFF                                      # expect_len of a 
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_restore.hip", "avr_api.cpp"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_restore.hip", "avr_plan_dev.hip", "avr_api.cpp"]
 _DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
-                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h"]
+                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h", "avr_plan_dev.h"]
 
 
 class AvrError(RuntimeError):
@@ -124,6 +124,21 @@ class ChunkedPart(ctypes.Structure):
 
 
 MAX_PARTS = 8
+PLAN_SERIAL, PLAN_CHUNKS, PLAN_CODES, PLAN_K1P = 0, 1, 2, 3
+
+
+class PlanArrays(ctypes.Structure):
+    """avr_plan_arrays: the device arrays avr_plan_chunks_device writes (include/avrecode_ms_amd.h)."""
+    _fields_ = [("out_off", c_void_p), ("rec_off", c_void_p), ("rec_round", c_uint32),
+                ("chunk_base", c_void_p), ("chunk_slice", c_void_p), ("cap_chunks", c_uint64),
+                ("dig_off", c_void_p), ("res_off", c_void_p),
+                ("blk_base", c_void_p), ("blk_slice", c_void_p), ("cap_blocks", c_uint64)]
+
+
+class PlanTotals(ctypes.Structure):
+    """avr_plan_totals: what the device plan calls report, valid after a synchronisation."""
+    _fields_ = [(name, c_uint64) for name in ("total_bins", "out_total", "rec_total", "res_total", "dig_total", "total_chunks",
+                                              "total_blocks", "tile_chunks")]
 
 
 class SynthConfig(ctypes.Structure):
@@ -245,6 +260,12 @@ SIGNATURES = {
                                                c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "avr_range_encode_slices_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avr_plan_bounds": (None, [c_size_t, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
+    "avr_plan_workspace_bytes": (c_size_t, [c_size_t]),
+    "avr_plan_chunks_device": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "avr_plan_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "avr_chunk_plan_from": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "avr_compact_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_void_p, c_void_p, c_size_t]),
     "avr_context_census_device": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_void_p]),
     "avr_context_remap_device": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_void_p]),
     "avr_states_permute_device": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
@@ -621,9 +642,11 @@ class MultiBatch:
         return out.tolist()
 
 
-from .device import DeviceWorkload, encode_tiles, plan_tiles, synth_config  # noqa: E402  (torch-backed helpers)
+from .device import (DeviceWorkload, chunk_plan_arrays_device, compact_device, device_plan, encode_tiles, plan_tiles,  # noqa: E402
+                     plan_tiles_device, synth_config)  # noqa: E402  (torch-backed helpers)
 
 __all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS",
            "SEL_BYPASS", "SEL_TERMINATE", "SLICE_VERIFY_FAILED", "VERIFY_NONE", "EXPECT_NONE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
-           "make_cabac_records", "make_range_records", "plan_tiles", "synth_config", "tail_patch"]
+           "make_cabac_records", "make_range_records", "plan_tiles", "plan_tiles_device", "chunk_plan_arrays_device", "compact_device",
+           "device_plan", "synth_config", "tail_patch"]

@@ -24,6 +24,7 @@
 #include "avr_cabac_verify.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
+#include "avr_plan_dev.h"
 #include "avr_synth.h"
 #include "avr_tables.h"
 
@@ -1597,6 +1598,81 @@ int avr_restore_check_device(int device, void *stream, const uint8_t *out, const
     if (reinterpret_cast<uintptr_t>(expect) & 7) return fail(AVR_ERR_INVALID, "expect is not 8-byte aligned");
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_restore_check(hip(stream), OutputView{out, out_off, out_len, status}, uint32_t(n_slices), expect, expect_off, expect_len, first_diff));
+    return AVR_OK;
+}
+
+// ------------------------------------------------------------------ the plan and the compaction on the device (avr_plan_dev.hip)
+
+void avr_plan_bounds(size_t n_slices, uint64_t max_total_bins, uint64_t *cap_chunks, uint64_t *cap_blocks) {
+    avr::plan_dev::bounds(n_slices, max_total_bins, cap_chunks, cap_blocks);
+}
+
+size_t avr_plan_workspace_bytes(size_t n_slices) { return size_t(avr::plan_dev::workspace_bytes(n_slices)); }
+
+// what the three calls ask of n_slices, their workspace and an array's alignment: no device needed
+static int check_plan_call(size_t n_slices, const void *workspace, size_t workspace_bytes) {
+    if (n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_slices %zu out of range", n_slices);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) return fail(AVR_ERR_INVALID, "workspace null or not 256-byte aligned");
+    if (workspace_bytes < avr_plan_workspace_bytes(n_slices))
+        return fail(AVR_ERR_INVALID, "workspace of %zu bytes, avr_plan_workspace_bytes says %zu", workspace_bytes, avr_plan_workspace_bytes(n_slices));
+    return AVR_OK;
+}
+static bool misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
+
+int avr_plan_chunks_device(int device, void *stream, const uint32_t *n_bins, size_t n_slices, int level, const avr_plan_arrays *arrays,
+                           void *workspace, size_t workspace_bytes, avr_plan_totals *totals) {
+    if (!arrays || !totals) return fail(AVR_ERR_INVALID, "null arrays or totals");
+    if (level < AVR_PLAN_SERIAL || level > AVR_PLAN_K1P) return fail(AVR_ERR_INVALID, "level %d: expected 0..3 (AVR_PLAN_*)", level);
+    if (int rc = check_plan_call(n_slices, workspace, workspace_bytes)) return rc;
+    const avr_plan_arrays &a = *arrays;
+    if (a.rec_round != 8 && a.rec_round != 16) return fail(AVR_ERR_INVALID, "rec_round %u: expected 8 or 16", a.rec_round);
+    // the n + 1 arrays are written even for an empty batch (their single zero); chunk_slice / blk_slice only with slices
+    if (!a.out_off || (level >= AVR_PLAN_CHUNKS && !a.chunk_base) || (level >= AVR_PLAN_CODES && !a.dig_off) ||
+        (level >= AVR_PLAN_K1P && (!a.res_off || !a.blk_base)))
+        return fail(AVR_ERR_INVALID, "null array that level %d writes", level);
+    if (n_slices && (!n_bins || (level >= AVR_PLAN_CHUNKS && !a.chunk_slice) || (level >= AVR_PLAN_K1P && !a.blk_slice)))
+        return fail(AVR_ERR_INVALID, "null array that level %d needs", level);
+    if (misaligned(n_bins, 4) || misaligned(totals, 8) || misaligned(a.out_off, 8) || misaligned(a.rec_off, 8) ||
+        (level >= AVR_PLAN_CHUNKS && (misaligned(a.chunk_base, 4) || misaligned(a.chunk_slice, 4))) || (level >= AVR_PLAN_CODES && misaligned(a.dig_off, 8)) ||
+        (level >= AVR_PLAN_K1P && (misaligned(a.res_off, 8) || misaligned(a.blk_base, 4) || misaligned(a.blk_slice, 4))))
+        return fail(AVR_ERR_INVALID, "misaligned array");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_plan_chunks(hip(stream), n_bins, uint32_t(n_slices), level, a, workspace, totals));
+    return AVR_OK;
+}
+
+int avr_plan_tiles_device(int device, void *stream, const uint32_t *n_bins, size_t n_slices, uint32_t records_per_chunk, uint32_t *order,
+                          uint64_t *tile_off, void *workspace, size_t workspace_bytes, avr_plan_totals *totals) {
+    if (!totals || !tile_off) return fail(AVR_ERR_INVALID, "null totals or tile_off");
+    if (records_per_chunk != 8 && records_per_chunk != 16) return fail(AVR_ERR_INVALID, "records_per_chunk %u: expected 8 or 16", records_per_chunk);
+    if (int rc = check_plan_call(n_slices, workspace, workspace_bytes)) return rc;
+    if (n_slices && (!n_bins || !order)) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (misaligned(n_bins, 4) || misaligned(order, 4) || misaligned(tile_off, 8) || misaligned(totals, 8)) return fail(AVR_ERR_INVALID, "misaligned array");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_plan_tiles(hip(stream), n_bins, uint32_t(n_slices), records_per_chunk, order, tile_off, workspace, totals));
+    return AVR_OK;
+}
+
+int avr_chunk_plan_from(const avr_plan_arrays *arrays, const avr_plan_totals *totals, avr_chunk_plan *plan) {
+    if (!arrays || !totals || !plan) return fail(AVR_ERR_INVALID, "null pointer");
+    if (totals->total_chunks > arrays->cap_chunks || totals->total_blocks > arrays->cap_blocks)
+        return fail(AVR_ERR_CAPACITY, "%llu chunks and %llu blocks, room for %llu and %llu: the bound on the bins did not hold",
+                    (unsigned long long)totals->total_chunks, (unsigned long long)totals->total_blocks, (unsigned long long)arrays->cap_chunks,
+                    (unsigned long long)arrays->cap_blocks);
+    if ((totals->total_chunks >> 32) || (totals->total_blocks >> 32)) return fail(AVR_ERR_CAPACITY, "2^32 chunks or blocks and more: chunk_base / blk_base have wrapped");
+    *plan = avr_chunk_plan{arrays->res_off, arrays->chunk_base, arrays->chunk_slice, arrays->blk_base, arrays->blk_slice, arrays->dig_off,
+                           totals->res_total, totals->dig_total, uint32_t(totals->total_chunks), uint32_t(totals->total_blocks)};
+    return AVR_OK;
+}
+
+int avr_compact_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, size_t n_slices,
+                       uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off, void *workspace, size_t workspace_bytes) {
+    if (!dense_off) return fail(AVR_ERR_INVALID, "null dense_off");
+    if (int rc = check_plan_call(n_slices, workspace, workspace_bytes)) return rc;
+    if (n_slices && (!out || !out_off || !out_len || (!dense && dense_capacity))) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (misaligned(out_off, 8) || misaligned(out_len, 4) || misaligned(dense_off, 8)) return fail(AVR_ERR_INVALID, "misaligned array");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_compact_wide(hip(stream), out, out_off, out_len, uint32_t(n_slices), dense, dense_capacity, dense_off, workspace));
     return AVR_OK;
 }
 

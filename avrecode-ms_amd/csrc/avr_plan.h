@@ -2,7 +2,8 @@
 // avr_chunk_plan, the slices' output regions, the tiles, and whether the batch goes through the intra-slice parallel kernels.  Each rule is
 // written ONCE here; the kernels index chunk_slice[], res_off[] and dig_off[] unchecked, so these rules keep them inside their
 // buffers.  Python twin: chunk_plan_arrays() in avrecode-ms_amd/device.py; tests/test_plan.py holds the two to each other and to
-// recorded numbers.  Host only, plain C++17, no HIP header: tests/plan_check.cpp compiles it alone.
+// recorded numbers.  Plain C++17, no HIP header: tests/plan_check.cpp compiles it alone.  The per-slice rules are `__host__ __device__`
+// under hipcc, in the way avr_div.h is: the device planner (avr_plan_dev.hip) applies the very functions fill_plan applies.
 #pragma once
 #include <algorithm>
 #include <numeric>
@@ -10,14 +11,20 @@
 
 #include "avr_layout.h"
 
+#if defined(__HIPCC__)
+#define AVR_PLAN_HD __host__ __device__ inline
+#else
+#define AVR_PLAN_HD inline
+#endif
+
 namespace avr {
 
 // ------------------------------------------------------------------ per slice of nb bins
-inline uint32_t slice_chunks(uint64_t nb) { return nb ? uint32_t((nb + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS) : 1u; }            // an empty slice has one
-inline uint32_t slice_blocks(uint64_t nb) { return nb ? uint32_t((nb + AVR_SORT_BLOCK_BINS - 1) / AVR_SORT_BLOCK_BINS) : 1u; }  // census blocks
-inline uint64_t slice_work_bytes(uint64_t nb) { return ((nb + 15) & ~uint64_t(15)) + 16; }   // per-bin work arrays: whole 16-byte groups and one more
-inline uint64_t slice_digit_sums(uint64_t nb) { return nb / 2 + 8; }
-inline uint64_t slice_out_bytes(uint64_t nb) { return (nb + 16 + 7) & ~uint64_t(7); }        // worst case 8 bits per bin for either coder ("output sizing") + stop bytes
+AVR_PLAN_HD uint32_t slice_chunks(uint64_t nb) { return nb ? uint32_t((nb + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS) : 1u; }            // an empty slice has one
+AVR_PLAN_HD uint32_t slice_blocks(uint64_t nb) { return nb ? uint32_t((nb + AVR_SORT_BLOCK_BINS - 1) / AVR_SORT_BLOCK_BINS) : 1u; }  // census blocks
+AVR_PLAN_HD uint64_t slice_work_bytes(uint64_t nb) { return ((nb + 15) & ~uint64_t(15)) + 16; }   // per-bin work arrays: whole 16-byte groups and one more
+AVR_PLAN_HD uint64_t slice_digit_sums(uint64_t nb) { return nb / 2 + 8; }
+AVR_PLAN_HD uint64_t slice_out_bytes(uint64_t nb) { return (nb + 16 + 7) & ~uint64_t(7); }        // worst case 8 bits per bin for either coder ("output sizing") + stop bytes
 
 // Which arrays a path reads; each level needs those of the levels before it.
 //   Serial   one lane per slice: out_off

@@ -60,6 +60,112 @@ def chunk_plan_arrays(n_bins):
     return t, (int(res_off[-1]), int(dig_off[-1]), int(chunk_base[-1]), int(blk_base[-1]))
 
 
+def _plan_workspace(n_slices, dev):
+    """(tensor, its 256-byte aligned address, the quoted bytes): the one workspace of the three device plan calls."""
+    import torch
+    n = lib().avr_plan_workspace_bytes(n_slices)
+    ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+    return ws, _aligned(ws), n
+
+
+def _device_index(t):
+    return t.device.index if t.device.index is not None else 0
+
+
+def device_plan(n_bins, level=0, rec_round=None, max_total_bins=None):
+    """avr_plan_chunks_device on torch's current stream: the arrays of `level` (PLAN_SERIAL .. PLAN_K1P) for per-slice bin counts
+    (int32 tensor on a GPU), as a dict of tensors -- out_off, rec_off (rec_round 8 or 16; None: left out), and by level chunk_base,
+    chunk_slice, dig_off, res_off, blk_base, blk_slice -- and the PlanTotals.  max_total_bins: an upper bound on the bins, which sizes
+    chunk_slice / blk_slice (avr_plan_bounds); None: a PLAN_SERIAL call asks the device for the sum first.  Synchronises once (twice
+    without a bound) and checks the bound (avr_chunk_plan_from)."""
+    import torch
+    from . import PLAN_CHUNKS, PLAN_CODES, PLAN_K1P, ChunkPlan, PlanArrays, PlanTotals
+    L = lib()
+    dev, n = n_bins.device, n_bins.numel()
+    if n_bins.dtype != torch.int32 or dev.type != "cuda":
+        raise AvrError("device_plan: n_bins must be an int32 tensor on a GPU")
+    n_bins = n_bins.contiguous()
+    if level >= PLAN_CHUNKS and max_total_bins is None:
+        max_total_bins = device_plan(n_bins)[1].total_bins
+    with torch.cuda.device(dev):
+        caps = [ctypes.c_uint64(0), ctypes.c_uint64(0)]
+        if level >= PLAN_CHUNKS:
+            L.avr_plan_bounds(n, int(max_total_bins), ctypes.byref(caps[0]), ctypes.byref(caps[1]))
+        t = dict(out_off=torch.empty(n + 1, dtype=torch.int64, device=dev))
+        if rec_round is not None:
+            t["rec_off"] = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if level >= PLAN_CHUNKS:
+            t["chunk_base"] = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            t["chunk_slice"] = torch.empty(caps[0].value, dtype=torch.int32, device=dev)
+        if level >= PLAN_CODES:
+            t["dig_off"] = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if level >= PLAN_K1P:
+            t["res_off"] = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            t["blk_base"] = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            t["blk_slice"] = torch.empty(caps[1].value, dtype=torch.int32, device=dev)
+        ptr = lambda name: t[name].data_ptr() if name in t else None
+        arrays = PlanArrays(ptr("out_off"), ptr("rec_off"), rec_round or 8, ptr("chunk_base"), ptr("chunk_slice"), caps[0].value,
+                            ptr("dig_off"), ptr("res_off"), ptr("blk_base"), ptr("blk_slice"), caps[1].value)
+        ws, ws_ptr, ws_bytes = _plan_workspace(n, dev)
+        totals = torch.zeros(8, dtype=torch.int64).pin_memory()
+        _check(L.avr_plan_chunks_device(_device_index(n_bins), _stream_ptr(torch), n_bins.data_ptr(), n, level, ctypes.byref(arrays),
+                                        ws_ptr, ws_bytes, totals.data_ptr()))
+        torch.cuda.current_stream().synchronize()
+    tot = PlanTotals(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in totals.tolist()])
+    _check(L.avr_chunk_plan_from(ctypes.byref(arrays), ctypes.byref(tot), ctypes.byref(ChunkPlan())))
+    if "chunk_slice" in t:
+        t["chunk_slice"] = t["chunk_slice"][:tot.total_chunks]
+    if "blk_slice" in t:
+        t["blk_slice"] = t["blk_slice"][:tot.total_blocks]
+    return t, tot
+
+
+def chunk_plan_arrays_device(n_bins, max_total_bins=None):
+    """chunk_plan_arrays() made on the device (avr_plan_chunks_device at PLAN_K1P): the same six tensors, shapes and dtypes, and the
+    same four totals, for an int32 tensor on a GPU."""
+    t, tot = device_plan(n_bins, 3, None, max_total_bins)
+    del t["out_off"]
+    return t, (tot.res_total, tot.dig_total, tot.total_chunks, tot.total_blocks)
+
+
+def plan_tiles_device(n_bins, records_per_chunk=8):
+    """plan_tiles() made on the device (avr_plan_tiles_device on torch's current stream): (order int32[n], tile_off
+    int64[n_tiles + 1]) for an int32 tensor on a GPU.  Enqueues and returns; tile_off[-1] is the tile buffer's size in chunks."""
+    import torch
+    dev, n = n_bins.device, n_bins.numel()
+    if n_bins.dtype != torch.int32 or dev.type != "cuda":
+        raise AvrError("plan_tiles_device: n_bins must be an int32 tensor on a GPU")
+    n_bins = n_bins.contiguous()
+    with torch.cuda.device(dev):
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        tile_off = torch.empty((n + 63) // 64 + 1, dtype=torch.int64, device=dev)
+        totals = torch.empty(8, dtype=torch.int64, device=dev)
+        ws, ws_ptr, ws_bytes = _plan_workspace(n, dev)
+        _check(lib().avr_plan_tiles_device(_device_index(n_bins), _stream_ptr(torch), n_bins.data_ptr(), n, records_per_chunk,
+                                           order.data_ptr(), tile_off.data_ptr(), ws_ptr, ws_bytes, totals.data_ptr()))
+        ws.record_stream(torch.cuda.current_stream())
+        totals.record_stream(torch.cuda.current_stream())
+    return order, tile_off
+
+
+def compact_device(out, out_off, out_len, dense_capacity=None):
+    """avr_compact_device on torch's current stream: (dense uint8[dense_capacity], dense_off int64[n + 1]) -- every slice's
+    min(out_len, region) bytes one behind the other.  dense_capacity None: out_off[-1], which always suffices.  Enqueues and
+    returns; dense_off[-1] > dense_capacity says that the slices from the first that did not fit were not copied."""
+    import torch
+    dev, n = out_off.device, out_len.numel()
+    with torch.cuda.device(dev):
+        if dense_capacity is None:
+            dense_capacity = int(out_off[-1].item())
+        dense = torch.empty(dense_capacity, dtype=torch.uint8, device=dev)
+        dense_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        ws, ws_ptr, ws_bytes = _plan_workspace(n, dev)
+        _check(lib().avr_compact_device(_device_index(out_off), _stream_ptr(torch), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n,
+                                        dense.data_ptr(), dense_capacity, dense_off.data_ptr(), ws_ptr, ws_bytes))
+        ws.record_stream(torch.cuda.current_stream())
+    return dense, dense_off
+
+
 def _aligned(t):
     """t's address rounded up to 256 bytes, as the C ABI wants a workspace (the workspaces here are allocated 256 bytes larger)."""
     return (t.data_ptr() + 255) // 256 * 256
@@ -92,30 +198,41 @@ class DeviceWorkload:
     tiles avr_pack_tiles8_device makes of them (encode() then blocks like any two-byte K1 call), with narrow_tiles=True the one-byte
     tiles of avr_pack_tiles8_narrow_device (encode() is avr_cabac8_encode_tiles_device: nothing waits)."""
 
-    def __init__(self, kind, device_index, n_bins, order, tile_off, tiles, init_states, n_states):
+    def __init__(self, kind, device_index, n_bins, order, tile_off, tiles, init_states, n_states, plan="torch"):
         import torch
+        if plan not in ("torch", "device"):
+            raise AvrError(f"plan={plan!r}: expected 'torch' or 'device'")
+        self.plan_mode = plan
         self.kind, self.device_index = kind, device_index
         self.n_bins, self.order, self.tile_off, self.tiles = n_bins, order, tile_off, tiles
         self.init_states, self.n_states = init_states, n_states
         self.n_slices = n_bins.numel()
         dev = n_bins.device
-        cap = (n_bins.to(torch.int64) + 16 + 7) // 8 * 8          # worst case 8 bits per bin + stop bytes
-        self.out_off = torch.zeros(self.n_slices + 1, dtype=torch.int64, device=dev)
-        self.out_off[1:] = torch.cumsum(cap, 0)
-        self.out = torch.empty(int(self.out_off[-1].item()), dtype=torch.uint8, device=dev)
+        if plan == "device":                                      # avr_plan_chunks_device: the regions and the sum of the bins
+            t, tot = device_plan(n_bins)
+            self.out_off, out_total, self.total_bins = t["out_off"], tot.out_total, tot.total_bins
+        else:
+            cap = (n_bins.to(torch.int64) + 16 + 7) // 8 * 8      # worst case 8 bits per bin + stop bytes
+            self.out_off = torch.zeros(self.n_slices + 1, dtype=torch.int64, device=dev)
+            self.out_off[1:] = torch.cumsum(cap, 0)
+            out_total = int(self.out_off[-1].item())
+        self.out = torch.empty(out_total, dtype=torch.uint8, device=dev)
         self.out_len = torch.zeros(self.n_slices, dtype=torch.int32, device=dev)
         self.status = torch.zeros(self.n_slices, dtype=torch.int32, device=dev)
         self.final_states = (torch.empty(self.n_slices * max(n_states, 1), dtype=torch.uint8, device=dev)
                              if kind in (KIND_CABAC, KIND_CABAC8) else None)
-        self.total_bins = int(n_bins.to(torch.int64).sum().item())
+        if plan != "device":
+            self.total_bins = int(n_bins.to(torch.int64).sum().item())
         # K1 sized by the context count of the previous run of this object (avr_cabac_encode_*_device_hinted): no host round trip
         # in the call; settle() looks at what the device reported once the caller has synchronised
         self.rows_hint, self._hinted_path = 0, None
         self._counts = torch.zeros(2, dtype=torch.int32).pin_memory() if dev.type == "cuda" and kind == KIND_CABAC else None
 
     @classmethod
-    def synth(cls, workload, n_slices, kind=KIND_CABAC, device_index=0, scale_permille=1000, first_slice=0):
-        """Generate BASELINE.json config `workload` on the device (avr_synth_*_device)."""
+    def synth(cls, workload, n_slices, kind=KIND_CABAC, device_index=0, scale_permille=1000, first_slice=0, plan="torch"):
+        """Generate BASELINE.json config `workload` on the device (avr_synth_*_device).  plan="device": the order, the tiles, the
+        regions, the record offsets and the chunk plans of this workload come from the device planner (avr_plan_*_device) instead
+        of torch ops -- the same values."""
         import torch
         L = lib()
         dev = torch.device("cuda", device_index)
@@ -124,7 +241,7 @@ class DeviceWorkload:
             sp = _stream_ptr(torch)
             n_bins = torch.zeros(n_slices, dtype=torch.int32, device=dev)
             _check(L.avr_synth_count_device(device_index, sp, ctypes.byref(cfg), kind, n_slices, n_bins.data_ptr()))
-            order, tile_off = plan_tiles(n_bins)
+            order, tile_off = plan_tiles_device(n_bins) if plan == "device" else plan_tiles(n_bins)
             tiles = torch.empty(int(tile_off[-1].item()) * 16, dtype=torch.uint8, device=dev)
             init_states = (torch.empty(n_slices * cfg.n_states, dtype=torch.uint8, device=dev)
                            if kind == KIND_CABAC else None)
@@ -132,12 +249,12 @@ class DeviceWorkload:
                 device_index, sp, ctypes.byref(cfg), kind, n_slices, order.data_ptr(), tile_off.data_ptr(),
                 tiles.data_ptr(), init_states.data_ptr() if init_states is not None else None))
             torch.cuda.synchronize(dev)
-        w = cls(kind, device_index, n_bins, order, tile_off, tiles, init_states, cfg.n_states if kind == KIND_CABAC else 0)
+        w = cls(kind, device_index, n_bins, order, tile_off, tiles, init_states, cfg.n_states if kind == KIND_CABAC else 0, plan)
         w.cfg = cfg
         return w
 
     @classmethod
-    def from_host(cls, kind, recs_list, init_states_list=None, device_index=0, pad_bytes=None, narrow_tiles=False):
+    def from_host(cls, kind, recs_list, init_states_list=None, device_index=0, pad_bytes=None, narrow_tiles=False, plan="torch"):
         """Upload per-slice uint16 record arrays and pack them into tiles on the device.  KIND_CABAC8: uint8 records, slice-major
         at multiples of 16 bytes; the bytes between a slice's last record and the next slice are taken from pad_bytes (a uint8
         array, repeated over the whole buffer; default zeros) -- the kernels must not code them, whatever they hold.
@@ -145,7 +262,7 @@ class DeviceWorkload:
         import numpy as np
         import torch
         if kind == KIND_CABAC8:
-            return cls._from_host8(recs_list, init_states_list, device_index, pad_bytes, narrow_tiles)
+            return cls._from_host8(recs_list, init_states_list, device_index, pad_bytes, narrow_tiles, plan)
         if narrow_tiles:
             raise AvrError("narrow_tiles: one-byte tiles hold KIND_CABAC8 records only")
         L = lib()
@@ -163,7 +280,7 @@ class DeviceWorkload:
             d_flat = torch.from_numpy(flat.view(np.int16)).to(dev)
             d_off = torch.from_numpy(rec_off).to(dev)
             n_bins = torch.from_numpy(nb).to(dev)
-            order, tile_off = plan_tiles(n_bins)
+            order, tile_off = plan_tiles_device(n_bins) if plan == "device" else plan_tiles(n_bins)
             tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
             pack_status = torch.zeros(n, dtype=torch.int32, device=dev)
             _check(L.avr_pack_tiles_device(device_index, _stream_ptr(torch), kind, n_states, d_flat.data_ptr(),
@@ -174,7 +291,7 @@ class DeviceWorkload:
                 init = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.uint8) for s in init_states_list])
                                         if n_states else np.zeros(1, np.uint8)).to(dev)
             torch.cuda.synchronize(dev)
-        w = cls(kind, device_index, n_bins, order, tile_off, tiles, init, n_states)
+        w = cls(kind, device_index, n_bins, order, tile_off, tiles, init, n_states, plan)
         w.rec_flat, w.rec_off = d_flat, d_off
         w.status.copy_(pack_status)
         return w
@@ -200,14 +317,14 @@ class DeviceWorkload:
                                         torch.from_numpy(nb).to(dev), group_first, est_in, device_index)
 
     @classmethod
-    def from_device_keys(cls, key_flat, rec_off, n_bins, group_first, est_in=None, device_index=0):
+    def from_device_keys(cls, key_flat, rec_off, n_bins, group_first, est_in=None, device_index=0, plan="torch"):
         """The same from slice-major key records already on the device (a synthetic K1 record is a key record)."""
         import numpy as np
         import torch
         dev = n_bins.device
-        order, tile_off = plan_tiles(n_bins)
+        order, tile_off = plan_tiles_device(n_bins) if plan == "device" else plan_tiles(n_bins)
         tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
-        w = cls(KIND_RANGE_KEYS, device_index, n_bins, order, tile_off, tiles, None, 0)
+        w = cls(KIND_RANGE_KEYS, device_index, n_bins, order, tile_off, tiles, None, 0, plan)
         w.key_flat, w.rec_off = key_flat, rec_off
         w.group_first = torch.from_numpy(np.asarray(group_first, dtype=np.int32)).to(dev)
         w.n_groups = w.group_first.numel() - 1
@@ -263,7 +380,7 @@ class DeviceWorkload:
         import torch
         self.status.zero_()
         recs = self.resolve_keys()
-        w = DeviceWorkload(KIND_RANGE, self.device_index, self.n_bins, self.order, self.tile_off, self.tiles, None, 0)
+        w = DeviceWorkload(KIND_RANGE, self.device_index, self.n_bins, self.order, self.tile_off, self.tiles, None, 0, self.plan_mode)
         w.rec_flat, w.rec_off = recs, self.rec_off
         w.status.copy_(self.status)
         _check(lib().avr_pack_tiles_device(self.device_index, _stream_ptr(torch), KIND_RANGE, 0, recs.data_ptr(), self.rec_off.data_ptr(),
@@ -272,7 +389,7 @@ class DeviceWorkload:
         return w
 
     @classmethod
-    def _from_host8(cls, recs_list, init_states_list, device_index, pad_bytes, narrow_tiles=False):
+    def _from_host8(cls, recs_list, init_states_list, device_index, pad_bytes, narrow_tiles=False, plan="torch"):
         import numpy as np
         import torch
         dev = torch.device("cuda", device_index)
@@ -289,12 +406,12 @@ class DeviceWorkload:
             init = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.uint8) for s in init_states_list])
                                     if n_states else np.zeros(1, np.uint8)).to(dev)
             w = cls._pack8(device_index, torch.from_numpy(flat).to(dev), torch.from_numpy(rec_off).to(dev),
-                           torch.from_numpy(nb).to(dev), init, n_states, narrow_tiles)
+                           torch.from_numpy(nb).to(dev), init, n_states, narrow_tiles, plan)
             torch.cuda.synchronize(dev)
         return w
 
     @classmethod
-    def _pack8(cls, device_index, rec8_flat, rec8_off, n_bins, init_states, n_states, narrow_tiles=False):
+    def _pack8(cls, device_index, rec8_flat, rec8_off, n_bins, init_states, n_states, narrow_tiles=False, plan="torch"):
         """A KIND_CABAC8 workload from one-byte slice-major records on the device: two-byte tiles by avr_pack_tiles8_device, or
         one-byte tiles by avr_pack_tiles8_narrow_device (narrow_tiles)."""
         import torch
@@ -302,13 +419,13 @@ class DeviceWorkload:
             raise AvrError(f"n_states {n_states} > {MAX_STATES8}: one-byte records name at most {MAX_STATES8} contexts")
         dev = n_bins.device
         n = n_bins.numel()
-        order, tile_off = plan_tiles(n_bins, 16 if narrow_tiles else 8)
+        order, tile_off = (plan_tiles_device if plan == "device" else plan_tiles)(n_bins, 16 if narrow_tiles else 8)
         tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
         pack_status = torch.zeros(n, dtype=torch.int32, device=dev)
         pack = lib().avr_pack_tiles8_narrow_device if narrow_tiles else lib().avr_pack_tiles8_device
         _check(pack(device_index, _stream_ptr(torch), n_states, rec8_flat.data_ptr(), rec8_off.data_ptr(),
                     n_bins.data_ptr(), order.data_ptr(), n, tile_off.data_ptr(), tiles.data_ptr(), pack_status.data_ptr()))
-        w = cls(KIND_CABAC8, device_index, n_bins, order, tile_off, tiles, init_states, n_states)
+        w = cls(KIND_CABAC8, device_index, n_bins, order, tile_off, tiles, init_states, n_states, plan)
         w.rec8_flat, w.rec8_off, w.narrow_tiles = rec8_flat, rec8_off, bool(narrow_tiles)
         w.status.copy_(pack_status)
         return w
@@ -326,7 +443,10 @@ class DeviceWorkload:
         with torch.cuda.device(dev):
             nb = self.n_bins.to(torch.int64)
             pad16 = (nb + 15) // 16 * 16
-            off8 = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(pad16, 0)])
+            if self.plan_mode == "device":                       # the one-byte records' offsets: rec_round 16
+                off8 = device_plan(self.n_bins, 0, 16)[0]["rec_off"]
+            else:
+                off8 = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(pad16, 0)])
             total = int(off8[-1])
             slice_of = torch.repeat_interleave(torch.arange(self.n_slices, device=dev), pad16)
             src = torch.arange(total, device=dev) - off8[:-1][slice_of] + rec_off[:-1][slice_of]   # (< rec_off[-1] + 8: in the copy)
@@ -338,7 +458,7 @@ class DeviceWorkload:
             flat8 = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
             flat8[:total] = (((sel8 << 1) | (r & 1)) & 0xff).to(torch.uint8)
             del r, sel, sel8
-            w = DeviceWorkload._pack8(self.device_index, flat8, off8, self.n_bins, self.init_states, self.n_states, narrow_tiles)
+            w = DeviceWorkload._pack8(self.device_index, flat8, off8, self.n_bins, self.init_states, self.n_states, narrow_tiles, self.plan_mode)
             torch.cuda.synchronize(dev)
         return w
 
@@ -496,7 +616,10 @@ class DeviceWorkload:
         if getattr(self, "rec_flat", None) is None:
             dev = self.n_bins.device
             nb = self.n_bins.to(torch.int64)
-            self.rec_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum((nb + 7) // 8 * 8, 0)])
+            if self.plan_mode == "device":
+                self.rec_off = device_plan(self.n_bins, 0, 8)[0]["rec_off"]
+            else:
+                self.rec_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum((nb + 7) // 8 * 8, 0)])
             self.rec_flat = torch.empty(int(self.rec_off[-1]) + 8, dtype=torch.int16, device=dev)
             _check(lib().avr_synth_generate_slices_device(
                 self.device_index, _stream_ptr(torch), ctypes.byref(self.cfg), self.kind, self.n_slices,
@@ -516,7 +639,10 @@ class DeviceWorkload:
         """Plan arrays and workspace of the intra-slice parallel path for slices [a, b), numbered from 0."""
         import torch
         from . import ChunkPlan
-        t, totals = chunk_plan_arrays(self.n_bins[a:b])
+        if self.plan_mode == "device":
+            t, totals = chunk_plan_arrays_device(self.n_bins[a:b], self.total_bins)
+        else:
+            t, totals = chunk_plan_arrays(self.n_bins[a:b])
         plan = ChunkPlan(t["res_off"].data_ptr(), t["chunk_base"].data_ptr(), t["chunk_slice"].data_ptr(),
                          t["blk_base"].data_ptr(), t["blk_slice"].data_ptr(), t["dig_off"].data_ptr(), *totals)
         p = dict(tensors=t, plan=plan, first=a, n=b - a)
@@ -534,7 +660,10 @@ class DeviceWorkload:
         one, 0.70 in two)."""
         import torch
         from . import MAX_PARTS
-        chunk_base = chunk_plan_arrays(self.n_bins)[0]["chunk_base"]
+        if self.plan_mode == "device":
+            chunk_base = device_plan(self.n_bins, 1, None, self.total_bins)[0]["chunk_base"]
+        else:
+            chunk_base = chunk_plan_arrays(self.n_bins)[0]["chunk_base"]
         total = int(chunk_base[-1])
         if n_parts == 0:
             waves = (total + 63) // 64
@@ -782,3 +911,11 @@ class DeviceWorkload:
         lens, st = self.out_len.cpu().numpy(), self.status.cpu().numpy()
         return [out[off[i]:off[i] + min(int(lens[i]), int(off[i + 1] - off[i]))].tobytes()
                 for i in range(self.n_slices)], st.tolist()
+
+    def results_dense(self):
+        """The coded bytes compacted on the device (avr_compact_device behind the encode on torch's current stream):
+        (dense uint8 tensor, dense_off int64[n + 1]) on the device -- slice i's bytes are dense[dense_off[i]:dense_off[i + 1]], the
+        concatenation of what results() returns.  Synchronises once, to size the view by dense_off[-1]."""
+        import torch
+        dense, dense_off = compact_device(self.out, self.out_off, self.out_len)
+        return dense[:int(dense_off[-1].item())], dense_off

@@ -762,6 +762,84 @@ int avr_range_encode_slices_device(int device, void *stream,
                                    uint8_t *out, const uint64_t *out_off,
                                    uint32_t *out_len, int32_t *status);
 
+/* ------------------------------------------------------------------ the plan, and the way back, on the device
+ * Every device-resident call above takes a plan: out_off and the arrays of an avr_chunk_plan for the intra-slice parallel paths, the
+ * estimator resolver and checker; `order` and tile_off for the packers and the one-lane-per-slice coders.  A caller whose lengths
+ * (n_bins) lie in HBM makes them here, from the rules the batch API applies on the host (avrecode-ms_amd/csrc/avr_plan.h; the kernels
+ * in avr_plan_dev.hip call the same per-slice functions), and gets its coded bytes back dense without the lengths leaving the device.
+ * All three device calls enqueue on `stream` and return: they never wait or allocate, and write nothing outside
+ * [workspace, workspace + workspace_bytes), `totals` and the extents given below (MEMORY and STREAMS above hold for them as they stand).
+ *   workspace   avr_plan_workspace_bytes(n_slices) bytes of device memory, 256-byte aligned: one quote that covers each of the three
+ *               calls (about 16 bytes a slice and a megabyte), arbitrary on entry, free again once the call's work has run
+ *   totals      DEVICE or PINNED HOST memory, 8-byte aligned, valid once the caller has synchronised `stream` (the scheme of `counts`
+ *               of the hinted calls).  A plan call fills only its own fields: avr_plan_chunks_device all but tile_chunks,
+ *               avr_plan_tiles_device tile_chunks alone -- both may be handed the same struct.
+ * The sequence of a device-resident caller: avr_plan_bounds sizes chunk_slice / blk_slice from an upper bound on the
+ * bins that the caller, who allocated the records, knows; the plan calls; ONE synchronisation; avr_chunk_plan_from makes the struct the
+ * existing calls take and says whether the bound held; the *_workspace_bytes quotes follow from it.
+ *
+ * avr_plan_bounds (host): cap_chunks = max_total_bins / AVR_CHUNK_BINS + n_slices, cap_blocks = max_total_bins / AVR_SORT_BLOCK_BINS +
+ * n_slices -- a slice has at most n_bins / 1024 + 1 chunks, an empty one has one; no list of n_slices lengths with that sum has more.
+ *
+ * avr_plan_chunks_device: element for element what the host plan holds for the same lengths.  `level` says which arrays are written
+ * (each level those of the levels before it); the others, and their caps, are ignored:
+ *   AVR_PLAN_SERIAL   out_off[n + 1]: slice i may write roundup8(n_bins[i] + 16) bytes; and rec_off[n + 1] unless NULL: the slice-major
+ *                     record offsets, slice i taking roundup(n_bins[i], rec_round) -- rec_round 8: two-byte records, offsets in
+ *                     records; 16: one-byte records, offsets in bytes
+ *   AVR_PLAN_CHUNKS   chunk_base[n + 1], chunk_slice[total_chunks]                  (K2p, the estimator resolver and checker)
+ *   AVR_PLAN_CODES    dig_off[n + 1]                                                (K1p from resolved codes)
+ *   AVR_PLAN_K1P      res_off[n + 1], blk_base[n + 1], blk_slice[total_blocks]      (the whole of K1p)
+ * chunk_base and blk_base are 32 bits wide as in avr_chunk_plan; the totals are 64.  chunk_slice[k] is never written for k >= cap_chunks,
+ * nor blk_slice[k] for k >= cap_blocks, whatever n_bins holds: a bound that did not hold costs the plan (avr_chunk_plan_from refuses
+ * it), not memory.  A total of a level above `level` is 0, rec_total is 0 without rec_off.
+ *
+ * avr_chunk_plan_from (host, after the synchronisation): AVR_ERR_CAPACITY when total_chunks > cap_chunks or total_blocks > cap_blocks,
+ * or when either is 2^32 or more (the 32-bit arrays have wrapped); else *plan points at `arrays` with the totals filled in.
+ *
+ * avr_plan_tiles_device: order[n] = the slices by n_bins descending over the full 32-bit range, equal lengths in the caller's order
+ * (a stable sort); tile_off[n_tiles + 1], n_tiles = ceil(n / 64): tile t holds 64 * ceil(n_bins[order[64 t]] / records_per_chunk)
+ * 16-byte chunks (8: two-byte records; 16: one-byte tiles); totals->tile_chunks = tile_off[n_tiles], the tile buffer's size in chunks.
+ *
+ * avr_compact_device: dense_off[n + 1] = the exclusive prefix sum of min(out_len[i], out_off[i + 1] - out_off[i]) with the total
+ * appended -- what avr_batch_wait works out on the host -- and slice i's bytes copied to dense + dense_off[i], in 8-byte words over an
+ * aligned body, if they end at or before dense_capacity.  No byte at or past dense_capacity is written; dense_off is complete either
+ * way, so an overflow shows as dense_off[n] > dense_capacity (that slice and all later ones were not copied).  out_off: multiples of 8
+ * as everywhere, gaps of any size; all offsets 64 bits wide.  Run it behind the encode on the same stream.
+ *
+ * Refused before anything touches a device (AVR_ERR_INVALID): a null array that the level needs, or a null n_bins / order / tile_off /
+ * out / out_off / out_len / dense / dense_off, with n_slices > 0; null arrays, totals or (with a quote above 0) workspace; a level
+ * outside 0..3; rec_round or records_per_chunk neither 8 nor 16; an array not aligned to its element, a workspace not 256-byte aligned;
+ * a workspace below the quote; n_slices >= 2^31.  n_slices == 0 writes the single zero of each n + 1 array and zero totals. */
+/* AVR_NOWAIT marks a call that enqueues on `stream` and returns whatever its arguments: no wait, no allocation, no stream of its own.
+ * (It also sets the three calls apart for tests/device_api_refusals.py, whose table is made from the parameter names of the unmarked
+ * *_device declarations and cannot describe a struct of arrays with caps; tests/test_plan_bounds.py holds these three to their refusals.) */
+#define AVR_NOWAIT
+#define AVR_PLAN_SERIAL 0   /* out_off (+ rec_off)                                  */
+#define AVR_PLAN_CHUNKS 1   /* + chunk_base, chunk_slice      (K2p, resolver)       */
+#define AVR_PLAN_CODES  2   /* + dig_off                      (K1p from codes)      */
+#define AVR_PLAN_K1P    3   /* + res_off, blk_base, blk_slice                       */
+
+typedef struct {            /* DEVICE arrays the caller allocated; those a level does not write are ignored */
+    uint64_t *out_off;      /* n + 1 */
+    uint64_t *rec_off;      /* n + 1, or NULL: slice-major record offsets; slice i takes roundup(n_bins[i], rec_round)  */
+    uint32_t  rec_round;    /* 8 (two-byte records, offsets in records) or 16 (one-byte, offsets in bytes) */
+    uint32_t *chunk_base;  uint32_t *chunk_slice;  uint64_t cap_chunks;
+    uint64_t *dig_off;  uint64_t *res_off;
+    uint32_t *blk_base;    uint32_t *blk_slice;    uint64_t cap_blocks;
+} avr_plan_arrays;
+
+typedef struct { uint64_t total_bins, out_total, rec_total, res_total, dig_total, total_chunks, total_blocks, tile_chunks; } avr_plan_totals;
+
+void   avr_plan_bounds(size_t n_slices, uint64_t max_total_bins, uint64_t *cap_chunks, uint64_t *cap_blocks);   /* host */
+size_t avr_plan_workspace_bytes(size_t n_slices);                                                               /* host, covers all three calls */
+int avr_plan_chunks_device(int device, void *stream, const uint32_t *n_bins, size_t n_slices, int level,
+                           const avr_plan_arrays *arrays, void *workspace, size_t workspace_bytes, avr_plan_totals *totals) AVR_NOWAIT;
+int avr_plan_tiles_device(int device, void *stream, const uint32_t *n_bins, size_t n_slices, uint32_t records_per_chunk /* 8 | 16 */,
+                          uint32_t *order, uint64_t *tile_off, void *workspace, size_t workspace_bytes, avr_plan_totals *totals) AVR_NOWAIT;
+int avr_chunk_plan_from(const avr_plan_arrays *arrays, const avr_plan_totals *totals, avr_chunk_plan *plan);     /* host, after a sync */
+int avr_compact_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, size_t n_slices,
+                       uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off /* n + 1 */, void *workspace, size_t workspace_bytes) AVR_NOWAIT;
+
 /* ------------------------------------------------------------------ dense context ids
  * A context is identified by the offset of its state byte in libavcodec's cabac_state[1024]
  * (recode.cpp:325 keys the model on the address), but a stream uses far fewer of them, and K1
