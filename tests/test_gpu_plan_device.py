@@ -52,18 +52,41 @@ def expected_plan(torch, lengths, rec_round):
     from avrecode_ms_amd.device import chunk_plan_arrays
     t, totals = chunk_plan_arrays(torch.from_numpy(lengths))
     want = {k: v.numpy() for k, v in t.items()}
-    want["out_off"] = prefix((lengths + 16 + 7) // 8 * 8)
-    want["rec_off"] = prefix((lengths + rec_round - 1) // rec_round * rec_round)
+    want["out_off"], want["rec_off"] = serial_offsets(lengths, rec_round)
     return want, totals
+
+
+def serial_offsets(lengths, rec_round):
+    """out_off and rec_off (AVR_PLAN_SERIAL) by the expressions DeviceWorkload uses for them."""
+    return prefix((lengths + 16 + 7) // 8 * 8), prefix((lengths + rec_round - 1) // rec_round * rec_round)
 
 
 LEVEL_ARRAYS = [("out_off", "rec_off"), ("chunk_base", "chunk_slice"), ("dig_off",), ("res_off", "blk_base", "blk_slice")]
 WIDTH = dict(out_off=8, rec_off=8, dig_off=8, res_off=8, chunk_base=4, chunk_slice=4, blk_base=4, blk_slice=4)
 
 
-def run_chunks(avr, torch, n_bins, total_bins, level, rec_round, poison, caps=None, with_rec=True):
+def _bytes_of(torch, x):
+    """The uint8 tensor of a caller's buffer: a guarded.Guarded's view, or a tensor as it is (pinned host memory, say)."""
+    return x if torch.is_tensor(x) else x.view
+
+
+def _own_stream(torch, stream):
+    """The stream a call runs on: the caller's, or one of its own behind whatever the current one holds (the poison)."""
+    if stream is None:
+        stream = torch.cuda.Stream()
+        stream.wait_stream(torch.cuda.current_stream())
+    return stream
+
+
+def run_chunks(avr, torch, n_bins, total_bins, level, rec_round, poison, caps=None, with_rec=True, ws=None, totals=None, stream=None,
+               defer=False):
     """One avr_plan_chunks_device call into guarded buffers of the exact sizes, on a stream of its own.  Returns ({array: numpy},
-    totals as 8 uint64, the buffers, the PlanArrays)."""
+    totals as 8 uint64, the buffers, the PlanArrays).
+    ws, totals: the caller's own (a guarded.Guarded; totals may be any 64-byte uint8 tensor), neither poisoned nor checked here.
+    stream: the caller's; the poison is then filled in on the current stream, which the caller orders.  defer: enqueue only, nothing
+    is synchronised: returns (collect, seconds the C call took on the host); collect() gives the tuple above once the caller has
+    synchronised the stream."""
+    import time
     L = avr.lib()
     n = n_bins.numel()
     if caps is None:
@@ -73,23 +96,31 @@ def run_chunks(avr, torch, n_bins, total_bins, level, rec_round, poison, caps=No
     size = dict(out_off=n + 1, rec_off=n + 1, dig_off=n + 1, res_off=n + 1, chunk_base=n + 1, blk_base=n + 1, chunk_slice=caps[0], blk_slice=caps[1])
     bufs = guarded.Buffers()
     g = {name: bufs.add(name, size[name] * WIDTH[name], "cuda") for name in size}
-    ws = bufs.add("ws", L.avr_plan_workspace_bytes(n), "cuda")
-    totals = bufs.add("totals", 64, "cuda")
+    if ws is None:
+        ws = bufs.add("ws", L.avr_plan_workspace_bytes(n), "cuda")
+    if totals is None:
+        totals = bufs.add("totals", 64, "cuda")
     for x in bufs.all.values():
         x.view.fill_(poison)
     ptr = lambda name: g[name].view.data_ptr()
     arrays = avr.PlanArrays(ptr("out_off"), ptr("rec_off") if with_rec else None, rec_round, ptr("chunk_base"), ptr("chunk_slice"), caps[0],
                             ptr("dig_off"), ptr("res_off"), ptr("blk_base"), ptr("blk_slice"), caps[1])
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())              # (the poison was filled in on the current one)
+    stream = _own_stream(torch, stream)                          # (the poison was filled in on the current one)
     with torch.cuda.stream(stream):
+        t0 = time.perf_counter()
         rc = L.avr_plan_chunks_device(0, ctypes.c_void_p(stream.cuda_stream), n_bins.data_ptr(), n, level, ctypes.byref(arrays),
-                                      ws.view.data_ptr(), ws.n, totals.view.data_ptr())
+                                      ws.view.data_ptr(), ws.n, _bytes_of(torch, totals).data_ptr())
+        took = time.perf_counter() - t0
     assert rc == OK, L.avr_last_error()
+
+    def collect():
+        bufs.check()
+        got = {name: g[name].view.cpu().numpy().view(np.int64 if WIDTH[name] == 8 else np.int32) for name in size}
+        return got, _bytes_of(torch, totals).cpu().numpy().view(np.uint64), bufs, arrays
+    if defer:
+        return collect, took
     stream.synchronize()
-    bufs.check()
-    got = {name: g[name].view.cpu().numpy().view(np.int64 if WIDTH[name] == 8 else np.int32) for name in size}
-    return got, totals.view.cpu().numpy().view(np.uint64), bufs, arrays
+    return collect()
 
 
 @pytest.mark.parametrize("name", sorted(LENGTHS))
@@ -155,25 +186,36 @@ def test_a_cap_one_too_small_costs_the_plan_not_memory(avr, short):
         assert avr.lib().avr_chunk_plan_from(ctypes.byref(arrays), ctypes.byref(t), ctypes.byref(avr.ChunkPlan())) == ERR_CAPACITY
 
 
-def run_tiles(avr, torch, n_bins, per_chunk, poison):
+def run_tiles(avr, torch, n_bins, per_chunk, poison, ws=None, totals=None, stream=None, defer=False):
+    """One avr_plan_tiles_device call: (order, tile_off, totals as 8 uint64).  ws, totals, stream, defer: as run_chunks takes them."""
+    import time
     L = avr.lib()
     n = n_bins.numel()
     bufs = guarded.Buffers()
     order = bufs.add("order", 4 * n, "cuda")
     tile_off = bufs.add("tile_off", 8 * ((n + 63) // 64 + 1), "cuda")
-    ws = bufs.add("ws", L.avr_plan_workspace_bytes(n), "cuda")
-    totals = bufs.add("totals", 64, "cuda")
+    if ws is None:
+        ws = bufs.add("ws", L.avr_plan_workspace_bytes(n), "cuda")
+    if totals is None:
+        totals = bufs.add("totals", 64, "cuda")
     for x in bufs.all.values():
         x.view.fill_(poison)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())              # (the poison was filled in on the current one)
+    stream = _own_stream(torch, stream)                          # (the poison was filled in on the current one)
     with torch.cuda.stream(stream):
+        t0 = time.perf_counter()
         rc = L.avr_plan_tiles_device(0, ctypes.c_void_p(stream.cuda_stream), n_bins.data_ptr(), n, per_chunk, order.view.data_ptr(),
-                                     tile_off.view.data_ptr(), ws.view.data_ptr(), ws.n, totals.view.data_ptr())
+                                     tile_off.view.data_ptr(), ws.view.data_ptr(), ws.n, _bytes_of(torch, totals).data_ptr())
+        took = time.perf_counter() - t0
     assert rc == OK, L.avr_last_error()
+
+    def collect():
+        bufs.check()
+        return (order.view.cpu().numpy().view(np.int32), tile_off.view.cpu().numpy().view(np.int64),
+                _bytes_of(torch, totals).cpu().numpy().view(np.uint64))
+    if defer:
+        return collect, took
     stream.synchronize()
-    bufs.check()
-    return order.view.cpu().numpy().view(np.int32), tile_off.view.cpu().numpy().view(np.int64), totals.view.cpu().numpy().view(np.uint64)
+    return collect()
 
 
 @pytest.mark.parametrize("name", sorted(TILE_LENGTHS))
@@ -193,25 +235,39 @@ def test_tile_plans(avr, name):
 
 # ------------------------------------------------------------------ compaction
 
-def run_compact(avr, torch, out, out_off, out_len, capacity, poison):
+def run_compact(avr, torch, out, out_off, out_len, capacity, poison, ws=None, stream=None, defer=False, dense=None):
+    """One avr_compact_device call: (dense, dense_off).  out_off, out_len: numpy, or device tensors as the C ABI takes them (int64,
+    and uint32 as an int32 tensor's bits).  dense: the caller's own uint8 view of `capacity` bytes, of any alignment, inside a buffer
+    the caller guards.  ws, stream, defer: as run_chunks takes them."""
+    import time
     L = avr.lib()
     n = len(out_len)
     bufs = guarded.Buffers()
-    dense = bufs.add("dense", capacity, "cuda")
+    if dense is None:
+        dense = bufs.add("dense", capacity, "cuda").view
+    assert dense.numel() == capacity
     dense_off = bufs.add("dense_off", 8 * (n + 1), "cuda")
-    ws = bufs.add("ws", L.avr_plan_workspace_bytes(n), "cuda")
+    if ws is None:
+        ws = bufs.add("ws", L.avr_plan_workspace_bytes(n), "cuda")
     for x in bufs.all.values():
         x.view.fill_(poison)
-    d_off, d_len = torch.from_numpy(out_off).cuda(), torch.from_numpy(out_len.astype(np.uint32).view(np.int32)).cuda()
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    d_off = out_off if torch.is_tensor(out_off) else torch.from_numpy(out_off).cuda()
+    d_len = out_len if torch.is_tensor(out_len) else torch.from_numpy(out_len.astype(np.uint32).view(np.int32)).cuda()
+    stream = _own_stream(torch, stream)
     with torch.cuda.stream(stream):
+        t0 = time.perf_counter()
         rc = L.avr_compact_device(0, ctypes.c_void_p(stream.cuda_stream), out.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n,
-                                  dense.view.data_ptr(), capacity, dense_off.view.data_ptr(), ws.view.data_ptr(), ws.n)
+                                  dense.data_ptr(), capacity, dense_off.view.data_ptr(), ws.view.data_ptr(), ws.n)
+        took = time.perf_counter() - t0
     assert rc == OK, L.avr_last_error()
+
+    def collect():
+        bufs.check()
+        return dense.cpu().numpy(), dense_off.view.cpu().numpy().view(np.int64)
+    if defer:
+        return collect, took
     stream.synchronize()
-    bufs.check()
-    return dense.view.cpu().numpy(), dense_off.view.cpu().numpy().view(np.int64)
+    return collect()
 
 
 def compact_case():
