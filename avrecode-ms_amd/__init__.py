@@ -328,7 +328,7 @@ def library_sha256() -> str:
 def test_hooks(**hooks):
     """FOR tests/ ONLY.  Inside the block, lib() is libavrecode_hip_hooks.so -- the same sources built with
     -DAVR_TEST_HOOKS -- with the named hooks set (csrc/avr_internal.h: k1p_force_retry_every, census_stride,
-    chain_lanes, k1_path [1 serial, 2 chunked], no_dense, no_hint, k2p_seg_len, local_waves, k2p_wave); all of them keep the bytes exact and
+    k1_path [1 serial, 2 chunked], no_dense, no_hint, k2p_seg_len, local_waves, k2p_wave); all of them keep the bytes exact and
     only force paths that real batches take rarely -- except est_flip / est_flip_bin, which add one to neg of one resolved record of a batch of key records with set_verify on
     (between the resolver and the encode: only the estimator checker can see it), verify_flip, which corrupts one slice's first byte on the device in front of the verifier (a batch with
     set_verify or set_verify_k1 on) so that a test sees a failure travel through the batch API, restore_flip, the same in front of the restore check (a batch with expectations), and k1p_keep_retry, which leaves the slices that K1p declines or its phase D hands over uncoded (status

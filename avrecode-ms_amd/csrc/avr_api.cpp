@@ -329,9 +329,9 @@ extern "C" {
 int avr_test_hook_set(const char *name, uint32_t value) {
     static const struct { const char *name; uint32_t avr::TestHooks::*field; } kHooks[] = {
 #define AVR_HOOK(f) {#f, &avr::TestHooks::f}
-        AVR_HOOK(k1p_force_retry_every), AVR_HOOK(census_stride), AVR_HOOK(chain_lanes),
+        AVR_HOOK(k1p_force_retry_every), AVR_HOOK(census_stride),
         AVR_HOOK(k1_path), AVR_HOOK(no_dense), AVR_HOOK(no_hint), AVR_HOOK(k2p_seg_len), AVR_HOOK(local_waves), AVR_HOOK(k2p_wave),
-        AVR_HOOK(k1p_keep_retry), AVR_HOOK(k1_waves), AVR_HOOK(chain_nsegs), AVR_HOOK(chain_whole),
+        AVR_HOOK(k1p_keep_retry), AVR_HOOK(chain_nsegs), AVR_HOOK(chain_whole),
         AVR_HOOK(chain_segments), AVR_HOOK(chain_force_redo), AVR_HOOK(verify_flip), AVR_HOOK(est_flip), AVR_HOOK(est_flip_bin),
         AVR_HOOK(restore_flip),
 #undef AVR_HOOK
@@ -743,7 +743,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
         else AVR_HIP(avr::launch_pack_tiles(s, b->kind, uint32_t(ns), recs, b->d_tile_off.p, b->d_tiles.p, b->output.status));
         AVR_HIP(hipEventRecord(b->ev[2], s));
         if (b->recs8) AVR_HIP(avr::launch_cabac8_encode(s, b->read, b->states, b->output));      // no census, no guess, nothing waits
-        else if (cabac) AVR_HIP(avr::launch_cabac_encode(s, b->read, b->states, b->output, AVR_SLICE_OK, true, &hint));
+        else if (cabac) AVR_HIP(avr::launch_cabac_encode(s, b->read, b->states, b->output, &hint));
         else AVR_HIP(avr::launch_range_encode(s, b->read, b->output));
     }
     return enqueue_checks(b, n32);
@@ -827,7 +827,7 @@ int avr_batch_wait(avr_batch *b) {
     if ((rc = b->d_dense.reserve(dense_total + 1)) || (rc = b->h_out.reserve(dense_total + 1))) return rc;
     b->plan_used = 0;                                            // the run's plan arrays are consumed: the arena is free again
     AVR_STAGE(b->d_dense_off.p, b->dense_off.data(), n + 1);
-    AVR_HIP(avr::launch_compact(s, b->output, b->d_dense_off.p, n32, b->d_dense.p));
+    AVR_HIP(avr::launch_compact(s, b->output, b->d_dense_off.p, n32, b->d_dense.p, dense_total));
     if (dense_total) AVR_HIP(hipMemcpyAsync(b->h_out.p, b->d_dense.p, dense_total, hipMemcpyDeviceToHost, s));
     AVR_HIP(hipEventRecord(b->ev[4], s));
     AVR_HIP(hipStreamSynchronize(s));
@@ -1193,7 +1193,7 @@ static int cabac_encode_device(int device, void *stream, const Slices &in, size_
     }
     counts[0] = counts[1] = 0;
     const avr::DenseHint hint{std::min<uint32_t>(rows_hint, uint32_t(n_states)), counts, nullptr};
-    AVR_HIP(avr::launch_cabac_encode(hip(stream), in, st, o, AVR_SLICE_OK, true, &hint));
+    AVR_HIP(avr::launch_cabac_encode(hip(stream), in, st, o, &hint));
     return AVR_OK;
 }
 int avr_cabac_encode_tiles_device(int device, void *stream, const void *tiles, const uint64_t *tile_off, const uint32_t *n_bins,

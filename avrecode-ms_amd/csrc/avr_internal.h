@@ -15,8 +15,9 @@
 //   K1: selector 1026, bin 0 -> r1 = 0, symbol 0: low, range and states unchanged
 //   K2: pos = neg = 0 (never valid in a real record) -> skipped
 #define AVR_NOP_CABAC2  (AVR_NOP_CABAC | (AVR_NOP_CABAC << 16))
-// transient per-slice status: K1p declined the slice, k_cabac_encode codes it in the same call
-// (never leaves a call: k_cabac_encode / k_cabac_encode_codes replace it with the slice's real status)
+// transient per-slice status, the hand-over to a serial coder in the same call: K1p's phase D declined the slice (k_cabac_encode_codes
+// codes it from the resolved codes the call has made), or the renumbered launch of k_cabac_encode met a context its census missed (a
+// second launch without renumbering codes it).  Never leaves a call: the coder that takes the slice writes its real status.
 #define AVR_SLICE_RETRY_SERIAL 100
 // transient, inside the intra-slice parallel path only: the slice has a bin in a context the sampled census of the
 // batch missed (it takes the second, fully counted pass); the slice is finished and must be left alone by that pass
@@ -39,7 +40,6 @@ const Env &env();
 struct TestHooks {
     uint32_t k1p_force_retry_every;  // k_k1p_d hands every n-th slice to the serial kernel (0 = off)
     uint32_t census_stride;          // sampling stride of both census kernels (0 = the built-in 16)
-    uint32_t chain_lanes;            // lanes per wave of k_k1p_ctxchain (0 = by batch shape)
     uint32_t k1_path, no_dense, no_hint;   // the environment switches above, settable per test (non-zero wins over env())
     uint32_t chain_segments;         // K1p: the context chains in segments whatever the batch's size
     uint32_t chain_whole;            // K1p: every context chain start to end (k_k1p_ctxchain alone), no segments
@@ -47,7 +47,6 @@ struct TestHooks {
     uint32_t k2p_seg_len;            // chunks per segment of K2p's overlapped passes (0 = by batch shape): short slices through many segments
     uint32_t local_waves;            // K1p: waves to a workgroup of k_k1p_local (0 = as many waves to a CU as its LDS takes)
     uint32_t chain_nsegs;            // K1p: segments the context chains are cut in (0 = as many as keep the launch in one round of workgroups)
-    uint32_t k1_waves;               // one-lane-per-slice K1: waves to a workgroup (0 = the built-in count)
     uint32_t k2p_wave;               // K2p pass 1: 1 = a wave per slice, 2 = a lane per slice, 3 = a lane per slice and a wave each for the longest (0 = by slice count)
     uint32_t verify_flip;            // batch API with verify on: k > 0 complements bit 7 of byte 0 of slice k - 1's output region between the encode and the verifier
     uint32_t est_flip, est_flip_bin; // batch API with verify on, key records: k > 0 adds one to neg of bin est_flip_bin of slice k - 1's resolved record, between the
@@ -79,6 +78,10 @@ inline bool no_hint() { return test_hooks().no_hint || env().no_hint; }
 //   * sharing: how many calls like this one are in flight on the device at once (the parts of avr_cabac_encode_chunked_device_parts):
 //     the context chains are cut into as many segments as keep ALL of them in one round of workgroups (0 = 1).
 struct DenseHint { uint32_t rows; uint32_t *host_count; uint32_t *host_retry; uint32_t sharing = 0; };
+// The rows to size by, once the census and launch_densemap have left the batch's context count in *n_dense (device) on `s`: the
+// hint's guess, the count copied to *hint->host_count behind what is enqueued (nothing waits) -- or, without a guess, the count itself,
+// read back (the call waits for the stream) and left in *hint->host_count too; either way no more than n_states.
+hipError_t dense_rows(hipStream_t s, const uint32_t *n_dense, uint32_t n_states, const DenseHint *hint, uint32_t *rows);
 
 // Something the library keeps per (device, stream): made on first use, under the pool's mutex, and kept -- work on one stream is
 // ordered, so consecutive calls may share it -- until forget() releases what is kept for a stream that is going away.
@@ -143,8 +146,7 @@ struct Output {
     operator OutputView() const { return {out, out_off, out_len, status}; }
 };
 
-hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st, const Output &o, int32_t want_status = AVR_SLICE_OK,
-                               bool dense = true, const DenseHint *hint = nullptr);
+hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st, const Output &o, const DenseHint *hint = nullptr);
 // used (1024 bits) -> table[caller's context number] = dense id (0xffff: unused), index[dense id] = caller's number, *n_dense
 hipError_t launch_densemap(hipStream_t s, const uint32_t *used, uint16_t *table, uint16_t *index, uint32_t *n_dense);
 hipError_t launch_range_encode(hipStream_t s, const Slices &in, const Output &o);
@@ -178,7 +180,8 @@ hipError_t launch_context_census(hipStream_t s, const uint16_t *recs, uint64_t n
 hipError_t launch_context_remap(hipStream_t s, uint16_t *recs, uint64_t n, const uint16_t *table);
 hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_src, uint8_t *dst, uint32_t n_dst,
                                  const uint16_t *index, uint32_t n_index, uint64_t n_slices, int scatter);
-hipError_t launch_compact(hipStream_t s, const OutputView &o, const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense);
+// every slice's coded bytes to dense + dense_off[i] (avr_plan_dev.hip's wide copy on the caller's own offsets; dense_total = dense_off[n_slices])
+hipError_t launch_compact(hipStream_t s, const OutputView &o, const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense, uint64_t dense_total);
 
 // The intra-slice parallel K1 path (avr_k1p.hip), slice-major records.  Workspace of the three whole-path launchers:
 // k1p_layout(n_slices, n_states, pl).total bytes (avr_layout.h, as every workspace here)

@@ -17,7 +17,9 @@
 //
 // Input is the slice-major record layout (a slice's bins must be consecutive for the chunk lanes).
 // Results are byte-identical to k_cabac_encode (tests/test_gpu_k1p.py); a slice the scheme declines
-// (no coded LPS for 16 chunks) is coded by k_cabac_encode itself.
+// (no coded LPS for 16 chunks, or digit sums phase D does not resolve) is coded by k_cabac_encode_codes from
+// the resolved codes of the same call, which are complete for every slice that reaches phase D: nothing here
+// goes back to the records or to avr_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -1309,7 +1311,7 @@ struct DeviceAdder {
     __device__ void add(uint32_t i, uint32_t v) { atomicAdd(&S[i], v); }
 };
 
-template <bool TILE_CODES>
+// `res`: the codes wave-interleaved (TileCodes), as k_k1p_replay or k_k1p_b1 left them
 __global__ __launch_bounds__(256, 7) void k_k1p_c(Plan p, uint32_t total_chunks, const uint8_t *res,
                                                   const Stretch *st, const Entry *en, const SliceTotals *tot,
                                                   uint32_t *S) {
@@ -1326,8 +1328,7 @@ __global__ __launch_bounds__(256, 7) void k_k1p_c(Plan p, uint32_t total_chunks,
     DeviceAdder add;
     add.S = S + p.dig_off[slice];
     add.ring = ring + (threadIdx.x >> 6) * (kRing * 64) + (threadIdx.x & 63u);
-    if (TILE_CODES) c_stretch_in(TileCodes{res, p.chunk_base[slice]}, o, en[gc], gc - p.chunk_base[slice], codes, add);
-    else c_stretch(res + p.res_off[slice], o, en[gc], gc - p.chunk_base[slice], codes, add);
+    c_stretch_in(TileCodes{res, p.chunk_base[slice]}, o, en[gc], gc - p.chunk_base[slice], codes, add);
 }
 
 // ------------------------------------------------------------------ phase D
@@ -1441,8 +1442,9 @@ __global__ __launch_bounds__(256) void k_k1p_d(Plan p, const SliceTotals *tot, c
 // carry pattern of k_k1p_d, or the test switch), and batches of many short slices, where one lane per
 // slice fills the chip and the per-chunk machinery of K1p would be all overhead.
 // Slice i's codes are at codes + res_off[i] (16-byte aligned, readable up to the next multiple of 16); TILE: in the kernels' own
-// wave-interleaved buffer instead (TileCodes, slice i from global chunk chunk_base[i] on) -- the hand-over of the one-byte K1p call,
-// which has no two-byte records to hand over (launch_k1p8).
+// wave-interleaved buffer instead (TileCodes, slice i from global chunk chunk_base[i] on) -- the hand-over of the whole path, from
+// records of either width (k1p_pass): k_k1p_replay has written every code of every slice that gets as far as phase D, whatever
+// phase D then makes of its digit sums, so the slice is coded from them with no state table and no further read of its records.
 template <bool TILE>
 __global__ __launch_bounds__(64) void k_cabac_encode_codes(const uint8_t *codes_in, const uint64_t *res_off, const uint32_t *chunk_base,
                                                            const uint32_t *n_bins, const uint32_t *order, uint32_t n_slices, uint8_t *out,
@@ -1590,14 +1592,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         hipLaunchKernelGGL(k_k1p_census, dim3((pl->total_blocks + kCensusBlocks - 1) / kCensusBlocks), dim3(256), 0, s, p, pl->total_blocks, status, used, mode.census_stride);
         hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
         if ((e = tn_table(s, &tn)) != hipSuccess) return e;
-        if (hint && hint->rows) {                                    // sized by the caller's guess, checked by the caller afterwards (DenseHint)
-            n_states = hint->rows < ns ? hint->rows : ns;
-            if (hint->host_count && (e = hipMemcpyAsync(hint->host_count, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        } else {
-            if ((e = hipMemcpyAsync(&n_states, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-            if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-            if (hint && hint->host_count) *hint->host_count = n_states;
-        }
+        if ((e = dense_rows(s, n_dense, ns, hint, &n_states)) != hipSuccess) return e;   // a guess is checked by the caller afterwards (DenseHint)
     }
     p.n_states = n_states;
     {
@@ -1647,7 +1642,6 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         // issuing the waves becomes the limit (measured on 512 slices x 86 contexts: 8 lanes 0.77 ms, 16 0.44, 22 .. 64 0.29)
         uint32_t chain_lanes = uint32_t((uint64_t(n_slices) * n_states + 2047) / 2048);
         chain_lanes = chain_lanes < kChainLanes ? kChainLanes : chain_lanes > 64 ? 64 : chain_lanes;
-        if (const uint32_t v = test_hooks().chain_lanes) chain_lanes = v <= 64 ? v : 64;     // tuning switch (test build)
         const bool packed = chain_lanes == 64;                   // lanes to spare: full waves of 64 pairs (see k_k1p_ctxchain)
         const uint32_t groups = packed ? 0u : (n_states + chain_lanes - 1) / chain_lanes;
         const uint32_t whole_waves = packed ? uint32_t((uint64_t(n_slices) * n_states + 63) / 64) : n_slices * groups;
@@ -1691,10 +1685,10 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
 }
 
 // Phases B-D: resolved codes -> bytes.  `w` is a CodeLayout.
-// `have` != nullptr: the stretch summaries (phase B1) have been made already, by k_k1p_replay.
+// `have` != nullptr: the stretch summaries (phase B1) have been made already, by k_k1p_replay, and `res` is wave-interleaved
+// (TileCodes) by contract -- the only form phase C reads; without `have`, `res` is slice-major and B1 makes the tile itself.
 static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, const avr_chunk_plan *pl, uint8_t *w,
-                              const uint8_t *res, uint32_t max_stretch, const Output &o, const Stretch *have = nullptr,
-                              bool tile_codes = false) {
+                              const uint8_t *res, uint32_t max_stretch, const Output &o, const Stretch *have = nullptr) {
     const CodeLayout L = code_layout(n_slices, pl);
     Stretch *st_own = reinterpret_cast<Stretch *>(w + L.stretch);
     const Stretch *st = have ? have : st_own;
@@ -1707,11 +1701,9 @@ static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, c
         uint8_t *tile = w + L.tile;
         hipLaunchKernelGGL(k_k1p_b1, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, o.status, st_own, max_stretch, tile);
         res = tile;
-        tile_codes = true;
     }
     hipLaunchKernelGGL(k_k1p_b2, dim3(n_slices), dim3(256), 0, s, p, o.status, st, en, tot, S);
-    if (tile_codes) hipLaunchKernelGGL(k_k1p_c<true>, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
-    else hipLaunchKernelGGL(k_k1p_c<false>, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
+    hipLaunchKernelGGL(k_k1p_c, dim3(chunk_blocks), dim3(256), 0, s, p, pl->total_chunks, res, st, en, tot, S);
     const uint32_t force_retry_every = test_hooks().k1p_force_retry_every;   // test build only, see k_k1p_d
     hipLaunchKernelGGL(k_k1p_d, dim3(n_slices), dim3(256), 0, s, p, tot, S, o.out, o.out_off, o.out_len, o.status, force_retry_every);
     return hipGetLastError();
@@ -1720,6 +1712,21 @@ static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, c
 hipError_t launch_densemap(hipStream_t s, const uint32_t *used, uint16_t *table, uint16_t *index, uint32_t *n_dense) {
     hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
     return hipGetLastError();
+}
+
+hipError_t dense_rows(hipStream_t s, const uint32_t *n_dense, uint32_t n_states, const DenseHint *hint, uint32_t *rows) {
+    hipError_t e;
+    uint32_t n = 0;
+    if (hint && hint->rows) {                                    // sized by the caller's guess: nothing waits (see DenseHint)
+        n = hint->rows;
+        if (hint->host_count && (e = hipMemcpyAsync(hint->host_count, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    } else {
+        if ((e = hipMemcpyAsync(&n, n_dense, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        if (hint && hint->host_count) *hint->host_count = n;
+    }
+    *rows = n < n_states ? n : n_states;
+    return hipSuccess;
 }
 
 hipError_t launch_cabac_encode_codes(hipStream_t s, const Slices &in, const Output &o, int32_t want_status) {
@@ -1744,22 +1751,17 @@ static K1pJob k1p_job(Records kind, const Slices &in, uint32_t n_states, const a
     return K1pJob{in, make_plan(kind, in, n_states, pl), pl, w + L.codes, w + L.resolve, w + L.code};
 }
 
-// Both stages of a job over the slices whose status is AVR_SLICE_OK; what comes after them is the caller's.
-static hipError_t k1p_stages(hipStream_t s, const K1pJob &j, const States &st, const Output &o, ResolveMode mode) {
+// One pass of the whole path, from records of either width: both stages over the slices whose status is AVR_SLICE_OK, then the
+// slices phase D declined (status AVR_SLICE_RETRY_SERIAL) through the serial coder, from the resolved codes this pass made, where they lie.
+static hipError_t k1p_pass(hipStream_t s, const K1pJob &j, const States &st, const Output &o, ResolveMode mode) {
     const Stretch *stretch = nullptr;
     mode.tile_codes = true;
     hipError_t e = launch_resolve(s, j.p, j.in.n_slices, j.pl, j.resolve_ws, j.codes, st, o.status, kMaxStretch, &stretch, mode);
-    if (e != hipSuccess) return e;
-    return launch_code(s, j.p, j.in.n_slices, j.pl, j.code_ws, j.codes, kMaxStretch, o, stretch, true);
-}
-
-// One pass of the whole path from two-byte records.
-static hipError_t k1p_pass(hipStream_t s, const K1pJob &j, const States &st, const Output &o, const ResolveMode &mode) {
-    const hipError_t e = k1p_stages(s, j, st, o, mode);
+    if (e == hipSuccess) e = launch_code(s, j.p, j.in.n_slices, j.pl, j.code_ws, j.codes, kMaxStretch, o, stretch);
     if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;    // (test hook: the hand-overs stay visible, uncoded)
-    // slices the scheme declined (status AVR_SLICE_RETRY_SERIAL) are coded by the serial kernel, from the same slice-major records
-    return launch_cabac_encode(s, Slices{j.p.recs, j.p.rec_off, j.p.n_bins, nullptr, j.in.n_slices}, States{st.init_states, st.n_states, nullptr}, o,
-                               AVR_SLICE_RETRY_SERIAL);
+    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((j.in.n_slices + 63) / 64), dim3(64), 0, s, j.codes, nullptr, j.pl->chunk_base, j.in.n_bins,
+                       nullptr, j.in.n_slices, o.out, o.out_off, o.out_len, o.status, int32_t(AVR_SLICE_RETRY_SERIAL));
+    return hipGetLastError();
 }
 
 // The second pass: the slices k_k1p_local set aside (a bin in a context the sampled census missed) once more, with every
@@ -1816,16 +1818,10 @@ hipError_t launch_k1p_resolve(hipStream_t s, const Slices &in, const States &st,
 }
 // The one-byte form (AVR_KIND_CABAC8, avr_cabac8_encode_chunked_device): the same phases on p.recs8, without the census, the
 // renumbering, the second pass and the host round trip (the selectors are dense ids below n_states <= AVR_MAX_STATES8 already):
-// everything is enqueued, nothing waits.  The slices phase D hands over are coded by the serial coder from the resolved codes this
-// call made (k_cabac_encode_codes on the wave-interleaved buffer): same bytes as from the records, and no two-byte copy of them.
+// everything is enqueued, nothing waits.
 hipError_t launch_k1p8(hipStream_t s, const Slices &in, const States &st, const avr_chunk_plan *pl, void *workspace, const Output &o) {
     if (in.n_slices == 0) return hipSuccess;
-    const K1pJob j = k1p_job(Records::kOneByte, in, st.n_states, pl, workspace);
-    const hipError_t e = k1p_stages(s, j, st, o, ResolveMode{});
-    if (e != hipSuccess || test_hooks().k1p_keep_retry) return e;
-    hipLaunchKernelGGL(k_cabac_encode_codes<true>, dim3((in.n_slices + 63) / 64), dim3(64), 0, s, j.codes, nullptr, pl->chunk_base, in.n_bins,
-                       nullptr, in.n_slices, o.out, o.out_off, o.out_len, o.status, int32_t(AVR_SLICE_RETRY_SERIAL));
-    return hipGetLastError();
+    return k1p_pass(s, k1p_job(Records::kOneByte, in, st.n_states, pl, workspace), st, o, ResolveMode{});
 }
 
 // ... and phases B-D from resolved codes (no stretch is declined for its length here: a stretch without an

@@ -134,7 +134,6 @@ struct CabacLaneN {
 
 constexpr uint32_t kCensusStride = 16;                           // the one-lane-per-slice kernel renumbers from a 1-in-16 sample
 constexpr uint32_t kK1Waves = 4;                                 // waves per workgroup (fewer when the state rows are large): they share the two tables
-constexpr uint32_t kK1MaxWaves = 16;
 
 // table / index: the dense renumbering of the batch's contexts (k_k1p_densemap), or null: contexts as the caller
 // numbers them.  n_rows: contexts the kernel keeps states for (dense count, or n_states); init_states / final_states
@@ -142,9 +141,9 @@ constexpr uint32_t kK1MaxWaves = 16;
 // The coder is CabacLaneN; the forms it was measured against are gone from the library: their numbers are in DESIGN.md section 4.
 // REC_BYTES: 2 = two-byte records (AVR_KIND_CABAC, AVR_NOP_CABAC padding), 1 = ONE-BYTE tiles (AVR_KIND_CABAC8, 16 records a chunk:
 // k_pack_tiles8_narrow) -- no renumbering (table / index null, n_rows = n_states <= AVR_MAX_STATES8: the selectors are
-// dense ids already), at most kK1Waves waves: reading sixteen selectors ahead takes registers, and a 1024-thread bound caps a lane at 128.
+// dense ids already).  At most kK1Waves waves a workgroup, either form (eight and sixteen were measured: DESIGN.md section 4).
 template <bool TILED, int REC_BYTES = 2>
-__global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) void k_cabac_encode(
+__global__ __launch_bounds__(64 * kK1Waves) void k_cabac_encode(
     const void *recs, const uint64_t *off, const uint32_t *n_bins, const uint32_t *order,
     uint32_t n_slices, const uint8_t *init_states, uint32_t n_states, const uint16_t *table, const uint16_t *index, uint32_t n_rows,
     uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status,
@@ -163,8 +162,8 @@ __global__ __launch_bounds__(REC_BYTES == 1 ? 64 * kK1Waves : 64 * kK1MaxWaves) 
     const bool in_range = g < n_slices;
     const uint32_t slice = in_range ? (order ? order[g] : g) : 0;
     // Only slices whose status is `want_status` are coded: AVR_SLICE_OK in the normal case (a slice
-    // flagged by the packer is skipped), AVR_SLICE_RETRY_SERIAL when slices are handed back (by K1p, or by
-    // the renumbered launch of this kernel).  A workgroup without any leaves before it fills a table.
+    // flagged by the packer is skipped), AVR_SLICE_RETRY_SERIAL when slices are handed back by the renumbered
+    // launch of this kernel.  A workgroup without any leaves before it fills a table.
     int32_t st = in_range ? status[slice] : AVR_SLICE_OK;
     const bool active = in_range && st == want_status;
     if (!__syncthreads_or(active)) {
@@ -639,20 +638,6 @@ __global__ __launch_bounds__(256) void k_states_permute(const uint8_t *src, uint
     else dst[s * n_dst + j] = src[s * n_src + index[j]];
 }
 
-// ------------------------------------------------------------------ compact: per-slice regions -> dense
-
-// One workgroup per slice; the copy is contiguous on both sides.  dense_off[i+1]-dense_off[i]
-// is min(out_len[i], capacity) as computed by the host.
-__global__ __launch_bounds__(64) void k_compact(const uint8_t *out, const uint64_t *out_off, const uint64_t *dense_off,
-                                                uint32_t n_slices, uint8_t *dense) {
-    const uint32_t i = blockIdx.x;
-    if (i >= n_slices) return;
-    const uint8_t *src = out + out_off[i];
-    uint8_t *dst = dense + dense_off[i];
-    const uint32_t len = uint32_t(dense_off[i + 1] - dense_off[i]);
-    for (uint32_t k = threadIdx.x; k < len; k += 64) dst[k] = src[k];
-}
-
 // ------------------------------------------------------------------ synthetic streams
 
 struct TileRecordSink {               // gathers 8 records, stores one 16-byte chunk
@@ -756,9 +741,7 @@ void forget_stream(hipStream_t s) {
 // The one-lane-per-slice kernel keeps 64 x (contexts) state bytes in LDS per wave, so it renumbers the batch onto the
 // contexts its records use (census -> k_k1p_densemap -> one 4-byte read-back to size the launch), applied to the
 // records as they are loaded (sel_off): nothing is rewritten, init_states / final_states stay in the caller's numbering.
-// dense = false (and every hand-over from K1p, want_status != OK): the caller's numbering as it is.
-hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st, const Output &o, int32_t want_status, bool dense,
-                               const DenseHint *hint) {
+hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st, const Output &o, const DenseHint *hint) {
     const uint32_t n_slices = in.n_slices, n_states = st.n_states;
     if (n_slices == 0) return hipSuccess;
     hipError_t err;
@@ -766,7 +749,7 @@ hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st
     uint8_t **scratch = nullptr;                                 // -> used[32] + n_dense | table[1024] | index[1024]
     const uint16_t *table = nullptr, *index = nullptr;
     bool retry = false;                                          // the census was a sample: a second launch takes what it missed
-    if (dense && want_status == AVR_SLICE_OK && n_states > 8 && !no_dense()) {
+    if (n_states > 8 && !no_dense()) {
         err = g_scratch.get(s, &scratch, [](uint8_t *&p) { return hipMalloc(reinterpret_cast<void **>(&p), 256 + 4096); });
         if (err != hipSuccess) return err;
         uint32_t *used = reinterpret_cast<uint32_t *>(*scratch);
@@ -778,19 +761,10 @@ hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st
         if (in.tiled) hipLaunchKernelGGL(k_k1_census<true>, cgrid, dim3(256), 0, s, in.recs, in.off, in.n_bins, in.order, n_slices, used, stride);
         else hipLaunchKernelGGL(k_k1_census<false>, cgrid, dim3(256), 0, s, in.recs, in.off, in.n_bins, in.order, n_slices, used, stride);
         if ((err = launch_densemap(s, used, t, t + 1024, used + 32)) != hipSuccess) return err;
-        uint32_t nd = 0;
-        if (hint && hint->rows) {                                // sized by the caller's guess: nothing waits (see DenseHint)
-            nd = hint->rows;
-            retry = true;
-            if (hint->host_count && (err = hipMemcpyAsync(hint->host_count, used + 32, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return err;
-        } else {
-            if ((err = hipMemcpyAsync(&nd, used + 32, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return err;
-            if ((err = hipStreamSynchronize(s)) != hipSuccess) return err;
-            if (hint && hint->host_count) *hint->host_count = nd;
-        }
-        // a selector >= n_states is not a context of the slice even if it occurs: the table only serves selectors < n_states
-        // (k_pack_tiles has flagged such records; the kernel sends them to the no-op row either way, see sel_off)
-        n_rows = nd < n_states ? nd : n_states;
+        // (no more rows than n_states: a selector >= n_states is not a context of the slice even if it occurs -- the table only serves
+        // selectors < n_states; k_pack_tiles has flagged such records, and the kernel sends them to the no-op row either way, see sel_off)
+        if ((err = dense_rows(s, used + 32, n_states, hint, &n_rows)) != hipSuccess) return err;
+        if (hint && hint->rows) retry = true;                    // sized by a guess: contexts beyond it are handed back like missed ones
         table = t;
         index = t + 1024;
         if (st.final_states && (err = hipMemcpyAsync(st.final_states, st.init_states, size_t(n_slices) * n_states, hipMemcpyDeviceToDevice, s)) != hipSuccess)
@@ -798,9 +772,7 @@ hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st
     }
     auto launch = [&](uint32_t rows, const uint16_t *tb, const uint16_t *ix, int32_t want) -> hipError_t {
         const uint32_t per_wave = ((rows + 4 + 3) / 4) * 256;
-        uint32_t want_waves = test_hooks().k1_waves ? test_hooks().k1_waves : kK1Waves;
-        if (want_waves > kK1MaxWaves) want_waves = kK1MaxWaves;
-        const uint32_t waves = per_wave * want_waves <= 60 * 1024 ? want_waves : per_wave * 4 <= 60 * 1024 ? 4 : per_wave * 2 <= 60 * 1024 ? 2 : 1;
+        const uint32_t waves = per_wave * kK1Waves <= 60 * 1024 ? kK1Waves : per_wave * 2 <= 60 * 1024 ? 2 : 1;
         const uint32_t lds = waves * per_wave;
         const dim3 grid((n_slices + 64 * waves - 1) / (64 * waves)), block(64 * waves);
         // Shipped: the coder in normalised form with the digits taken every fourth bin, in step across the wave (CabacLaneN) --
@@ -815,7 +787,7 @@ hipError_t launch_cabac_encode(hipStream_t s, const Slices &in, const States &st
                            o.out_off, o.out_len, o.status, st.final_states, want);
         return hipGetLastError();
     };
-    err = launch(n_rows, table, index, want_status);
+    err = launch(n_rows, table, index, AVR_SLICE_OK);
     if (err == hipSuccess && retry) err = launch(n_states, nullptr, nullptr, AVR_SLICE_RETRY_SERIAL);
     return err;
 }
@@ -884,12 +856,6 @@ hipError_t launch_states_permute(hipStream_t s, const uint8_t *src, uint32_t n_s
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(k_states_permute, dim3(uint32_t((total + 255) / 256)), dim3(256), 0, s, src, n_src, dst, n_dst, index,
                        n_index, n_slices, scatter);
-    return hipGetLastError();
-}
-
-hipError_t launch_compact(hipStream_t s, const OutputView &o, const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense) {
-    if (n_slices == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_compact, dim3(n_slices), dim3(64), 0, s, o.out, o.out_off, dense_off, n_slices, dense);
     return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "avr_internal.h"
 #include "avr_plan.h"
 #include "avr_plan_dev.h"
 
@@ -420,14 +421,18 @@ hipError_t launch_plan_tiles(hipStream_t s, const uint32_t *n_bins, uint32_t n_s
     return scan<1>(s, TileSrc{n_bins, order, n_slices, records_per_chunk}, TileSink{tile_off, totals}, (uint64_t(n_slices) + 63) / 64, w + L.sums);
 }
 
+// the copy alone, on offsets the caller has made (the batch makes them on the host, where its getters need them): `dense` holds dense_total bytes
+hipError_t launch_compact(hipStream_t s, const OutputView &o, const uint64_t *dense_off, uint32_t n_slices, uint8_t *dense, uint64_t dense_total) {
+    if (n_slices == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_compact_wide, dim3((n_slices + 3u) / 4u), dim3(256), 0, s, o.out, o.out_off, n_slices, dense, dense_total, dense_off);
+    return hipGetLastError();
+}
+
 hipError_t launch_compact_wide(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, uint32_t n_slices,
                                uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off, void *ws) {
     const CompactLayout L = compact_layout(n_slices);
     if (hipError_t e = scan<1>(s, LenSrc{out_off, out_len}, LenSink{dense_off}, n_slices, static_cast<uint8_t *>(ws) + L.sums); e != hipSuccess) return e;
-    if (n_slices == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_compact_wide, dim3((n_slices + 3u) / 4u), dim3(256), 0, s, out, out_off, n_slices, dense, dense_capacity,
-                       static_cast<const uint64_t *>(dense_off));
-    return hipGetLastError();
+    return launch_compact(s, OutputView{out, out_off}, dense_off, n_slices, dense, dense_capacity);
 }
 
 }  // namespace avr

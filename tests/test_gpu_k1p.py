@@ -320,20 +320,61 @@ def test_serial_codes_kernel_equals_stage2_and_oracle(avr, oracle):
     assert got == oracle.encode_batch(0, *compact(recs, off, nb), states, cfg.n_states, threads=8)[0]
 
 
-@pytest.mark.parametrize("every", [1, 3])
-def test_phase_d_hand_over_is_coded_by_the_serial_kernels(avr, oracle, hooks, every):
+def _hand_over_slices(rng, shape):
+    """The batches of the hand-over test below by shape: (records, states) per slice, 120 contexts a slice."""
+    def stream(n, term, n_ctx=120):                          # n records in all, the last one put_terminate(1) if term
+        r, s = oracle_lib.random_cabac_stream(rng, n - int(term), n_ctx, terminate=term)
+        return r, np.concatenate([s, rng.integers(0, 126, 120 - n_ctx).astype(np.uint8)])
+    if shape == "random":
+        return [oracle_lib.random_cabac_stream(rng, int(rng.integers(1, 30000)), 120, terminate=bool(i % 3)) for i in range(20)]
+    if shape == "edges":
+        # nothing to code; lengths around a group of 16 codes and around a chunk of 1024 (exactly one chunk, with and without the
+        # terminate); one slice of 66 chunks and 70 slices of one chunk each, which both lie across a 64-chunk tile of the code buffer
+        lens = [0, 1, 15, 16, 17, 1000, 1023, 1024, 1024, 1025, 66 * 1024 - 5] + [int(n) for n in rng.integers(1, 1025, 70)]
+        return [stream(n, bool(n) and i != 7) for i, n in enumerate(lens)]
+    # a few chunks each, bins in 60 of the 120 contexts; "second-pass": three lone bins in contexts that a census of next to nothing misses
+    slices = [stream(2500 + 700 * i, bool(i % 3), 60) for i in range(10)]
+    if shape == "second-pass":
+        for i, ctx in ((2, 119), (5, 90), (8, 61)):
+            slices[i][0][1100 + 300 * i] = np.uint16((ctx << 1) | (i & 1))
+    return slices
+
+
+@pytest.mark.parametrize("every,shape", [pytest.param(1, "random", id="1"), pytest.param(3, "random", id="3"), pytest.param(1, "edges", id="edges"),
+                                         pytest.param(1, "second-pass", id="second-pass"), pytest.param(1, "parts", id="parts")])
+def test_phase_d_hand_over_is_coded_by_the_serial_kernels(avr, oracle, hooks, every, shape):
     """Phase D hands a slice whose carries it does not resolve in parallel to a serial kernel.  The pattern (a
     carry >= 2 into a 33-digit segment ffff...fffe) does not occur in practice, so the test hook
-    k1p_force_retry_every (test build of the library only) makes phase D hand over every n-th slice: the bytes must still be the oracle's, from
-    records (k_cabac_encode) and from resolved codes (k_cabac_encode_codes), with status 0 everywhere."""
-    hooks(k1p_force_retry_every=every)
-    rng = np.random.default_rng(31 + every)
-    slices = [oracle_lib.random_cabac_stream(rng, int(rng.integers(1, 30000)), 120, terminate=bool(i % 3)) for i in range(20)]
+    k1p_force_retry_every (test build of the library only) makes phase D hand over every n-th slice: the bytes, lengths, statuses and final
+    states must still be the oracle's.  The serial kernel is k_cabac_encode_codes either way: on the path's own wave-interleaved codes
+    behind records, on the caller's behind resolved codes.  Shapes: random lengths; the edges of the code buffer (_hand_over_slices);
+    a hand-over inside the second pass (census_stride 4099: every slice with a lone context is set aside, then handed over there --
+    asked in one call, and sized by a guess with the second pass as a call of its own); a call in two parts."""
+    import torch
+    hooks(k1p_force_retry_every=every, **({"census_stride": 4099} if shape == "second-pass" else {}))
+    rng = np.random.default_rng(31 + every if shape == "random" else [31, len(shape)])
+    slices = _hand_over_slices(rng, shape)
     want = [oracle.cabac_encode(r, s) for r, s in slices]
     w = avr.DeviceWorkload.from_host(0, [r for r, _ in slices], [s for _, s in slices], 0)
-    w.encode_chunked()                                       # records: phase A .. D, then k_cabac_encode
-    got, status = w.results()
-    assert not any(status) and got == [x[0] for x in want]
+
+    def check(what):
+        got, status = w.results()
+        fs = w.final_states.cpu().numpy().reshape(len(slices), 120)
+        for i in range(len(slices)):
+            assert status[i] == 0 and got[i] == want[i][0] and fs[i].tobytes() == want[i][1], f"{what}: slice {i} n={len(slices[i][0])}"
+        w.out.zero_(); w.out_len.zero_(); w.final_states.zero_()
+
+    if shape == "parts":
+        assert w.set_parts(2) == 2
+    w.encode_chunked(); torch.cuda.synchronize()             # records: phase A .. D, then k_cabac_encode_codes on the path's own codes
+    first = w.settle()
+    assert not first["redone"]
+    check("asked")
+    if shape != "random":
+        w.encode_chunked(); torch.cuda.synchronize()         # sized by the count of the run before: nothing waits
+        assert w.settle()["redone"] == (shape == "second-pass")
+        check("guessed")
+        return
     codes = w.resolve()
     w.out.zero_(); w.out_len.zero_()
     w.encode_resolved(codes)                                 # codes: phases B .. D, then k_cabac_encode_codes
