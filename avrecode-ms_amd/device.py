@@ -505,12 +505,15 @@ class DeviceWorkload:
                 rows_hint, self._part_counts.data_ptr() + 8 * i)
         return arr
 
-    def settle(self):
+    def settle(self, stream=None):
         """After the caller has synchronised the stream of encode() / encode_chunked(): what the device reported about the run that
         was sized by a guess.  Returns {"rows": context rows the batch needs, "hint": what the run was sized by, "redone": ...}.
         The one-lane-per-slice path is exact whatever the guess; the chunked path is run again (asking the device) if the batch needed
-        more rows than guessed, and its second pass is run if slices were left for it -- then the stream is synchronised again."""
+        more rows than guessed, and its second pass is run if slices were left for it -- then the device is synchronised again, or,
+        given `stream` (torch's current stream, the one the run was enqueued on), that stream alone: whatever the library ran on
+        streams of its own has been joined back to it."""
         import torch
+        wait = stream.synchronize if stream is not None else (lambda: torch.cuda.synchronize(self.n_bins.device))
         if self._counts is None or self._hinted_path is None:
             return {"rows": 0, "hint": 0, "redone": False}
         if self._hinted_path == "parts":                     # what every part reported
@@ -520,7 +523,7 @@ class DeviceWorkload:
                 self.status.copy_(self._status_before)
                 self.rows_hint = 0
                 self.encode_chunked()
-                torch.cuda.synchronize(self.n_bins.device)
+                wait()
                 rows, redone = max(int(self._part_counts[2 * i]) for i in range(self.n_parts)), True
             recs, rec_off = self._slice_major()
             for i, p in enumerate(self._parts):
@@ -532,7 +535,7 @@ class DeviceWorkload:
                         q.final_states))
                     redone = True
             if redone:
-                torch.cuda.synchronize(self.n_bins.device)
+                wait()
             if rows:
                 self.rows_hint = min(self.n_states, rows + 8)
             return {"rows": rows, "hint": used, "redone": redone, "parts": self.n_parts}
@@ -542,7 +545,7 @@ class DeviceWorkload:
             self.status.copy_(self._status_before)
             self.rows_hint = 0
             self.encode_chunked()
-            torch.cuda.synchronize(self.n_bins.device)
+            wait()
             rows, left, redone = int(self._counts[0]), int(self._counts[1]), True
         if self._hinted_path == "chunked" and left:
             recs, rec_off = self._slice_major()
@@ -553,7 +556,7 @@ class DeviceWorkload:
                 self.n_slices, self.init_states.data_ptr(), self.n_states, ctypes.byref(p["plan"]), ws_ptr, p["ws_bytes"],
                 self.out.data_ptr(), self.out_off.data_ptr(), self.out_len.data_ptr(), self.status.data_ptr(),
                 self.final_states.data_ptr() if self.final_states is not None else None))
-            torch.cuda.synchronize(self.n_bins.device)
+            wait()
             redone = True
         if rows:
             self.rows_hint = min(self.n_states, rows + 8)        # a little room, as avr_batch leaves (csrc/avr_api.cpp)
