@@ -40,9 +40,9 @@ EXPECT_NONE = 0xFFFFFFFF                                      # expect_len of a 
 NOP_CABAC, NOP_RANGE = 1026 << 1, 0
 CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
-_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_restore.hip", "avr_plan_dev.hip", "avr_api.cpp"]
+_SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_restore.hip", "avr_plan_dev.hip", "avr_api.cpp", "avr_multi.cpp"]
 _DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
-                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h", "avr_plan_dev.h"]
+                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h", "avr_plan_dev.h", "avr_multi.h"]
 
 
 class AvrError(RuntimeError):
@@ -215,6 +215,22 @@ SIGNATURES = {
     "avr_multi_get": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int)]),
     "avr_multi_placement": (c_int, [c_void_p, c_size_t]),
     "avr_multi_load": (c_int, [c_void_p, c_void_p]),
+    "avr_multi_reset": (c_int, [c_void_p]),
+    "avr_multi_created": (c_int, [c_void_p]),
+    "avr_multi_submit": (c_int, [c_void_p]),
+    "avr_multi_wait": (c_int, [c_void_p]),
+    "avr_multi_begin_group": (c_int, [c_void_p, c_void_p]),
+    "avr_multi_add_slice_range_keys": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "avr_multi_get_estimators": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "avr_multi_set_verify": (c_int, [c_void_p, c_int]),
+    "avr_multi_set_verify_k1": (c_int, [c_void_p, c_int]),
+    "avr_multi_get_verify": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_multi_get_verify_est": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_multi_expect": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t]),
+    "avr_multi_get_restore": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_multi_get_states": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "avr_multi_entry_info": (c_int, [c_void_p, c_size_t, POINTER(c_uint32)]),
+    "avr_multi_entry_ms": (c_int, [c_void_p, c_size_t, POINTER(c_float)]),
     "avr_pack_tiles_device": (c_int, [c_int, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p, c_void_p, c_void_p]),
     "avr_pack_tiles8_device": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
@@ -575,7 +591,9 @@ class Batch:
 
 
 class MultiBatch:
-    """One batch sharded over several GPUs (avr_multi_*): LPT by bin count, a host thread and an avr_batch per device."""
+    """One batch sharded over several GPUs (avr_multi_*): LPT by bin count, a host thread and an avr_batch per device.
+    The methods are Batch's, with Batch's results slice by slice and group by group, whichever entry coded what; a group of key
+    records stays on one entry.  submit() / wait() as Batch's; reset() keeps the sub-batches for the next run."""
 
     def __init__(self, devices, max_slices: int = 1024, max_bins: int = 1 << 24):
         import numpy as np
@@ -624,13 +642,92 @@ class MultiBatch:
         s = np.ascontiguousarray(init_states, dtype=np.uint8)
         return _check(self._L.avr_multi_add_slice_cabac8(self._h, r.ctypes.data, r.size, s.ctypes.data, s.size))
 
+    def begin_group(self, est=None) -> int:
+        """Key records, as Batch.begin_group: a group is the unit of placement, all its slices go to one entry."""
+        import numpy as np
+        if est is None:
+            return _check(self._L.avr_multi_begin_group(self._h, None))
+        e = np.ascontiguousarray(est, dtype=np.uint8)
+        if e.size != EST_KEYS * 2:
+            raise AvrError(f"a start table has {EST_KEYS} x 2 entries, not {e.size}")
+        return _check(self._L.avr_multi_begin_group(self._h, e.ctypes.data))
+
+    def add_slice_range_keys(self, recs) -> int:
+        import numpy as np
+        r = np.ascontiguousarray(recs, dtype=np.uint16)
+        return _check(self._L.avr_multi_add_slice_range_keys(self._h, r.ctypes.data, r.size))
+
+    def get_estimators(self, group: int):
+        """The group's table after the run (EST_KEYS x 2 uint8), from the sub-batch that owned it; a group without slices: its start table."""
+        import numpy as np
+        p, n = c_void_p(), c_size_t()
+        _check(self._L.avr_multi_get_estimators(self._h, group, ctypes.byref(p), ctypes.byref(n)))
+        return np.frombuffer(ctypes.string_at(p.value, n.value * 2), np.uint8).reshape(n.value, 2).copy()
+
+    def reset(self):
+        """Drops the slices, groups and expectations; keeps the device list, the verify settings and the sub-batches."""
+        _check(self._L.avr_multi_reset(self._h))
+
+    def created(self) -> int:
+        """How many avr_batch objects this object has created so far."""
+        return _check(self._L.avr_multi_created(self._h))
+
+    def submit(self):
+        _check(self._L.avr_multi_submit(self._h))
+
+    def wait(self):
+        _check(self._L.avr_multi_wait(self._h))
+
     def run(self):
         _check(self._L.avr_multi_run(self._h))
+
+    def set_verify(self, on: bool = True):
+        _check(self._L.avr_multi_set_verify(self._h, 1 if on else 0))
+
+    def set_verify_k1(self, on: bool = True):
+        _check(self._L.avr_multi_set_verify_k1(self._h, 1 if on else 0))
+
+    def _answer(self, fn, i: int) -> int:
+        v = c_uint32()
+        _check(fn(self._h, i, ctypes.byref(v)))
+        return v.value
+
+    def get_verify(self, i: int) -> int:
+        return self._answer(self._L.avr_multi_get_verify, i)
+
+    def get_verify_est(self, i: int) -> int:
+        return self._answer(self._L.avr_multi_get_verify_est, i)
+
+    def expect(self, i: int, payload):
+        """As Batch.expect: the bytes are copied now and go to the owning sub-batch at submit()."""
+        import numpy as np
+        p = np.frombuffer(bytes(payload), dtype=np.uint8)
+        _check(self._L.avr_multi_expect(self._h, i, p.ctypes.data if p.size else None, p.size))
+
+    def get_restore(self, i: int) -> int:
+        return self._answer(self._L.avr_multi_get_restore, i)
 
     def get(self, i: int):
         p, n, st = c_void_p(), c_size_t(), c_int()
         _check(self._L.avr_multi_get(self._h, i, ctypes.byref(p), ctypes.byref(n), ctypes.byref(st)))
         return (ctypes.string_at(p.value, n.value) if n.value else b""), st.value
+
+    def get_states(self, i: int) -> bytes:
+        p, n = c_void_p(), c_size_t()
+        _check(self._L.avr_multi_get_states(self._h, i, ctypes.byref(p), ctypes.byref(n)))
+        return ctypes.string_at(p.value, n.value) if n.value else b""
+
+    def entry_info(self, entry: int):
+        """avr_batch_run_info of the entry's sub-batch as four integers; zeros for an entry that got no slice."""
+        v = (c_uint32 * 4)()
+        _check(self._L.avr_multi_entry_info(self._h, entry, v))
+        return [int(x) for x in v]
+
+    def entry_ms(self, entry: int):
+        """[h2d, pack, encode, d2h, verify, verify_est, restore] milliseconds of the entry's sub-batch; zeros for an entry without a slice."""
+        ms = (c_float * 7)()
+        _check(self._L.avr_multi_entry_ms(self._h, entry, ms))
+        return list(ms)
 
     def placement(self, i: int) -> int:
         return _check(self._L.avr_multi_placement(self._h, i))

@@ -16,7 +16,7 @@ def shard_first_slice(rank: int, slices_per_rank: int) -> int:
 
 def lpt_assign(n_bins, world: int):
     """Greedy LPT: slices longest first, each to the rank with the least bins so far (ties: the lower rank).
-    Returns the rank of every slice.  Same plan as avr_multi_run (csrc/avr_api.cpp)."""
+    Returns the rank of every slice.  Same plan as avr_multi_submit (csrc/avr_multi.h) for slices that are their own units."""
     order = sorted(range(len(n_bins)), key=lambda i: -int(n_bins[i]))        # stable: equal lengths keep their order
     load = [0] * world
     owner = [0] * len(n_bins)
@@ -24,6 +24,26 @@ def lpt_assign(n_bins, world: int):
         r = min(range(world), key=lambda k: load[k])
         owner[i] = r
         load[r] += int(n_bins[i])
+    return owner
+
+
+def lpt_assign_groups(n_bins, group_first, world: int):
+    """Placement by units, the twin of avr::multi_place (csrc/avr_multi.h) for key records: group g holds the slices
+    [group_first[g], group_first[g + 1]), the last one up to len(n_bins), and weighs the sum of their bins; a group without
+    slices is no unit.  Groups heaviest first, equal weights in the caller's order, each to the rank with the least bins so far
+    (ties: the lower rank).  Returns the rank of every slice: all slices of a group share one."""
+    n = len(n_bins)
+    bounds = [int(f) for f in group_first] + [n]
+    units = [(bounds[g], bounds[g + 1]) for g in range(len(group_first)) if bounds[g] < bounds[g + 1]]
+    weight = [sum(int(n_bins[i]) for i in range(a, b)) for a, b in units]
+    order = sorted(range(len(units)), key=lambda u: -weight[u])           # stable
+    load = [0] * world
+    owner = [0] * n
+    for u in order:
+        r = min(range(world), key=lambda k: load[k])
+        load[r] += weight[u]
+        for i in range(*units[u]):
+            owner[i] = r
     return owner
 
 

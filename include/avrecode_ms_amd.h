@@ -190,7 +190,8 @@ int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n,
  * AVR_KIND_RANGE batch fed the resolved records.  avr_batch_get_estimators: the group's table after its last bin, in the layout
  * begin_group takes (valid until the next reset / destroy; undefined for a group with a malformed record).  A group split over two
  * batches -- the second begun from the first one's table -- gives the bytes and the table of the unsplit group.
- * avr_multi has no key records: a group must stay on one device. */
+ * avr_multi takes key records with the group as its unit of placement: a group's estimators are one serial table, so all slices of
+ * a group go to one device (avr_multi_begin_group, below). */
 int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in);
 int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n);
 int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg, size_t *n_keys);
@@ -290,24 +291,78 @@ int avr_batch_restore_ms(avr_batch *b, float *ms);
 
 /* ------------------------------------------------------------------ one batch over several GPUs
  * Slices are independent (one coder object each in the reference, recode.cpp:1270, :1525), so a batch shards
- * with no exchange between devices: avr_multi_run sorts the slices by bin count, hands them out longest first to
- * the device with the least work so far (greedy LPT), runs one avr_batch per device from a host thread of its
- * own (own stream, own pinned staging) and the getters return results by the caller's slice index.  `devices`
- * may name a device more than once (it then gets that many independent sub-batches).  Same record formats,
- * same rules (one kind per batch, one n_states) and same errors as the single-device batch. */
+ * with no exchange between devices: avr_multi_submit sorts the units by bin count, hands them out heaviest first to
+ * the entry of `devices` with the least work so far (greedy LPT, ties to the lower entry, equal weights in the caller's order),
+ * fills and submits one avr_batch per entry from a host thread of its own (own stream, own pinned staging), and the getters
+ * return results by the caller's slice index.  `devices` may name a device more than once (it then gets that many independent
+ * sub-batches).  Same record formats, same rules (one kind per batch, one n_states) and same errors as the single-device batch.
+ *
+ * THE RULE.  For any sequence of the calls below, an avr_multi over any device list gives, slice by slice and group by group, what
+ * ONE avr_batch on devices[0] given the same calls gives: bytes, lengths and statuses; final states; first_bad of either verifier
+ * and of the estimator checker; first_diff of the restore check; every group's table afterwards.  Which entry coded a slice, and
+ * which K1 / K2 path its sub-batch chose (the choice is per sub-batch, from its own share), shows in none of these.
+ *
+ * Units.  A unit is a slice; for key records a unit is a whole GROUP, whose weight is the sum of its slices' bins: a group's
+ * estimators are one serial table, so every slice of a group goes to one entry, where the entry's groups are begun in the caller's
+ * order from the tables copied at avr_multi_begin_group.  A group without slices is no unit and goes to no device;
+ * avr_multi_get_estimators answers for it from the multi's own copy of its start table, for every other group from the sub-batch
+ * that owned it.  avr_multi_begin_group / avr_multi_add_slice_range_keys carry avr_batch_begin_group's semantics word for word (the
+ * first slice opens a fresh group if none was begun; est_in copied and validated at the call; groups only with key records), and a
+ * group split over two multis -- the second begun from the first one's table -- gives the bytes and the table of the unsplit group.
+ *
+ * avr_multi_run = avr_multi_submit + avr_multi_wait.  avr_multi_submit places the units, fills and avr_batch_submits every entry's
+ * sub-batch, joins its threads and returns without waiting for any device (the one wait of avr_batch_submit remains: the first
+ * two-byte CABAC-record run of a fresh sub-batch).  avr_multi_wait runs avr_batch_wait on every entry, from threads.  Between the two,
+ * add, begin_group, expect, reset, the two settings and every getter return AVR_ERR_INVALID; avr_multi_wait without a submit does too.
+ * A run of a multi without slices succeeds and runs nothing.  After avr_multi_wait the getters work until avr_multi_reset /
+ * avr_multi_destroy; a second submit without a reset is refused ("batch already ran").  Two multis used in turn overlap the
+ * copies and kernels of consecutive batches the way two avr_batch objects do.
+ * Failure: if one entry's add, submit or wait fails, every entry already submitted is waited for before the call returns -- nothing
+ * stays in flight -- and the call returns that entry's code with "device entry E (device D): <its message>".  The object then
+ * accepts only avr_multi_reset and avr_multi_destroy.
+ *
+ * avr_multi_reset drops the slices, groups, expectations, kind and n_states; it keeps the device list, both verify settings and the
+ * sub-batches with their device and pinned buffers (AVR_ERR_INVALID while in flight).  On a later run an entry's sub-batch is reused
+ * (avr_batch_reset) when the capacity it was created with covers the entry's share; otherwise it is replaced by one that covers the
+ * larger of the two.  avr_multi_created: how many avr_batch objects the multi has created so far (a count, valid in every state).
+ *
+ * The checks are avr_batch's.  avr_multi_set_verify / avr_multi_set_verify_k1: kept over avr_multi_reset, applied to every sub-batch
+ * at submit; a K1 kind with set_verify on, or a K2 kind with set_verify_k1 on, is AVR_ERR_INVALID from avr_multi_submit before any
+ * sub-batch is touched, so the object stays usable (reset it, or switch the setting off and submit).  avr_multi_expect: the bytes are
+ * copied now and go to the owning sub-batch under the slice's local index at submit; avr_batch_expect's refusals apply at the call.
+ * avr_multi_get_verify / _get_verify_est / _get_restore / _get_states: the owning sub-batch's answer for the slice.
+ * All getters: AVR_ERR_INVALID before a completed run and for an index out of range. */
 typedef struct avr_multi avr_multi;
 avr_multi *avr_multi_create(const int *devices, size_t n_devices, size_t max_slices, size_t max_bins);
 void       avr_multi_destroy(avr_multi *m);
+int avr_multi_reset(avr_multi *m);
+int avr_multi_created(avr_multi *m);
 int avr_multi_add_slice_cabac(avr_multi *m, const uint16_t *recs, size_t n, const uint8_t *init_states, size_t n_states);
 int avr_multi_add_slice_range(avr_multi *m, const uint16_t *recs, size_t n);
 int avr_multi_add_slice_codes(avr_multi *m, const uint8_t *codes, size_t n);
 /* one-byte records, as avr_batch_add_slice_cabac8 (n_states <= AVR_MAX_STATES8) */
 int avr_multi_add_slice_cabac8(avr_multi *m, const uint8_t *recs8, size_t n, const uint8_t *init_states, size_t n_states);
+int avr_multi_begin_group(avr_multi *m, const uint8_t *est_in);
+int avr_multi_add_slice_range_keys(avr_multi *m, const uint16_t *recs, size_t n);
+int avr_multi_get_estimators(avr_multi *m, size_t group, const uint8_t **pos_neg, size_t *n_keys);
+int avr_multi_set_verify(avr_multi *m, int on);
+int avr_multi_set_verify_k1(avr_multi *m, int on);
+int avr_multi_expect(avr_multi *m, size_t slice, const uint8_t *bytes, size_t len);
+int avr_multi_submit(avr_multi *m);
+int avr_multi_wait(avr_multi *m);
 int avr_multi_run(avr_multi *m);
 int avr_multi_get(avr_multi *m, size_t slice, const uint8_t **bytes, size_t *len, int *status);
+int avr_multi_get_states(avr_multi *m, size_t slice, const uint8_t **states, size_t *n_states);
+int avr_multi_get_verify(avr_multi *m, size_t slice, uint32_t *first_bad);
+int avr_multi_get_verify_est(avr_multi *m, size_t slice, uint32_t *first_bad);
+int avr_multi_get_restore(avr_multi *m, size_t slice, uint32_t *first_diff);
 /* which entry of `devices` coded the slice, and the bins each entry was given (n_devices values): for tests and reports */
 int avr_multi_placement(avr_multi *m, size_t slice);
 int avr_multi_load(avr_multi *m, uint64_t *bins_per_device);
+/* avr_batch_run_info of the entry's sub-batch; ms[0..3] its avr_batch_timings, ms[4] avr_batch_verify_ms, ms[5]
+ * avr_batch_verify_est_ms, ms[6] avr_batch_restore_ms.  Zeros for an entry that got no slice. */
+int avr_multi_entry_info(avr_multi *m, size_t entry, uint32_t info[4]);
+int avr_multi_entry_ms(avr_multi *m, size_t entry, float ms[7]);
 
 /* ------------------------------------------------------------------ device-resident API
  * All pointers below are DEVICE pointers on `device`; `stream` is a hipStream_t (NULL = the
