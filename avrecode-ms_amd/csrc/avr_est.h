@@ -45,7 +45,6 @@ namespace est {
 constexpr uint32_t kKeys = 1026;                       // context ids 0..1023, bypass, terminate: h264_model's flat_[]
 constexpr uint32_t kLimit = 0x60;                      // recode.cpp:1046: halve when pos + neg exceeds this
 constexpr uint32_t kFresh = 1u | (1u << 8);            // {1, 1}; a table entry is pos | neg << 8
-constexpr uint32_t kChunk = 1024;                      // bins per chunk (AVR_CHUNK_BINS)
 constexpr uint32_t kNoBad = 0xffffffffu;
 
 AVR_EST_HD bool key_ok(uint32_t rec) { return (rec >> 1) < kKeys; }          // bits 12..15 clear and key <= AVR_SEL_TERMINATE

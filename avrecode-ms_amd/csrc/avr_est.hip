@@ -31,8 +31,8 @@ struct ChunkRef { uint32_t s, n, padded; uint64_t base; };
 __device__ inline ChunkRef chunk_ref(const EstParams &p, uint32_t c) {
     ChunkRef k;
     k.s = p.chunk_slice[c];
-    const uint32_t start = (c - p.chunk_base[k.s]) * kChunk, nb = p.n_bins[k.s];
-    k.n = nb > start ? min(kChunk, nb - start) : 0u;
+    const uint32_t in_slice = c - p.chunk_base[k.s], start = chunk_start(in_slice), nb = p.n_bins[k.s];
+    k.n = chunk_bins(in_slice, nb);                              // 0 for a chunk that starts at the slice's end (an empty slice's)
     k.padded = padded_bins(start, k.n, nb);
     k.base = p.rec_off[k.s] + start;
     return k;

@@ -38,7 +38,7 @@ namespace estv {
 
 constexpr uint32_t kKeys = 1026;                       // context ids 0..1023, bypass, terminate
 constexpr uint32_t kFresh = 1u | (1u << 8);            // {1, 1}; a table entry is pos | neg << 8
-constexpr uint32_t kChunk = 1024;                      // bins per chunk (AVR_CHUNK_BINS)
+static_assert(kSpan * kChunk < 65536, "last_entry: a bin's position in its piece (at most kSpan chunks) goes into 16 bits");
 constexpr uint32_t kNone = 0xffffffffu;                // AVR_VERIFY_NONE
 constexpr uint32_t kPieceBlock = 64;                   // pieces per block of the start walk
 constexpr int32_t kOk = 0, kBadRecord = 3, kVerifyFailed = 4;    // AVR_SLICE_OK, _BAD_RECORD, _VERIFY_FAILED

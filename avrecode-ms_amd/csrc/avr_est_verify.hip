@@ -31,9 +31,9 @@ struct ChunkAt { uint32_t s, start, n, padded; uint64_t base; };
 __device__ inline ChunkAt chunk_at(const EstvParams &p, uint32_t c) {
     ChunkAt k;
     k.s = p.chunk_slice[c];
-    const uint32_t nb = p.n_bins[k.s];
-    k.start = (c - p.chunk_base[k.s]) * kChunk;
-    k.n = nb > k.start ? min(kChunk, nb - k.start) : 0u;
+    const uint32_t nb = p.n_bins[k.s], in_slice = c - p.chunk_base[k.s];
+    k.start = chunk_start(in_slice);
+    k.n = chunk_bins(in_slice, nb);                              // 0 for a chunk that starts at the slice's end (an empty slice's)
     k.padded = padded_bins(k.start, k.n, nb);
     k.base = p.rec_off[k.s] + k.start;
     return k;
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(64) void k_estv_last(EstvParams p) {
             if (!takes_part(p, ck.s)) continue;
             const uint4 *ksrc = reinterpret_cast<const uint4 *>(p.keys + ck.base);
             const uint4 *rsrc = reinterpret_cast<const uint4 *>(p.recs + ck.base);
-            const uint32_t at = (c - pc[pi].c0) * kChunk;        // below 2^16: a piece has at most kSpan chunks
+            const uint32_t at = chunk_start(c - pc[pi].c0);      // below 2^16: a piece has at most kSpan chunks
             for (uint32_t v = lane; v * 8 < ck.n; v += 64) {
                 const uint4 kq = ksrc[v], rq = rsrc[v];
                 const uint32_t kw[4] = {kq.x, kq.y, kq.z, kq.w}, rw[4] = {rq.x, rq.y, rq.z, rq.w};

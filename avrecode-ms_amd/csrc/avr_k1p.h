@@ -33,6 +33,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "avr_chunk.h"
+
 #if defined(__HIPCC__)
 #define AVR_HD __host__ __device__ inline
 #else
@@ -52,7 +54,6 @@ namespace k1p {
 #define AVR_PIN2(a, b) ((void)0)
 #endif
 
-constexpr uint32_t kChunk = 1024;              // bins per fixed chunk (one lane of B1 / C)
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kMaxStretch = 16 * kChunk;  // a longer stretch sends the slice to the serial kernel
 constexpr uint32_t kCodeBypass = 252;
@@ -244,7 +245,7 @@ AVR_HD void code_entries4(const CodeEntryC *codes, uint32_t d, CodeEntryC e[4]) 
 
 AVR_HD void b1_stretch(const uint8_t *res, uint32_t n, uint32_t chunk, const CodeEntry *codes, uint32_t max_stretch,
                        Stretch *o) {
-    const uint32_t lo = chunk * kChunk, limit = lo + kChunk;
+    const uint32_t lo = chunk_start(chunk), limit = chunk_start(chunk + 1);   // limit: not clamped to n
     uint32_t R[4], T[4] = {0, 0, 0, 0};
     uint32_t i;
     o->too_long = 0;

@@ -38,8 +38,6 @@ static __device__ const CabacTables d_tables = make_cabac_tables();
 
 using namespace k1p;
 
-constexpr uint32_t kSortBlock = AVR_SORT_BLOCK_BINS;
-
 struct Plan {                       // device pointers of the caller's plan (avr_chunk_plan) + record layout
     const uint16_t *recs;
     const uint64_t *rec_off;
@@ -50,14 +48,14 @@ struct Plan {                       // device pointers of the caller's plan (avr
     const uint64_t *dig_off;
     uint32_t n_states;              // sort keys: the contexts the batch uses, numbered densely 0 .. n_states-1 (k_k1p_densemap)
     uint32_t ns_full;               // contexts per slice as the caller numbers them (init_states / final_states rows)
-    const uint16_t *table;          // [1024] caller's context number -> dense id (kNotUsed: occurs nowhere in the batch)
+    const uint16_t *table;          // [AVR_MAX_STATES] caller's context number -> dense id (kNotUsed: occurs nowhere in the batch)
     const uint16_t *index;          // [n_states] dense id -> caller's context number (null: the identity, one-byte records)
     const uint8_t *recs8;           // one-byte records (AVR_KIND_CABAC8) in place of recs: rec_off in bytes, multiples of 16
 };
 constexpr uint32_t kNotUsed = 0xffffu;
 
-// The kernels' own buffer of resolved codes, wave-interleaved: 16-byte group g (of 64) of global chunk gc is at
-//   base + (((gc / 64) * 64 + g) * 64 + gc % 64) * 16,
+// The kernels' own buffer of resolved codes, wave-interleaved in tiles of kTileChunks = 64 chunks: 16-byte group g (of kChunkCodeGroups) of
+// global chunk gc is at  base + (((gc / 64) * kChunkCodeGroups + g) * 64 + gc % 64) * 16,
 // so the 64 lanes of a wave -- 64 consecutive chunks -- store (k_k1p_replay) and load (k_k1p_c) group g as one
 // contiguous kilobyte, where slice-major codes cost a cache line per lane per 16-byte access.  chunk0 = the slice's
 // first global chunk; i = index of a code in the slice.  (The public two-stage entry points keep slice-major codes.)
@@ -65,9 +63,9 @@ struct TileCodes {
     const uint8_t *base;
     uint32_t chunk0;
     __device__ __forceinline__ size_t at(uint32_t i) const {
-        const uint32_t gc = chunk0 + (i >> 10), g = (i >> 4) & 63u;
-        return ((size_t(gc >> 6) * 64 + g) * 64 + (gc & 63u)) * 16;
+        return group_at(chunk0 + chunk_of(i), bin_in_chunk(i) >> 4);
     }
+    static __device__ __forceinline__ size_t group_at(uint32_t gc, uint32_t g) { return ((size_t(gc >> 6) * kChunkCodeGroups + g) * kTileChunks + (gc & 63u)) * 16; }
     __device__ __forceinline__ U4 load16(uint32_t i) const { return *reinterpret_cast<const U4 *>(base + at(i)); }
     __device__ __forceinline__ uint32_t byte(uint32_t i) const { return base[at(i) + (i & 15u)]; }
 };
@@ -95,7 +93,7 @@ struct TileCodes {
 // vector instructions per bin, three passes over the records, four more over the sorted copy).  Sorting
 // inside the chunk instead lets ONE LANE do it with private counters in LDS -- a count pass and a
 // placement pass of a dozen instructions per bin at full SIMD width, no cross-lane ranking at all -- and
-// the result is tiny: 1024 bits and one 16-bit end position per context per chunk.
+// the result is tiny: kChunk bits and one 16-bit end position per context per chunk.
 
 // Which contexts the batch uses: one bit per context that occurs (`used`), under the caller's numbering (the offset
 // of the state byte in cabac_state[], recode.cpp:325: up to 1024, of which a stream touches few).  `stride` > 1: from
@@ -157,14 +155,14 @@ __global__ __launch_bounds__(256) void k_k1p_swap(int32_t *status, uint32_t n, i
     else if (v == c) status[i] = d;
 }
 
-// used (1024 bits) -> table[caller's number] = dense id, index[dense id] = caller's number, *n_dense.
-__global__ __launch_bounds__(1024) void k_k1p_densemap(const uint32_t *used, uint16_t *table, uint16_t *index, uint32_t *n_dense) {
-    __shared__ uint32_t sc[1024];
+// used (AVR_MAX_STATES bits) -> table[caller's number] = dense id, index[dense id] = caller's number, *n_dense.  A thread per context.
+__global__ __launch_bounds__(AVR_MAX_STATES) void k_k1p_densemap(const uint32_t *used, uint16_t *table, uint16_t *index, uint32_t *n_dense) {
+    __shared__ uint32_t sc[AVR_MAX_STATES];
     const uint32_t k = threadIdx.x;
     const uint32_t bit = (used[k >> 5] >> (k & 31)) & 1u;
     sc[k] = bit;
     __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
+    for (uint32_t d = 1; d < AVR_MAX_STATES; d <<= 1) {
         const uint32_t v = k >= d ? sc[k - d] : 0;
         __syncthreads();
         sc[k] += v;
@@ -173,8 +171,8 @@ __global__ __launch_bounds__(1024) void k_k1p_densemap(const uint32_t *used, uin
     const uint32_t id = sc[k] - bit;
     table[k] = bit ? uint16_t(id) : uint16_t(kNotUsed);
     if (bit) index[id] = uint16_t(k);
-    if (k >= sc[1023]) index[k] = uint16_t(kNotUsed);            // rows a launch sized by a guess has beyond the count: no context
-    if (k == 1023) *n_dense = sc[1023];
+    if (k >= sc[AVR_MAX_STATES - 1]) index[k] = uint16_t(kNotUsed);            // rows a launch sized by a guess has beyond the count: no context
+    if (k == AVR_MAX_STATES - 1) *n_dense = sc[AVR_MAX_STATES - 1];
 }
 
 // State after n = 0 .. 8 bins, per state and bin pattern (first bin in the low bit; cabac_code.h:43-47):
@@ -240,12 +238,12 @@ __device__ __forceinline__ void for_record_groups8(const uint8_t *r, uint32_t i0
 // One lane per chunk: counting sort of the chunk's context bins by (dense) context, in LDS, serially.
 //   pass 1  count the bins of every context                    cnt[k][lane]++           (16-bit, lane-private)
 //   scan    exclusive prefix over the contexts                 cnt[k][lane] = first position of context k
-//   pass 2  place: position = cnt[k][lane]++, the bin goes to bit `position` of the lane's 1024-bit string
+//   pass 2  place: position = cnt[k][lane]++, the bin goes to bit `position` of the lane's kChunk-bit string
 // after which cnt[k][lane] is where context k's bins END (context k's bins are bits [end[k-1], end[k])).
-// Out: lbits[gc][32 dwords], lend[gc][nk] (16-bit), both written through a transposed read of the LDS
+// Out: lbits[gc][kChunkBitDwords], lend[gc][nk] (16-bit), both written through a transposed read of the LDS
 // arrays so that a wave's stores are contiguous.
 //
-// The counters of contexts 2j and 2j+1 share a dword (a chunk has at most 1024 bins: no carry from the low
+// The counters of contexts 2j and 2j+1 share a dword (a chunk has at most kChunk bins: no carry from the low
 // half), and every update is an LDS atomic on the lane's own dword: ds_add_u32 without return in pass 1,
 // ds_add_rtn_u32 in pass 2, ds_or_b32 for the bit.  Nothing else touches those dwords, so "atomic" only means
 // that the LDS does the read-modify-write itself, in issue order: the eight bins of a 16-byte group are
@@ -257,7 +255,7 @@ __device__ __forceinline__ void for_record_groups8(const uint8_t *r, uint32_t i0
 // values end up side by side behind the last context's), nk + 1 = bypass and padding (a record past the slice's last bin, by its
 // index), nk + 2 = a context of the slice that has no dense id (the sampled census missed it), nk + 3 = no selector of the slice at
 // all -- the no-op selector 1026 included, which only the padding may hold.  The last
-// three count from position 1024, i.e. land in a spare row of `bits`: no branch on the bin kind anywhere.
+// three count from position kChunk, i.e. land in the spare row of `bits` (kChunkSpareRow): no branch on the bin kind anywhere.
 //
 // This is also where every record of the path is examined (the census only samples).  A lane flags its slice
 //   AVR_SLICE_BAD_RECORD    if row nk + 3 is not empty, a record has a bit above its selector set, or a
@@ -273,18 +271,18 @@ __device__ __forceinline__ void for_record_groups8(const uint8_t *r, uint32_t i0
 template <class SelT, bool R8>
 __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks, int32_t *status, uint32_t *lbits,
                                                    uint16_t *lend, uint32_t *n_retry) {
-    extern __shared__ uint32_t local_lds[];                      // per wave: bits[33][64], then cnt[(nk + 5) / 2][64] (two 16-bit counters each)
+    extern __shared__ uint32_t local_lds[];                      // per wave: bits[kChunkBitDwords + 1][64], then cnt[(nk + 5) / 2][64] (two 16-bit counters each)
     constexpr uint32_t kSelTab = R8 ? 128 : 2048;
     __shared__ SelT sel_tab[kSelTab];
     const uint32_t nk = p.n_states, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t cnt_rows = (nk + 5) / 2;                      // contexts 0 .. nk-1 and the rows nk .. nk+3
-    const uint32_t wave_dwords = (33 + cnt_rows) * 64;
+    const uint32_t wave_dwords = (kChunkBitDwords + 1 + cnt_rows) * 64;
     uint32_t *bits = local_lds + wv * wave_dwords;
-    uint32_t *cnt = bits + 33 * 64;
+    uint32_t *cnt = bits + (kChunkBitDwords + 1) * 64;
     for (uint32_t sel = threadIdx.x; sel < kSelTab; sel += blockDim.x) {
         uint32_t k;
         if (R8) k = sel < nk ? sel : sel == AVR_SEL8_TERMINATE ? nk : sel == AVR_SEL8_BYPASS ? nk + 1 : nk + 3;
-        else if (sel < 1024u) {
+        else if (sel < AVR_MAX_STATES) {
             const uint32_t d = p.table[sel];
             k = d < nk ? d : sel < p.ns_full ? nk + 2 : nk + 3;
         } else k = sel == AVR_SEL_TERMINATE ? nk : sel == AVR_SEL_BYPASS ? nk + 1 : nk + 3;   // (the no-op selector too: a bad record)
@@ -303,9 +301,8 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
         if (status[s] == AVR_SLICE_OK) {
             mine = true;
             n = p.n_bins[s];
-            i0 = (gc - p.chunk_base[s]) * kChunk;
-            i1 = i0 + kChunk < n ? i0 + kChunk : n;
-            if (i0 > i1) i0 = i1;
+            const ChunkSpan sp = chunk_span(gc - p.chunk_base[s], n);
+            i1 = sp.i1; i0 = sp.i0 > i1 ? i1 : sp.i0;            // (clamped: an empty slice's one chunk)
             if (R8) {
                 const uint64_t off = p.rec_off[s];
                 misaligned = uint32_t(off & 15u);
@@ -362,10 +359,10 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
     const uint32_t n_term = count_of(nk), n_missed = count_of(nk + 2), n_invalid = count_of(nk + 3) | (high & 0xf000f000u) | misaligned;
     uint32_t term_at = 0;                                        // where the terminate row starts
     {
-        uint32_t run = 0;                                        // exclusive prefix over the contexts and the terminate row; the rest starts at 1024
+        uint32_t run = 0;                                        // exclusive prefix over the contexts and the terminate row; the rest starts at kChunk
         for (uint32_t j = 0; j < cnt_rows; j++) {
             const uint32_t c = my_cnt[64 * j], c0 = c & 0xffffu, c1 = c >> 16;
-            const uint32_t s0 = 2 * j <= nk ? run : 1024u, s1 = 2 * j + 1 <= nk ? run + c0 : 1024u;
+            const uint32_t s0 = 2 * j <= nk ? run : kChunk, s1 = 2 * j + 1 <= nk ? run + c0 : kChunk;
             if (2 * j == nk) term_at = s0;
             if (2 * j + 1 == nk) term_at = s1;
             my_cnt[64 * j] = s0 | s1 << 16;
@@ -381,8 +378,8 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
                                             __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
         for (uint32_t j = 0; j < 16; j++) {
-            const uint32_t at = (pos[j] >> (e[j] & 31u)) & 2047u;
-            const uint32_t row = at >> 5 < 32u ? at >> 5 : 32u;
+            const uint32_t at = (pos[j] >> (e[j] & 31u)) & kChunkPosMask;
+            const uint32_t row = at >> 5 < kChunkBitDwords ? at >> 5 : kChunkSpareRow;
             __hip_atomic_fetch_or(reinterpret_cast<uint32_t *>(bits_b + row * 256u), bin[j] << (at & 31u), __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -401,8 +398,8 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
                                             __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++) {
-            const uint32_t at = (pos[j] >> (e[j] & 31u)) & 2047u;            // < 1024: a context bin's place; the spare row counts from 1024
-            const uint32_t row = at >> 5 < 32u ? at >> 5 : 32u;
+            const uint32_t at = (pos[j] >> (e[j] & 31u)) & kChunkPosMask;    // < kChunk: a context bin's place; the spare row counts from kChunk
+            const uint32_t row = at >> 5 < kChunkBitDwords ? at >> 5 : kChunkSpareRow;
             const uint32_t bin = (w[j >> 1] >> ((j & 1) * 16)) & 1u;
             __hip_atomic_fetch_or(reinterpret_cast<uint32_t *>(bits_b + row * 256u), bin << (at & 31u), __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -424,9 +421,9 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
     }
     // out, transposed: flat element f of the wave's 64 rows <-> (chunk f / row, column f % row)
     {
-        uint32_t *dst = lbits + size_t(gc0) * 32;
-        const uint32_t lim = gc0 < total_chunks ? (total_chunks - gc0 < 64 ? total_chunks - gc0 : 64) * 32 : 0;
-        for (uint32_t f = lane; f < lim; f += 64) dst[f] = bits[64 * (f & 31u) + (f >> 5)];
+        uint32_t *dst = lbits + size_t(gc0) * kChunkBitDwords;
+        const uint32_t lim = gc0 < total_chunks ? (total_chunks - gc0 < 64 ? total_chunks - gc0 : 64) * kChunkBitDwords : 0;
+        for (uint32_t f = lane; f < lim; f += 64) dst[f] = bits[64 * (f % kChunkBitDwords) + f / kChunkBitDwords];
     }
     if (nk) {
         uint16_t *dst = lend + size_t(gc0) * nk;
@@ -445,7 +442,7 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
 // context through the slice (cabac_code.h:43-47), chunk by chunk.  At chunk c the lane notes the state
 // (est[gc][k]: what k_k1p_replay starts chunk c from), then walks the context's bins of the chunk -- bits
 // [end[k-1], end[k]) of the chunk's bit string -- up to eight per look-up (k_k1p_tn's table, in LDS).  The loads
-// are one row of `lend` and pieces of one 128-byte bit string per chunk; they do not depend on the state and
+// are one row of `lend` and pieces of one bit string (kChunkBitBytes) per chunk; they do not depend on the state and
 // run ahead of the chain: end positions four chunks ahead, the 64-bit window a run starts in two ahead.
 // They are unconditional (the arrays are padded past the last chunk, and in front for k = 0): a load inside a
 // branch is waited for at the end of the branch, which would put its whole latency into every step.
@@ -462,6 +459,10 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
 // four look-ups without a branch, four more if any lane needs them, one shift-add between two look-ups -- is 3 % faster
 // than the loops it replaced; taking out, for the measurement, the stores, or the window loads, changes nothing.)
 constexpr uint32_t kChainLanes = 22, kChainWaves = 8;         // kChainLanes: the fewest lanes a wave takes
+__device__ __forceinline__ uint4 window(const uint32_t *bw, uint32_t pos) {       // bits 32 (pos / 32) .. + 127 of a chunk's string
+    const uint32_t wi = (pos >> 5) & (kChunkBitDwords - 1);      // (past the last dword: the next chunk's, never used -- a run ends by bit kChunk)
+    return make_uint4(bw[wi], bw[wi + 1], bw[wi + 2], bw[wi + 3]);
+}
 __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint32_t n_slices, uint32_t groups, uint32_t chain_lanes, const int32_t *status,
                                                       const uint8_t *tng, const uint32_t *lbits, const uint16_t *lend,
                                                       const uint8_t *init_states, uint8_t *est, uint8_t *final_states) {
@@ -479,9 +480,9 @@ __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint3
     const uint32_t col = p.index ? p.index[k] : k, row4 = ((nk + 3) >> 2) << 2;
     if (col >= p.ns_full) return;                                // a row beyond the batch's contexts (launch sized by a guess)
     uint32_t st = init_states[size_t(s) * p.ns_full + col] & 127u;
-    const uint32_t c0 = p.chunk_base[s], nc = (p.n_bins[s] + kChunk - 1) / kChunk;
+    const uint32_t c0 = p.chunk_base[s], nc = chunks_of(p.n_bins[s]);
     const uint16_t *le = lend + size_t(c0) * nk + k;             // end[k] of the chunk being requested (four ahead)
-    const uint32_t *bw_ahead = lbits + size_t(c0) * 32;          // bit string of the chunk whose window is being requested (two ahead)
+    const uint32_t *bw_ahead = lbits + size_t(c0) * kChunkBitDwords;   // bit string of the chunk whose window is being requested (two ahead)
     const uint32_t *bw_cur = bw_ahead;                           // bit string of the chunk being walked
     uint8_t *eo = est + size_t(c0) * row4 + k;
     auto ends = [&]() {                                          // (end[k-1], end[k]), then on to the next chunk
@@ -489,17 +490,13 @@ __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint3
         le += nk;
         return make_uint2(k ? em : 0u, e1);
     };
-    auto window = [&](const uint32_t *bw, uint32_t pos) {        // bits 32 (pos / 32) .. + 127 of a chunk's string
-        const uint32_t wi = (pos >> 5) & 31u;                    // (past dword 31: the next chunk's, never used -- a run ends by bit 1024)
-        return make_uint4(bw[wi], bw[wi + 1], bw[wi + 2], bw[wi + 3]);
-    };
     uint2 e0 = ends(), e1 = ends(), e2 = ends(), e3 = ends();
-    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + 32, e1.x);
-    bw_ahead += 64;
+    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + kChunkBitDwords, e1.x);
+    bw_ahead += 2 * kChunkBitDwords;
     for (uint32_t c = 0; c < nc; c++) {
         const uint2 e4 = ends();
         const uint4 w2 = window(bw_ahead, e2.x);
-        bw_ahead += 32;
+        bw_ahead += kChunkBitDwords;
         *eo = uint8_t(st);
         eo += row4;
         uint32_t pos = e0.x;
@@ -543,7 +540,7 @@ __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint3
                 }
             }
         }
-        bw_cur += 32;
+        bw_cur += kChunkBitDwords;
         e0 = e1; e1 = e2; e2 = e3; e3 = e4;
         w0 = w1; w1 = w2;
     }
@@ -607,7 +604,7 @@ __device__ __forceinline__ void chain_step(const uint8_t *tn, const uint32_t *bw
             uint32_t have = 32;
             while (left) {
                 if (have == 0) {
-                    const uint32_t wi = (pos >> 5) & 31u;
+                    const uint32_t wi = (pos >> 5) & (kChunkBitDwords - 1);
                     avail = __builtin_amdgcn_alignbit(bw_cur[wi + 1], bw_cur[wi], pos & 31u);
                     have = 32;
                 }
@@ -632,7 +629,7 @@ __device__ __forceinline__ bool chain_lane(const Plan &p, uint32_t n_slices, uin
     if (s >= n_slices || status[s] != AVR_SLICE_OK) return false;
     const uint32_t col = p.index ? p.index[k] : k;
     if (col >= p.ns_full) return false;
-    const uint32_t nc = (p.n_bins[s] + kChunk - 1) / kChunk, seg_len = (nc + n_segs - 1) / n_segs;
+    const uint32_t nc = chunks_of(p.n_bins[s]), seg_len = (nc + n_segs - 1) / n_segs;
     const uint32_t c_begin = seg * seg_len < nc ? seg * seg_len : nc, c_end = c_begin + seg_len < nc ? c_begin + seg_len : nc;
     *o = ChainLane{s, k, seg, c_begin, c_end, nc, col};
     return true;
@@ -648,20 +645,19 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_k1p_chain_seg(Plan p, uint32
     const uint32_t nk = p.n_states, row4 = ((nk + 3) >> 2) << 2, k = L.k;
     const uint32_t c0 = p.chunk_base[L.s] + L.c_begin, n_ch = L.c_end - L.c_begin;
     const uint16_t *le = lend + size_t(c0) * nk + k;
-    const uint32_t *bw_ahead = lbits + size_t(c0) * 32, *bw_cur = bw_ahead;
+    const uint32_t *bw_ahead = lbits + size_t(c0) * kChunkBitDwords, *bw_cur = bw_ahead;
     uint8_t *eo = est + size_t(c0) * row4 + k;
     auto ends = [&]() { const uint32_t e1 = le[0], em = le[-1]; le += nk; return make_uint2(k ? em : 0u, e1); };
-    auto window = [&](const uint32_t *bw, uint32_t pos) { const uint32_t wi = (pos >> 5) & 31u; return make_uint4(bw[wi], bw[wi + 1], bw[wi + 2], bw[wi + 3]); };
     uint2 e0 = ends(), e1 = ends(), e2 = ends(), e3 = ends();
-    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + 32, e1.x);
-    bw_ahead += 64;
+    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + kChunkBitDwords, e1.x);
+    bw_ahead += 2 * kChunkBitDwords;
     uint32_t st[2] = {124u, 125u};                               // the two ends of the order: (valMPS 0, pStateIdx 62), (valMPS 1, pStateIdx 62)
     uint32_t met_chunk = n_ch, n_bins = 0;
     uint64_t bits0 = 0, bits1 = 0;
     for (uint32_t c = 0; c < n_ch; c++) {
         const uint2 e4 = ends();
         const uint4 w2 = window(bw_ahead, e2.x);
-        bw_ahead += 32;
+        bw_ahead += kChunkBitDwords;
         if (st[0] == st[1]) {                                    // met: this chunk's entry state is what it is whatever the segment was entered in
             *eo = uint8_t(st[0]);
             met_chunk = met_chunk < c ? met_chunk : c;
@@ -677,7 +673,7 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_k1p_chain_seg(Plan p, uint32
         }
         n_bins += cnt > 64u ? kSegBits + 1u : cnt;              // a chunk with more than 64 of them: the string is not kept
         chain_step<2>(tn, bw_cur, pos, end, w0, st);
-        bw_cur += 32;
+        bw_cur += kChunkBitDwords;
         e0 = e1; e1 = e2; e2 = e3; e3 = e4;
         w0 = w1; w1 = w2;
     }
@@ -695,21 +691,20 @@ template <bool NOTE>
 __device__ __forceinline__ uint32_t chain_chunks(const uint8_t *tn, const uint32_t *lbits, const uint16_t *lend, uint8_t *est, uint32_t nk, uint32_t row4,
                                                  uint32_t k, uint32_t c_first, uint32_t n_ch, uint32_t st0) {
     const uint16_t *le = lend + size_t(c_first) * nk + k;
-    const uint32_t *bw_ahead = lbits + size_t(c_first) * 32, *bw_cur = bw_ahead;
+    const uint32_t *bw_ahead = lbits + size_t(c_first) * kChunkBitDwords, *bw_cur = bw_ahead;
     uint8_t *eo = est + size_t(c_first) * row4 + k;
     auto ends = [&]() { const uint32_t e1 = le[0], em = le[-1]; le += nk; return make_uint2(k ? em : 0u, e1); };
-    auto window = [&](const uint32_t *bw, uint32_t pos) { const uint32_t wi = (pos >> 5) & 31u; return make_uint4(bw[wi], bw[wi + 1], bw[wi + 2], bw[wi + 3]); };
     uint2 e0 = ends(), e1 = ends(), e2 = ends(), e3 = ends();
-    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + 32, e1.x);
-    bw_ahead += 64;
+    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + kChunkBitDwords, e1.x);
+    bw_ahead += 2 * kChunkBitDwords;
     uint32_t st[1] = {st0};
     for (uint32_t c = 0; c < n_ch; c++) {
         const uint2 e4 = ends();
         const uint4 w2 = window(bw_ahead, e2.x);
-        bw_ahead += 32;
+        bw_ahead += kChunkBitDwords;
         if (NOTE) { *eo = uint8_t(st[0]); eo += row4; }
         if (st[0] < 126u) chain_step<1>(tn, bw_cur, e0.x, e0.y, w0, st);      // pStateIdx 63 never moves
-        bw_cur += 32;
+        bw_cur += kChunkBitDwords;
         e0 = e1; e1 = e2; e2 = e3; e3 = e4;
         w0 = w1; w1 = w2;
     }
@@ -919,8 +914,8 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
             kk = sel < nk ? sel : sel == AVR_SEL8_BYPASS ? nk + 1 : sel == AVR_SEL8_TERMINATE ? nk + 2 : nk + 4;
         } else {
             // contexts get their dense id; 1024 (bypass), 1025 (terminate), 1026 (no-op) -> nk+1, nk+2, nk+3; the rest nk / nk+4
-            const uint32_t over = (sel < 1023u ? 1023u : sel > 1027u ? 1027u : sel) - 1023u;
-            const uint32_t dense = sel < 1024u ? uint32_t(p.table[sel]) : kNotUsed;
+            const uint32_t kLast = AVR_MAX_STATES - 1, over = (sel < kLast ? kLast : sel > kLast + 4 ? kLast + 4 : sel) - kLast;   // kLast: the last context
+            const uint32_t dense = sel < AVR_MAX_STATES ? uint32_t(p.table[sel]) : kNotUsed;
             kk = (dense < nk ? dense : nk) + over;
         }
         sel_off[sel] = ((kk & ~3u) << 6) + (kk & 3u);
@@ -949,8 +944,9 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
     for (int q = 0; q < 4; q++) { o.t_exit[q] = 0; o.r_exit[q] = 0; }
     if (status[s] != AVR_SLICE_OK) { stretch[gc] = o; return; }
     const uint32_t c = gc - p.chunk_base[s];
-    const uint32_t n = p.n_bins[s], i0 = c * kChunk;
-    const uint32_t i1 = i0 + kChunk < n ? i0 + kChunk : n;      // end of the chunk's own bins = where a closing LPS may come from
+    const uint32_t n = p.n_bins[s];
+    const ChunkSpan span = chunk_span(c, n);
+    const uint32_t i0 = span.i0, i1 = span.i1;                   // i1: end of the chunk's own bins = where a closing LPS may come from
     {
         const uint32_t nkw = (nk + 3) >> 2;
         const uint32_t *e = est + size_t(gc) * nkw;
@@ -961,9 +957,9 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
     }
     const uint16_t *r = p.recs + p.rec_off[s];
     // where the chunk's codes go: bin i of the slice at ro + (i - ro_i0) * ro_scale / 16 ... in whole 16-byte groups only
-    uint8_t *ro = TILE_CODES ? res + ((size_t(gc >> 6) * 64) * 64 + (gc & 63u)) * 16 : res + p.res_off[s];
+    uint8_t *ro = TILE_CODES ? res + TileCodes::group_at(gc, 0) : res + p.res_off[s];
     auto put16 = [&](uint32_t i, const U4 &v) {                  // codes i .. i+15 of the slice (i a multiple of 16, in this chunk)
-        if (TILE_CODES) *reinterpret_cast<U4 *>(ro + size_t((i - i0) >> 4) * 1024) = v;
+        if (TILE_CODES) *reinterpret_cast<U4 *>(ro + size_t((i - i0) >> 4) * kTileRowBytes) = v;   // a row a group: the tile's 64 chunks x 16 bytes
         else *reinterpret_cast<U4 *>(ro + i) = v;
     };
     B1Walk b1;
@@ -1115,8 +1111,9 @@ __global__ __launch_bounds__(256) void k_k1p_b1(Plan p, uint32_t total_chunks, c
     if (gc >= total_chunks) return;
     const uint32_t slice = p.chunk_slice[gc];
     if (status[slice] != AVR_SLICE_OK) { st[gc].first = kNone; st[gc].too_long = 0; return; }
-    const uint32_t c = gc - p.chunk_base[slice], n = p.n_bins[slice], i0 = c * kChunk;
-    const uint32_t i1 = i0 + kChunk < n ? i0 + kChunk : n;
+    const uint32_t c = gc - p.chunk_base[slice], n = p.n_bins[slice];
+    const ChunkSpan span = chunk_span(c, n);
+    const uint32_t i0 = span.i0, i1 = span.i1;
     const uint8_t *r = res + p.res_off[slice];
     B1Walk b1;
     b1.init(c, i0, i1, n, max_stretch, codes2);
@@ -1124,9 +1121,9 @@ __global__ __launch_bounds__(256) void k_k1p_b1(Plan p, uint32_t total_chunks, c
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++) e[j] = cinfo[((j < 4 ? lo : hi) >> (8 * (j & 3))) & 0xffu];
     };
-    uint8_t *to = tile ? tile + ((size_t(gc >> 6) * 64) * 64 + (gc & 63u)) * 16 : nullptr;
+    uint8_t *to = tile ? tile + TileCodes::group_at(gc, 0) : nullptr;
     auto sixteen = [&](uint32_t base, const U4 &v) {
-        if (to) *reinterpret_cast<U4 *>(to + size_t((base - i0) >> 4) * 1024) = v;
+        if (to) *reinterpret_cast<U4 *>(to + size_t((base - i0) >> 4) * kTileRowBytes) = v;       // a row a group, as in k_k1p_replay
         uint4 e[8];
         eight(v.x, v.y, e); b1.group(base, e);
         eight(v.z, v.w, e); b1.group(base + 8, e);
@@ -1572,7 +1569,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
     if (stretch_out) *stretch_out = stretch;
     uint32_t *used = reinterpret_cast<uint32_t *>(w + L.meta);   // [32], then n_dense, then the number of slices for the second pass
     uint32_t *n_dense = used + 32, *n_retry = used + 33;
-    uint16_t *table = reinterpret_cast<uint16_t *>(w + L.meta + 256), *index = table + 1024;
+    uint16_t *table = reinterpret_cast<uint16_t *>(w + L.meta + 256), *index = table + AVR_MAX_STATES;
     const uint8_t *tn = nullptr;
     p.table = table;
     p.index = index;
@@ -1590,7 +1587,7 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         if ((e = tn_table(s, &tn)) != hipSuccess) return e;
     } else {
         hipLaunchKernelGGL(k_k1p_census, dim3((pl->total_blocks + kCensusBlocks - 1) / kCensusBlocks), dim3(256), 0, s, p, pl->total_blocks, status, used, mode.census_stride);
-        hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
+        hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(AVR_MAX_STATES), 0, s, used, table, index, n_dense);
         if ((e = tn_table(s, &tn)) != hipSuccess) return e;
         if ((e = dense_rows(s, n_dense, ns, hint, &n_states)) != hipSuccess) return e;   // a guess is checked by the caller afterwards (DenseHint)
     }
@@ -1599,9 +1596,9 @@ static hipError_t launch_resolve(hipStream_t s, Plan p, uint32_t n_slices, const
         // the waves of a workgroup share the renumbering table; each has its own counters and bit strings
         // as many waves to a CU as its LDS takes (the kernel waits on LDS round trips: two waves a SIMD against one and a half is
         // what there is to win), as workgroups of w waves: the w with the most waves resident, the smaller workgroup on a tie
-        const uint32_t per_wave = (33 + (n_states + 5) / 2) * 64 * 4;
+        const uint32_t per_wave = (kChunkBitDwords + 1 + (n_states + 5) / 2) * 64 * 4;   // k_k1p_local's bits and cnt
         const bool narrow = n_states <= 500;                     // (rows up to (n_states + 3) / 2 = 251: offsets below 2^16)
-        const uint32_t kLdsPerCu = 160 * 1024, kStatic = r8 ? 128 * 2 : narrow ? 2048 * 2 : 2048 * 4;
+        const uint32_t kLdsPerCu = 160 * 1024, kStatic = r8 ? 128 * 2 : narrow ? 2048 * 2 : 2048 * 4;   // sel_tab: 11-bit selectors
         auto local = r8 ? k_k1p_local<uint16_t, true> : narrow ? k_k1p_local<uint16_t, false> : k_k1p_local<uint32_t, false>;
         uint32_t waves = 1, best = 0;
         for (uint32_t w = 1; w <= 8; w++) {
@@ -1710,7 +1707,7 @@ static hipError_t launch_code(hipStream_t s, const Plan &p, uint32_t n_slices, c
 }
 
 hipError_t launch_densemap(hipStream_t s, const uint32_t *used, uint16_t *table, uint16_t *index, uint32_t *n_dense) {
-    hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(1024), 0, s, used, table, index, n_dense);
+    hipLaunchKernelGGL(k_k1p_densemap, dim3(1), dim3(AVR_MAX_STATES), 0, s, used, table, index, n_dense);
     return hipGetLastError();
 }
 

@@ -19,6 +19,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "avr_chunk.h"
+
 #if defined(__HIPCC__)
 #define AVR_K2P_HD __host__ __device__ inline
 #else
@@ -28,7 +30,7 @@
 namespace avr {
 namespace k2p {
 
-constexpr uint32_t kChunk = 1024;                      // bins per chunk
+using avr::kChunk;                                     // bins per chunk (avr_chunk.h)
 constexpr uint64_t kOne = uint64_t(1) << 63;           // fixed_one (arithmetic_code.h:54-55)
 constexpr uint64_t kMinRange = uint64_t(1) << 51;      // arithmetic_code.h:61-62
 constexpr uint32_t kTail = 8;                          // byte positions a chunk's left-over low is spread over

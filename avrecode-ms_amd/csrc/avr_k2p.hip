@@ -26,7 +26,6 @@
 namespace avr {
 
 using namespace k2p;
-static_assert(k2p::kChunk == AVR_CHUNK_BINS, "the chunk plan of the C ABI is made for this chunk size");
 
 namespace {
 
@@ -140,13 +139,13 @@ __global__ __launch_bounds__(64) void k_k2p_ranges(K2Plan p, uint32_t n_slices, 
     for (; g + 4 <= n_groups; g += 4) {
         U4 nx2[4];
         line(g + 8, nx2);
-        if ((g & (kChunk / 8 - 1)) == 0) { ck_range[c0 + (g >> 7)] = range; ck_pos[c0 + (g >> 7)] = pos; }
+        if (unit_in_chunk<8>(g) == 0) { ck_range[c0 + chunk_of_unit<8>(g)] = range; ck_pos[c0 + chunk_of_unit<8>(g)] = pos; }
         group(g, cur[0]); group(g + 1, cur[1]); group(g + 2, cur[2]); group(g + 3, cur[3]);
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) { cur[k] = nx1[k]; nx1[k] = nx2[k]; }
     }
     if (g < n_groups) {                                          // the slice's last, partial line (chunks start on whole lines)
-        if ((g & (kChunk / 8 - 1)) == 0) { ck_range[c0 + (g >> 7)] = range; ck_pos[c0 + (g >> 7)] = pos; }
+        if (unit_in_chunk<8>(g) == 0) { ck_range[c0 + chunk_of_unit<8>(g)] = range; ck_pos[c0 + chunk_of_unit<8>(g)] = pos; }
         for (uint32_t k = 0; g + k < n_groups; k++) group(g + k, cur[k]);
     }
     if (n_groups == 0) { ck_range[c0] = range; ck_pos[c0] = 0; }  // an empty slice still has its one chunk
@@ -195,9 +194,9 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
     if (p.chunk_base[s + 1] - c0 >= long_chunks) return;
     const U4 *r = reinterpret_cast<const U4 *>(p.recs + p.rec_off[s]);
     const uint32_t n_groups = (n + 7) >> 3, last = n_groups ? n_groups - 1 : 0;
-    const uint32_t g_begin = seg_begin * (kChunk / 8);
+    const uint32_t g_begin = seg_begin * kChunkRecGroups;
     if (seg_begin && g_begin >= n_groups) return;                // the slice ended in an earlier segment
-    const uint32_t g_end = uint64_t(seg_end) * (kChunk / 8) < n_groups ? seg_end * (kChunk / 8) : n_groups;
+    const uint32_t g_end = uint64_t(seg_end) * kChunkRecGroups < n_groups ? seg_end * kChunkRecGroups : n_groups;
     RangeFP rg = fp_from_u64(seg_begin ? ck_range[c0 + seg_begin] : kOne);          // arithmetic_code.h:96-97
     FpConsts K = fp_consts();
     asm volatile("" : "+s"(K.two32), "+s"(K.inv_two32), "+s"(K.split32), "+s"(K.two51), "+s"(K.two47));   // in scalar registers, see FpConsts
@@ -234,7 +233,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
         for (uint32_t k = 0; k < 4; k++) pos8 += range_step_fp(rg, vmin_hi, o[k], K);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto note = [&](uint32_t g) { ck_range[c0 + (g >> 7)] = fp_to_u64(rg); ck_pos[c0 + (g >> 7)] = pos8 >> 3; };
+    auto note = [&](uint32_t g) { ck_range[c0 + chunk_of_unit<8>(g)] = fp_to_u64(rg); ck_pos[c0 + chunk_of_unit<8>(g)] = pos8 >> 3; };
     auto line = [&](uint32_t g, U4 v[4]) {
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) v[k] = r[g + k < last ? g + k : last];
@@ -259,7 +258,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
     for (; g + 4 <= g_end; g += 4) {                             // (g_end is a whole number of lines unless it is the slice's end)
         U4 nx2[4];
         line(g + 8, nx2);
-        if ((g & (kChunk / 8 - 1)) == 0) note(g);
+        if (unit_in_chunk<8>(g) == 0) note(g);
         zmin = pk_min16(zmin, pk_min16(pk_min16(group_min(cur[0]), group_min(cur[1])),
                                        pk_min16(group_min(cur[2]), g + 3 == last ? last_min : group_min(cur[3]))));
         __builtin_amdgcn_s_waitcnt(0xc07f);                      // lgkmcnt(0), here where it costs nothing: all that is in flight is the
@@ -276,7 +275,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
         for (uint32_t k = 0; k < 4; k++) { cur[k] = nx1[k]; nx1[k] = nx2[k]; }
     }
     if (g < g_end) {                                             // the slice's last, partial line (chunks start on whole lines)
-        if ((g & (kChunk / 8 - 1)) == 0) note(g);
+        if (unit_in_chunk<8>(g) == 0) note(g);
         for (uint32_t k = 0; k < 3 && g + k < g_end; k++) zmin = pk_min16(zmin, g + k == last ? last_min : group_min(cur[k]));
         fetch(cur[0].z, cur[0].w, ob); walk(oa); walk(ob);
         if (g + 1 < g_end) { fetch(cur[1].x, cur[1].y, oa); fetch(cur[1].z, cur[1].w, ob); walk(oa); walk(ob); }
@@ -301,7 +300,7 @@ __device__ __forceinline__ void ranges_fp_body(uint32_t block, uint32_t long_chu
 // slot after slot at IMMEDIATE offsets from one base register (every lane the same address: a broadcast): three reads and
 // no address arithmetic per record, about 25 instructions where the lane-per-slice kernel has 31.5.  All lanes walk the same
 // range; lane 0 writes the notes.  Same notes, same statuses, same segments as k_k2p_ranges_fp.
-constexpr uint32_t kRingBins = 64, kRingBytes = kRingBins * 48;
+constexpr uint32_t kRingBins = 64, kRingBytes = kRingBins * 48;   // (a chunk is whole batches: chunk_of_unit<kRingBins> asserts it)
 __device__ __forceinline__ void ranges_wave_body(uint32_t s, uint32_t long_chunks, K2Plan p, uint32_t n_slices, uint64_t *ck_range, uint32_t *ck_pos,
                                                  uint64_t *fin_range, uint32_t *fin_pos, int32_t *status, uint32_t seg_begin, uint32_t seg_end) {
     __shared__ TotA tot_a[512];
@@ -349,14 +348,14 @@ __device__ __forceinline__ void ranges_wave_body(uint32_t s, uint32_t long_chunk
         *reinterpret_cast<double2 *>(slot + 4) = make_double2(pe.ps, pe.nb);
     };
     auto note = [&](uint32_t b) {
-        if (lane == 0) { ck_range[c0 + b / (kChunk / kRingBins)] = fp_to_u64(rg); ck_pos[c0 + b / (kChunk / kRingBins)] = pos8 >> 3; }
+        if (lane == 0) { ck_range[c0 + chunk_of_unit<kRingBins>(b)] = fp_to_u64(rg); ck_pos[c0 + chunk_of_unit<kRingBins>(b)] = pos8 >> 3; }
     };
     if (b_begin < b_end) {
         uint32_t rec1 = load(b_begin + 1);
         unpack(load(b_begin), b_begin);
         for (uint32_t b = b_begin; b < b_end; b++) {
             const uint32_t rec2 = load(b + 2);                   // two batches ahead of the walk (masked behind the slice's end)
-            if ((b & (kChunk / kRingBins - 1)) == 0) note(b);
+            if (unit_in_chunk<kRingBins>(b) == 0) note(b);
             unpack(rec1, b + 1);                                 // the next batch's operands: LDS works in order, the walk below finds its own complete
             uint32_t base = (b & 1u) * kRingBytes;
             asm volatile("" : "+v"(base));                       // one base register, the 192 reads at immediate offsets
@@ -500,8 +499,8 @@ __global__ __launch_bounds__(256) void k_k2p_code(K2Plan p, uint32_t n_slices, u
     __syncthreads();
     ChunkPick k;
     if (!pick_chunk(p, blockIdx.x * 256 + threadIdx.x, n_slices, total_chunks, seg_begin, seg_len, ck_pos, fin_pos, status, want, &k)) return;
-    const uint32_t s = k.s, gc = k.gc, n = k.n, i0 = k.c * kChunk;
-    const uint32_t i1 = i0 + kChunk < n ? i0 + kChunk : n;
+    const ChunkSpan span = chunk_span(k.c, k.n);
+    const uint32_t s = k.s, gc = k.gc, i0 = span.i0, i1 = span.i1;
     const uint16_t *r = p.recs + p.rec_off[s];
     uint32_t *at = S + p.out_off[s] + ck_pos[gc];
     uint32_t *const shared_end = at + kTail;                     // up to here the chunks before this one may have left bytes of their low

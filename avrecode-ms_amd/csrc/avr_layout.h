@@ -34,8 +34,9 @@ struct alignas(16) SegSummary {
     uint16_t met_chunk;       // first chunk of the segment (relative to its start) whose entry state is noted; segment length if none
 };
 
-// resolved codes, wave-interleaved in tiles of 64 chunks (TileCodes in avr_k1p.hip): a kilobyte per chunk, whole tiles
-inline uint64_t tile_codes_bytes(uint32_t total_chunks) { return (uint64_t(total_chunks) + 63) / 64 * 64 * 1024; }
+// resolved codes, wave-interleaved in tiles of kTileChunks chunks, a row a 16-byte group of each (TileCodes in avr_k1p.hip): whole tiles
+constexpr uint32_t kTileChunks = 64, kTileRowBytes = kTileChunks * 16;
+inline uint64_t tile_codes_bytes(uint32_t total_chunks) { return (uint64_t(total_chunks) + kTileChunks - 1) / kTileChunks * kTileChunks * kChunkCodeBytes; }
 
 // Phase A (launch_resolve): per-chunk bit strings, end positions and entry states, tables; laid out for the caller's context count
 // `ns` -- the kernels index it by the dense count, which is known only after the census.
@@ -43,11 +44,11 @@ struct ResolveLayout { uint64_t lbits, lend, est, stretch, meta, summ, total; };
 inline ResolveLayout resolve_layout(size_t n_slices, uint32_t ns, const avr_chunk_plan *pl) {
     ResolveLayout L;
     Cursor c;
-    L.lbits = c.take(uint64_t(pl->total_chunks + 64) * 128);     // + 64 chunks: the chains read a few chunks ahead, unconditionally
+    L.lbits = c.take(uint64_t(pl->total_chunks + 64) * kChunkBitBytes);   // + 64 chunks: the chains read a few chunks ahead, unconditionally
     L.lend = c.take(uint64_t(pl->total_chunks + 64) * ns * 2 + 256) + 128;   // 128 bytes into its region: k_k1p_ctxchain reads lend[-1]
     L.est = c.take(uint64_t(pl->total_chunks) * ((ns + 3) / 4) * 4 + 16);    // + 16: slack behind the last row; callers allocate exactly the quote, so it stays
     L.stretch = c.take(uint64_t(pl->total_chunks) * sizeof(k1p::Stretch));
-    L.meta = c.take(256 + 2048 + 2048 + kTnBytes);               // used[32] + n_dense, table[1024], index[1024], tn
+    L.meta = c.take(256 + 2 * AVR_MAX_STATES + 2 * AVR_MAX_STATES + kTnBytes);   // used[32] + n_dense, table[AVR_MAX_STATES], index[AVR_MAX_STATES], tn
     L.summ = c.take(uint64_t(n_slices) * ns * kMaxChainSegs * sizeof(SegSummary));    // the segmented chains' summaries
     L.total = c.at;
     return L;

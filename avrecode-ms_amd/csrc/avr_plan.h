@@ -20,8 +20,8 @@
 namespace avr {
 
 // ------------------------------------------------------------------ per slice of nb bins
-AVR_PLAN_HD uint32_t slice_chunks(uint64_t nb) { return nb ? uint32_t((nb + AVR_CHUNK_BINS - 1) / AVR_CHUNK_BINS) : 1u; }            // an empty slice has one
-AVR_PLAN_HD uint32_t slice_blocks(uint64_t nb) { return nb ? uint32_t((nb + AVR_SORT_BLOCK_BINS - 1) / AVR_SORT_BLOCK_BINS) : 1u; }  // census blocks
+AVR_PLAN_HD uint32_t slice_chunks(uint64_t nb) { return nb ? uint32_t((nb + kChunk - 1) / kChunk) : 1u; }            // an empty slice has one
+AVR_PLAN_HD uint32_t slice_blocks(uint64_t nb) { return nb ? uint32_t((nb + kSortBlock - 1) / kSortBlock) : 1u; }    // census blocks
 AVR_PLAN_HD uint64_t slice_work_bytes(uint64_t nb) { return ((nb + 15) & ~uint64_t(15)) + 16; }   // per-bin work arrays: whole 16-byte groups and one more
 AVR_PLAN_HD uint64_t slice_digit_sums(uint64_t nb) { return nb / 2 + 8; }
 AVR_PLAN_HD uint64_t slice_out_bytes(uint64_t nb) { return (nb + 16 + 7) & ~uint64_t(7); }        // worst case 8 bits per bin for either coder ("output sizing") + stop bytes

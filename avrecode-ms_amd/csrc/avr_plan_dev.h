@@ -99,8 +99,8 @@ inline uint64_t workspace_bytes(size_t n_slices) {
 }
 
 inline void bounds(size_t n_slices, uint64_t max_total_bins, uint64_t *cap_chunks, uint64_t *cap_blocks) {
-    if (cap_chunks) *cap_chunks = max_total_bins / AVR_CHUNK_BINS + n_slices;       // a slice has at most n_bins / 1024 + 1 chunks, an empty one has one
-    if (cap_blocks) *cap_blocks = max_total_bins / AVR_SORT_BLOCK_BINS + n_slices;
+    if (cap_chunks) *cap_chunks = max_total_bins / kChunk + n_slices;               // a slice has at most n_bins / kChunk + 1 chunks, an empty one has one
+    if (cap_blocks) *cap_blocks = max_total_bins / kSortBlock + n_slices;
 }
 
 }  // namespace plan_dev

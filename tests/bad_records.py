@@ -11,12 +11,14 @@ the oracle masks K1 selectors to 11 bits, ignores K2 bit 15 and reports the FIRS
 alone: expected() adds what it does not see."""
 import numpy as np
 
+from avrecode_ms_amd import CHUNK_BINS, SORT_BLOCK_BINS          # AVR_CHUNK_BINS, AVR_SORT_BLOCK_BINS (tests/test_cabi.py holds them to the header)
+
 KIND_CABAC, KIND_RANGE, KIND_CABAC8 = 0, 1, 3
 SLICE_OK, SLICE_ZERO_PROB, SLICE_OVERFLOW, SLICE_BAD_RECORD = 0, 1, 2, 3
 SEL_BYPASS, SEL_TERMINATE, SEL_NOP = 1024, 1025, 1026
 SEL8_BYPASS, SEL8_TERMINATE, MAX_STATES8 = 126, 127, 126
 TERM1, TERM1_8 = (SEL_TERMINATE << 1) | 1, (SEL8_TERMINATE << 1) | 1
-CHUNK_BINS, SORT_BLOCK_BINS, RING_BINS = 1024, 4096, 64      # AVR_CHUNK_BINS, AVR_SORT_BLOCK_BINS, K2p's kRingBins
+RING_BINS = 64                                                   # K2p's kRingBins
 
 _oracle = None
 

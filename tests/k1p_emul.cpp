@@ -22,6 +22,7 @@ struct HostAdder {
     void flush() {}
     size_t stores = 0, adds = 0;
 };
+uint32_t g_max_stretch = kMaxStretch;
 }  // namespace
 
 extern "C" {
@@ -33,19 +34,23 @@ int k1p_emul_resolve(const uint16_t *recs, size_t n, uint8_t *states, size_t n_s
     for (size_t i = 0; i < n; i++) {
         const uint32_t bin = recs[i] & 1, sel = (recs[i] >> 1) & 0x7ff;
         if (done) return 3;
-        if (sel < 1024) {
+        if (sel < AVR_MAX_STATES) {
             if (sel >= n_states) return 3;
             const uint32_t s = states[sel];
             res[m++] = uint8_t(code_context(s, bin));
             states[sel] = (bin != (s & 1)) ? kT.mlps_state[127 - s] : kT.mlps_state[128 + s];
-        } else if (sel == 1024) res[m++] = uint8_t(kCodeBypass | bin);
-        else if (sel == 1025) { res[m++] = uint8_t(code_terminate(bin)); done = bin; }
+        } else if (sel == AVR_SEL_BYPASS) res[m++] = uint8_t(kCodeBypass | bin);
+        else if (sel == AVR_SEL_TERMINATE) { res[m++] = uint8_t(code_terminate(bin)); done = bin; }
         else return 3;
     }
     *n_res = m;
     for (size_t k = m; k % 16; k++) res[k] = uint8_t(kCodePad);
     return 0;
 }
+
+// The stretch length from which a slice is declined (info[3] = 1): kMaxStretch, as the whole path has it, unless set otherwise --
+// 0xffffffff is what launch_k1p_code passes (avr_k1p.hip): no stretch is declined for its length.
+void k1p_emul_set_max_stretch(uint32_t max_stretch) { g_max_stretch = max_stretch; }
 
 // Phases B1, B2, C, D on resolved codes.  info (optional, 8 words): n_active, t_total, r_final, bad,
 // plain stores, atomic adds, n_digits, -.
@@ -54,10 +59,10 @@ size_t k1p_emul_encode_resolved(const uint8_t *res, size_t n, uint8_t *out, size
     for (int p = 0; p < 64; p++) rows[p] = kT.packed[2 * p][0];
     CodeEntry codes[256];
     for (uint32_t c = 0; c < 256; c++) codes[c] = code_entry(c, rows);
-    const uint32_t n_chunks = n ? uint32_t((n + kChunk - 1) / kChunk) : 1;
+    const uint32_t n_chunks = n ? chunks_of(uint32_t(n)) : 1;
     std::vector<Stretch> st(n_chunks);
     std::vector<Entry> en(n_chunks);
-    for (uint32_t c = 0; c < n_chunks; c++) b1_stretch(res, uint32_t(n), c, codes, kMaxStretch, &st[c]);
+    for (uint32_t c = 0; c < n_chunks; c++) b1_stretch(res, uint32_t(n), c, codes, g_max_stretch, &st[c]);
     SliceTotals tot;
     b2_chain(st.data(), n_chunks, en.data(), &tot);
     const uint32_t nd = ref_digits(tot.t_total);

@@ -20,7 +20,7 @@ CHUNKS = [1, 2, 7, 47, 48, 49, 95, 96, 1024]
 
 @pytest.fixture(scope="module")
 def emul():
-    deps = [SRC, os.path.join(CSRC, "avr_est.h"), os.path.join(CSRC, "avr_layout.h"), os.path.join(CSRC, "avr_k1p.h")]
+    deps = [SRC, os.path.join(CSRC, "avr_est.h"), os.path.join(CSRC, "avr_layout.h"), os.path.join(CSRC, "avr_k1p.h"), os.path.join(CSRC, "avr_chunk.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, "-o", SO, SRC], check=True)
     lib = ctypes.CDLL(SO)

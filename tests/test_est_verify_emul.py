@@ -21,7 +21,7 @@ SRC = os.path.join(ROOT, "tests", "est_verify_emul.cpp")
 SO = os.path.join(ROOT, "tests", "_est_verify_emul.so")
 CHECK_SRC = os.path.join(ROOT, "tests", "est_verify_check.cpp")
 CHECK_BIN = os.path.join(ROOT, "tests", "_est_verify_check")
-DEPS = [os.path.join(CSRC, h) for h in ("avr_est_verify.h", "avr_layout.h", "avr_k1p.h")]
+DEPS = [os.path.join(CSRC, h) for h in ("avr_est_verify.h", "avr_layout.h", "avr_k1p.h", "avr_chunk.h")]
 
 
 def _stale(target, sources):

@@ -2,7 +2,14 @@
 (avrecode-ms_amd/csrc/avr_k1p.h, the code the HIP kernels wrap) are compiled for the host by
 tests/k1p_emul.cpp and run chunk by chunk, then compared with the oracle.  This checks the
 decomposition itself -- stretch summaries, the 4->4 chain, digit sums, carries, finish() --
-without a GPU; tests/test_gpu_k1p.py checks the kernels."""
+without a GPU; tests/test_gpu_k1p.py checks the kernels.
+
+The same source is also built at two other chunk lengths (-DAVR_TEST_CHUNK_BINS, which csrc/avr_chunk.h honours in host-only
+builds): 256 and 4096 bins.  The chunk length is defined once, so every use of it in avr_k1p.h must follow; one that stayed a
+literal 1024 fails both (tried: `lo = chunk * 1024, limit = lo + 1024` in b1_stretch miscodes at 4096 and, at 256, codes right
+with a quarter of the stretches: see active_stretches).  Those builds decline no stretch for its
+length, as the resolved-code entry point of the library does not (launch_k1p_code): the limit is kMaxStretch = 16 chunks, so what it
+declines depends on the chunk length by design, and the tests about declined streams stay at the shipped length."""
 import ctypes
 import os
 import subprocess
@@ -14,19 +21,34 @@ import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "k1p_emul.cpp")
-SO = os.path.join(ROOT, "tests", "_k1p_emul.so")
 CSRC = os.path.join(ROOT, "avrecode-ms_amd", "csrc")
+OTHER_CHUNK_BINS = (256, 4096)                                   # the shipped length is 1024
+
+
+def build_emul(chunk_bins=None):
+    """tests/k1p_emul.cpp at the shipped chunk length, or at `chunk_bins`."""
+    so = os.path.join(ROOT, "tests", "_k1p_emul.so" if chunk_bins is None else f"_k1p_emul_{chunk_bins}.so")
+    deps = [SRC] + [os.path.join(CSRC, h) for h in ("avr_k1p.h", "avr_chunk.h", "avr_tables.h", "avr_div.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        define = [] if chunk_bins is None else [f"-DAVR_TEST_CHUNK_BINS={chunk_bins}"]
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC] + define + ["-o", so, SRC], check=True)
+    lib = ctypes.CDLL(so)
+    lib.k1p_emul_encode_resolved.restype = ctypes.c_size_t
+    lib.div_emul_check.restype = ctypes.c_uint64
+    lib.div_emul_check.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    return lib
 
 
 @pytest.fixture(scope="module")
 def emul():
-    deps = [SRC, os.path.join(CSRC, "avr_k1p.h"), os.path.join(CSRC, "avr_tables.h"), os.path.join(CSRC, "avr_div.h")]
-    if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, "-o", SO, SRC], check=True)
-    lib = ctypes.CDLL(SO)
-    lib.k1p_emul_encode_resolved.restype = ctypes.c_size_t
-    lib.div_emul_check.restype = ctypes.c_uint64
-    lib.div_emul_check.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    return build_emul()
+
+
+@pytest.fixture(scope="module", params=OTHER_CHUNK_BINS)
+def emul_other(request):
+    lib = build_emul(request.param)
+    lib.k1p_emul_set_max_stretch(ctypes.c_uint32(0xFFFFFFFF))
+    lib.chunk_bins = request.param                           # k1p() then also counts the stretches: see active_stretches
     return lib
 
 
@@ -34,6 +56,15 @@ def aligned(n):
     a = np.zeros(n + 64, np.uint8)
     o = (-a.ctypes.data) % 16
     return a[o:o + n + 16]
+
+
+def active_stretches(codes, chunk_bins):
+    """How many chunks of `chunk_bins` resolved codes open a stretch: chunk 0, and every later one that holds a coded LPS (a code with
+    symbol ((c >> 1) ^ c) & 1 set that is no bypass bin, avr_k1p.h).  The bytes alone do not tell the chunk length the emulation cut
+    the slice at -- any length gives the same bytes when every use of it agrees -- so the builds at other lengths are held to this."""
+    c = np.asarray(codes, np.uint32)
+    lps = ((((c >> 1) ^ c) & 1) == 1) & ((c >> 1) != 126)
+    return 1 + sum(bool(lps[i:i + chunk_bins].any()) for i in range(chunk_bins, c.size, chunk_bins))
 
 
 def k1p(emul, recs, states):
@@ -49,10 +80,12 @@ def k1p(emul, recs, states):
     out = np.zeros(recs.size + 64, np.uint8)
     info = np.zeros(8, np.uint32)
     n = emul.k1p_emul_encode_resolved(P(res), ctypes.c_size_t(m.value), P(out), ctypes.c_size_t(out.size), P(info))
+    if getattr(emul, "chunk_bins", None):
+        assert info[0] == active_stretches(res[:m.value], emul.chunk_bins), (info, emul.chunk_bins)
     return out[:n].tobytes(), st.tobytes(), info
 
 
-def test_golden_vectors(emul):
+def check_golden_vectors(emul):
     g = np.load(os.path.join(ROOT, "tests", "golden", "g3_cabac.npz"), allow_pickle=False)
     for i in range(int(g["n_cases"])):
         data, final, info = k1p(emul, g[f"recs_{i}"], g[f"states_{i}"])
@@ -60,9 +93,17 @@ def test_golden_vectors(emul):
         assert data == g[f"bytes_{i}"].tobytes() and final == g[f"final_{i}"].tobytes(), f"case {i}"
 
 
-def test_random_streams_many_chunks(emul, oracle):
+def test_golden_vectors(emul):
+    check_golden_vectors(emul)
+
+
+def test_golden_vectors_at_other_chunk_lengths(emul_other):
+    check_golden_vectors(emul_other)
+
+
+def check_random_streams(emul, oracle, count):
     rng = np.random.default_rng(31)
-    for t in range(250):
+    for t in range(count):
         n = int(rng.integers(0, 12000))
         nctx = int(rng.integers(1, 120))
         recs, states = oracle_lib.random_cabac_stream(rng, n, nctx, terminate=bool(t % 3))
@@ -71,6 +112,14 @@ def test_random_streams_many_chunks(emul, oracle):
         want = oracle.cabac_encode(recs, states)
         data, final, info = k1p(emul, recs, states)
         assert info[3] == 0 and (data, final) == want[:2], f"stream {t} n={n} info={info}"
+
+
+def test_random_streams_many_chunks(emul, oracle):
+    check_random_streams(emul, oracle, 250)
+
+
+def test_random_streams_at_other_chunk_lengths(emul_other, oracle):
+    check_random_streams(emul_other, oracle, 100)
 
 
 def test_hard_shapes(emul, oracle):
@@ -151,8 +200,7 @@ def test_fp64_division_of_the_recoded_coder_is_exact(emul):
     assert emul.div_emul_check(7, 200000) == 0
 
 
-@pytest.mark.parametrize("end", ["carry", "none", "cut"])
-def test_long_carry_chains(emul, oracle, end):
+def check_long_carry_chains(emul, oracle, end):
     """Chains of 30 .. 20 000 16-bit digits (tests/carry_streams.py) -- past one of phase D's 33-digit segments, one of its
     8 448-digit tiles, two tiles -- that one carry turns from 0xff to 0x00 ("carry"), that stay 0xff ("none") or that
     finish() decides ("cut"): exact bytes and final states, and none of them declined."""
@@ -163,6 +211,16 @@ def test_long_carry_chains(emul, oracle, end):
         data, final, info = k1p(emul, recs, st)
         assert info[3] == 0 and (data, final) == want[:2], f"chain {n_chain} {end} info={info}"
         assert carry_streams.longest_run(data, 0 if end == "carry" else data[2 * (3 + 40 * k) + 8])[1] >= 2 * (n_chain - 3)
+
+
+@pytest.mark.parametrize("end", ["carry", "none", "cut"])
+def test_long_carry_chains(emul, oracle, end):
+    check_long_carry_chains(emul, oracle, end)
+
+
+@pytest.mark.parametrize("end", ["carry", "none", "cut"])
+def test_long_carry_chains_at_other_chunk_lengths(emul_other, oracle, end):
+    check_long_carry_chains(emul_other, oracle, end)
 
 
 def test_long_carry_chain_without_lps_is_declined(emul, oracle):

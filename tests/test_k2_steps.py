@@ -12,7 +12,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.join(ROOT, "tests")
 CSRC = os.path.join(ROOT, "avrecode-ms_amd", "csrc")
-DEPS = [os.path.join(TESTS, f) for f in ("k2_steps_cases.h", "k2_steps_run.h")] + [os.path.join(CSRC, f) for f in ("avr_div.h", "avr_k2p.h")]
+DEPS = [os.path.join(TESTS, f) for f in ("k2_steps_cases.h", "k2_steps_run.h")] + [os.path.join(CSRC, f) for f in ("avr_div.h", "avr_k2p.h", "avr_chunk.h")]
 HOST_SRC, HOST_BIN = os.path.join(TESTS, "k2_steps_host.cpp"), os.path.join(TESTS, "_k2_steps_host")
 DEV_SRC, DEV_BIN = os.path.join(TESTS, "k2_steps_dev.hip"), os.path.join(TESTS, "_k2_steps_dev")
 CHECKS = 5

@@ -19,7 +19,7 @@ SO = os.path.join(ROOT, "tests", "_k2p_emul.so")
 
 @pytest.fixture(scope="module")
 def emul():
-    deps = [SRC, os.path.join(CSRC, "avr_k2p.h")]
+    deps = [SRC, os.path.join(CSRC, "avr_k2p.h"), os.path.join(CSRC, "avr_chunk.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, "-o", SO, SRC], check=True)
     lib = ctypes.CDLL(SO)

@@ -85,7 +85,7 @@ RECORDED = {
 @pytest.fixture(scope="module")
 def layouts():
     """{shape: {layout: [offsets ..., total]}} and the sizeofs, from the stand-alone program."""
-    deps = [SRC, os.path.join(CSRC, "avr_layout.h"), os.path.join(CSRC, "avr_k1p.h")]
+    deps = [SRC, os.path.join(CSRC, "avr_layout.h"), os.path.join(CSRC, "avr_k1p.h"), os.path.join(CSRC, "avr_chunk.h")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I" + CSRC, "-o", EXE, SRC], check=True)
     shapes = grid()

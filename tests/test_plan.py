@@ -38,7 +38,7 @@ def batches():
 @pytest.fixture(scope="module")
 def plan_check():
     """run(text) -> the stand-alone program's output lines."""
-    deps = [SRC] + [os.path.join(CSRC, h) for h in ("avr_plan.h", "avr_layout.h", "avr_k1p.h")]
+    deps = [SRC] + [os.path.join(CSRC, h) for h in ("avr_plan.h", "avr_layout.h", "avr_k1p.h", "avr_chunk.h")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I" + CSRC, "-o", EXE, SRC], check=True)
     return lambda text: subprocess.run([EXE], input=text, capture_output=True, text=True, check=True).stdout.split("\n")

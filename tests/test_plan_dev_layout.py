@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "avrecode-ms_amd", "csrc")
 CHECK_SRC = os.path.join(ROOT, "tests", "plan_dev_layout_check.cpp")
 CHECK_BIN = os.path.join(ROOT, "tests", "_plan_dev_layout_check")
-DEPS = [os.path.join(CSRC, h) for h in ("avr_plan_dev.h", "avr_layout.h", "avr_k1p.h")] + [os.path.join(ROOT, "include", "avrecode_ms_amd.h")]
+DEPS = [os.path.join(CSRC, h) for h in ("avr_plan_dev.h", "avr_layout.h", "avr_k1p.h", "avr_chunk.h")] + [os.path.join(ROOT, "include", "avrecode_ms_amd.h")]
 
 
 def _stale(target, sources):

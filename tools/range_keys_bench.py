@@ -24,7 +24,9 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-WINDOW_CHUNKS, CHUNK_BINS, ROW_BYTES = 16, 1024, 1028 * 6
+from avrecode_ms_amd import CHUNK_BINS  # noqa: E402  (AVR_CHUNK_BINS)
+
+WINDOW_CHUNKS, ROW_BYTES = 16, 1028 * 6
 
 
 def spanning_bins(n_bins, group_first):
