@@ -42,7 +42,7 @@ CHUNK_BINS, SORT_BLOCK_BINS = 1024, 4096
 
 _SOURCES = ["avr_kernels.hip", "avr_k1p.hip", "avr_k2p.hip", "avr_est.hip", "avr_est_verify.hip", "avr_verify.hip", "avr_cabac_verify.hip", "avr_restore.hip", "avr_plan_dev.hip", "avr_api.cpp", "avr_multi.cpp"]
 _DEPS = _SOURCES + ["avr_coder.h", "avr_est.h", "avr_div.h", "avr_internal.h", "avr_chunk.h", "avr_k1p.h", "avr_k2p.h", "avr_layout.h", "avr_plan.h", "avr_synth.h", "avr_tables.h",
-                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h", "avr_plan_dev.h", "avr_multi.h"]
+                    "avr_verify.h", "avr_cabac_verify.h", "avr_est_verify.h", "avr_restore.h", "avr_finish.h", "avr_plan_dev.h", "avr_multi.h"]
 
 
 class AvrError(RuntimeError):
@@ -282,6 +282,9 @@ SIGNATURES = {
     "avr_plan_tiles_device": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "avr_chunk_plan_from": (c_int, [c_void_p, c_void_p, c_void_p]),
     "avr_compact_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_void_p, c_void_p, c_size_t]),
+    "avr_finish_workspace_bytes": (c_size_t, [c_size_t]),
+    "avr_finish_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
+                                  c_size_t]),
     "avr_context_census_device": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_void_p]),
     "avr_context_remap_device": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_void_p]),
     "avr_states_permute_device": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
@@ -739,11 +742,12 @@ class MultiBatch:
         return out.tolist()
 
 
-from .device import (DeviceWorkload, chunk_plan_arrays_device, compact_device, device_plan, encode_tiles, plan_tiles,  # noqa: E402
-                     plan_tiles_device, synth_config)  # noqa: E402  (torch-backed helpers)
+from .device import (DeviceWorkload, chunk_plan_arrays_device, compact_device, device_plan, encode_tiles, finish_device, finish_word,  # noqa: E402
+                     plan_tiles, plan_tiles_device, synth_config)  # noqa: E402  (torch-backed helpers)
 
 __all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS",
            "SEL_BYPASS", "SEL_TERMINATE", "SLICE_VERIFY_FAILED", "VERIFY_NONE", "EXPECT_NONE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
            "make_cabac_records", "make_range_records", "plan_tiles", "plan_tiles_device", "chunk_plan_arrays_device", "compact_device",
+           "finish_device", "finish_word",
            "device_plan", "synth_config", "tail_patch"]

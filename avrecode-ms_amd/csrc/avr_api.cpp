@@ -1542,6 +1542,26 @@ int avr_compact_device(int device, void *stream, const uint8_t *out, const uint6
     return AVR_OK;
 }
 
+// ------------------------------------------------------------------ the epilogue on the device (avr_plan_dev.hip, avr_finish.h)
+
+size_t avr_finish_workspace_bytes(size_t n_slices) { return size_t(avr::plan_dev::finish_layout(n_slices).total); }
+
+int avr_finish_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const int32_t *status,
+                      size_t n_slices, const uint32_t *finish, uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off, void *workspace,
+                      size_t workspace_bytes) {
+    if (!dense_off) return fail(AVR_ERR_INVALID, "null dense_off");
+    if (n_slices > 0x7fffffffu) return fail(AVR_ERR_INVALID, "n_slices %zu out of range", n_slices);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) return fail(AVR_ERR_INVALID, "workspace null or not 256-byte aligned");
+    if (workspace_bytes < avr_finish_workspace_bytes(n_slices))
+        return fail(AVR_ERR_INVALID, "workspace of %zu bytes, avr_finish_workspace_bytes says %zu", workspace_bytes, avr_finish_workspace_bytes(n_slices));
+    if (n_slices && (!out || !out_off || !out_len || !finish || (!dense && dense_capacity))) return fail(AVR_ERR_INVALID, "null device pointer");
+    if (misaligned(out_off, 8) || misaligned(out_len, 4) || misaligned(status, 4) || misaligned(finish, 4) || misaligned(dense_off, 8))
+        return fail(AVR_ERR_INVALID, "misaligned array");
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_finish(hip(stream), out, out_off, out_len, status, uint32_t(n_slices), finish, dense, dense_capacity, dense_off, workspace));
+    return AVR_OK;
+}
+
 // ------------------------------------------------------------------ dense context ids
 
 int avr_context_census_device(int device, void *stream, const uint16_t *recs, uint64_t n_records, uint32_t *bitmap) {

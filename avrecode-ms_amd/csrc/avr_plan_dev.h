@@ -94,6 +94,18 @@ inline CompactLayout compact_layout(size_t n_slices) {
     return L;
 }
 
+// avr_finish_device: the slices' final lengths (64 bits each, pass 1 writes them, the scan reads them), then the scan's sums.  A quote
+// of its own (avr_finish_workspace_bytes): avr_plan_workspace_bytes stays what it was.
+struct FinishLayout { uint64_t lens, sums, total; };
+inline FinishLayout finish_layout(size_t n_slices) {
+    FinishLayout L;
+    Cursor c;
+    L.lens = c.take(uint64_t(n_slices) * 8);
+    L.sums = c.take(scan_levels(n_slices, 8).bytes);
+    L.total = std::max<uint64_t>(c.at, 256);
+    return L;
+}
+
 inline uint64_t workspace_bytes(size_t n_slices) {
     return std::max(std::max(chunks_layout(n_slices).total, tiles_layout(n_slices).total), std::max<uint64_t>(compact_layout(n_slices).total, 256));
 }
@@ -113,6 +125,9 @@ hipError_t launch_plan_tiles(hipStream_t s, const uint32_t *n_bins, uint32_t n_s
                              uint64_t *tile_off, void *ws, avr_plan_totals *totals);
 hipError_t launch_compact_wide(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, uint32_t n_slices,
                                uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off, void *ws);
+// `ws`: finish_layout(n_slices).total bytes; status: null or n_slices words; finish: n_slices words (AVR_FINISH_WORD)
+hipError_t launch_finish(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const int32_t *status,
+                         uint32_t n_slices, const uint32_t *finish, uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off, void *ws);
 #endif
 
 }  // namespace avr

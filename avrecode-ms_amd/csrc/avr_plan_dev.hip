@@ -1,7 +1,7 @@
 // The device planner for gfx950 (MI355X): a batch's plan from lengths that lie in HBM, and its coded bytes compacted, with no host
-// round trip (avr_plan_chunks_device, avr_plan_tiles_device, avr_compact_device; layouts and bounds in avr_plan_dev.h).  The per-slice
-// rules are avr_plan.h's own functions.  Four kernels' worth of ideas, none of which lets a workgroup wait on another workgroup of
-// its launch: every dependence between workgroups is a kernel boundary on the caller's stream.
+// round trip (avr_plan_chunks_device, avr_plan_tiles_device, avr_compact_device, avr_finish_device; layouts and bounds in
+// avr_plan_dev.h).  The per-slice rules are avr_plan.h's own functions.  Five kernels' worth of ideas, none of which lets a workgroup
+// wait on another workgroup of its launch: every dependence between workgroups is a kernel boundary on the caller's stream.
 //
 //   scan      k_reduce / k_apply   an exclusive prefix sum over Q 64-bit quantities at once (the chunk plan sums seven per slice in one
 //             sweep).  A workgroup of 256 threads takes 1024 entries, four to a thread: the threads' sums are scanned inside each wave by
@@ -23,11 +23,19 @@
 //   copy      k_compact_wide       a wave per slice: the destination is brought to an 8-byte boundary by up to seven single bytes, the
 //             body goes in 8-byte words (aligned stores; aligned loads of the two source words a destination word straddles, funnel
 //             shifted), up to seven bytes finish.  A wave's body step is 512 contiguous bytes on both sides.
+//   finish    k_finish_lengths / k_finish_copy   avr_finish_device: the copy with the decompressor's epilogue in it (avr_finish.h: stop
+//             byte, tail patch, emulation prevention).  Escaping changes lengths, so they are a pass of their own, a wave per slice: a
+//             lane makes of its 8-byte word a map from the escape rule's three entry states to (exit state, escapes), the wave composes
+//             the maps in lane order by shuffles and carries state and count from trip to trip.  The scan above makes dense_off of the
+//             lengths; the second pass walks again, each lane knowing its entry state and the escapes in front of it, and stores an
+//             escaped slice by bytes -- a slice without escapes goes the wide copy's way, the word with the special byte through
+//             patched_word.
 //
 // Resource use by the compiler's report (-Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md, "Planning on the device".
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "avr_finish.h"
 #include "avr_internal.h"
 #include "avr_plan.h"
 #include "avr_plan_dev.h"
@@ -381,6 +389,116 @@ __global__ __launch_bounds__(256) void k_compact_wide(const uint8_t *out, const 
     if (lane < tail) dst[head + 8 * words + lane] = src[head + 8 * words + lane];
 }
 
+// ------------------------------------------------------------------ the epilogue: compaction with the tail patch and the escapes
+
+struct FinishIn {
+    const uint8_t *out;
+    const uint64_t *out_off;
+    const uint32_t *out_len;
+    const int32_t *status;                                       // or null: every slice is sound
+    const uint32_t *finish;
+};
+
+struct FinishSlice {
+    const uint64_t *base;                                        // the aligned word that holds the slice's first byte
+    uint32_t skew, word;
+    finish::Shape shape;
+};
+
+// false: the slice gives no bytes.  The same for a wave's 64 lanes.
+__device__ inline bool finish_slice(const FinishIn &in, uint32_t slice, FinishSlice &f) {
+    if (in.status && in.status[slice] != AVR_SLICE_OK) return false;
+    const uint64_t cap = in.out_off[slice + 1] - in.out_off[slice], len = in.out_len[slice];
+    const uint32_t L = uint32_t(len < cap ? len : cap);
+    const uint8_t *src = in.out + in.out_off[slice];
+    f.word = in.finish[slice];
+    f.shape = finish::shape_of(L, L ? src[L - 1] : 0u, f.word);
+    f.skew = uint32_t(reinterpret_cast<uintptr_t>(src) & 7u);
+    f.base = reinterpret_cast<const uint64_t *>(src - f.skew);
+    return true;
+}
+
+__device__ inline finish::Xfer shfl_up_xfer(const finish::Xfer &x, uint32_t d) {
+    return finish::Xfer{uint32_t(__shfl_up(int(x.exit), d, 64)), uint32_t(__shfl_up(int(x.cnt), d, 64))};
+}
+
+// One walk over a slice's patched bytes, a word per lane and 512 bytes per trip: the lanes' runs composed in lane order, the state
+// and the escapes carried from trip to trip.  kWrite: every lane escapes its run to where it belongs in dst[0, end).  Returns the
+// slice's escapes; every lane of the wave calls it.
+template <bool kWrite>
+__device__ inline uint64_t finish_walk(const FinishSlice &f, uint32_t lane, uint8_t *dst, uint64_t end) {
+    uint32_t z = finish::zeros_before(f.word);
+    uint64_t escapes = 0;
+    const uint64_t R = f.shape.R;
+    for (uint64_t k0 = 0; k0 < R; k0 += finish::kTripBytes) {   // the same trip count for every lane
+        const uint64_t k = k0 + 8u * lane;
+        const uint32_t n = k < R ? (R - k < 8 ? uint32_t(R - k) : 8u) : 0u;
+        const uint64_t word = n ? finish::patched_word(f.base, f.skew, k, f.shape) : 0;
+        finish::Xfer inc = finish::run_of(word, n);
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const finish::Xfer front = shfl_up_xfer(inc, d);
+            if (lane >= d) inc = finish::then(front, inc);
+        }
+        finish::Xfer ex = shfl_up_xfer(inc, 1);
+        if (lane == 0) ex = finish::identity();
+        if (kWrite) finish::emit_run(word, n, finish::exit_of(ex, z), dst, k + escapes + finish::count_of(ex, z), end);
+        const finish::Xfer all{uint32_t(__shfl(int(inc.exit), 63, 64)), uint32_t(__shfl(int(inc.cnt), 63, 64))};
+        escapes += finish::count_of(all, z);
+        z = finish::exit_of(all, z);
+    }
+    return escapes;
+}
+
+// pass 1: lens[slice] = the bytes slice gives in the end
+__global__ __launch_bounds__(256) void k_finish_lengths(FinishIn in, uint32_t n_slices, uint64_t *lens) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t slice = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (slice >= n_slices) return;
+    FinishSlice f;
+    uint64_t len = 0;
+    if (finish_slice(in, slice, f))
+        len = finish::final_length(f.shape, AVR_FINISH_ESCAPE(f.word) ? finish_walk<false>(f, lane, nullptr, 0) : 0);
+    if (lane == 0) lens[slice] = len;
+}
+
+// pass 2: a slice without escapes goes as k_compact_wide's slices go, the word that holds the special byte through patched_word; an
+// escaped one by bytes
+__global__ __launch_bounds__(256) void k_finish_copy(FinishIn in, uint32_t n_slices, uint8_t *dense, uint64_t dense_capacity, const uint64_t *dense_off) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t slice = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (slice >= n_slices) return;
+    const uint64_t d0 = dense_off[slice], d1 = dense_off[slice + 1], len = d1 - d0;
+    if (len == 0 || d1 > dense_capacity || d1 < d0) return;      // a slice is written whole or not at all
+    FinishSlice f;
+    if (!finish_slice(in, slice, f)) return;
+    uint8_t *dst = dense + d0;
+    if (AVR_FINISH_ESCAPE(f.word)) {
+        finish_walk<true>(f, lane, dst, len);
+        return;
+    }
+    const uint64_t to_word = (8u - uint32_t(reinterpret_cast<uintptr_t>(dst) & 7u)) & 7u, head = to_word < len ? to_word : len;
+    if (lane < head) dst[lane] = uint8_t(finish::patched_word(f.base, f.skew, 0, f.shape) >> (8 * lane));
+    const uint64_t words = (len - head) >> 3, tail = (len - head) & 7u;
+    uint64_t *d = reinterpret_cast<uint64_t *>(dst + head);
+    // The words that lie whole in front of the special byte and of the slice's end go as k_compact_wide's do; the one behind them, if
+    // there is one, through patched_word.
+    const uint64_t plain = finish::plain_words(f.shape, head, words);
+    const uint8_t *s = reinterpret_cast<const uint8_t *>(f.base) + f.skew + head;
+    const uint32_t skew = uint32_t(reinterpret_cast<uintptr_t>(s) & 7u);
+    const uint64_t *sw = reinterpret_cast<const uint64_t *>(s - skew);    // every word read below holds a byte of the slice
+    if (skew == 0) {
+#pragma unroll 4
+        for (uint64_t w = lane; w < plain; w += 64) d[w] = sw[w];
+    } else {
+        const uint32_t down = 8 * skew, up = 64 - down;
+#pragma unroll 4
+        for (uint64_t w = lane; w < plain; w += 64) d[w] = sw[w] >> down | sw[w + 1] << up;
+    }
+    for (uint64_t w = plain + lane; w < words; w += 64) d[w] = finish::patched_word(f.base, f.skew, head + 8 * w, f.shape);
+    if (lane < tail) dst[head + 8 * words + lane] = uint8_t(finish::patched_word(f.base, f.skew, head + 8 * words, f.shape) >> (8 * lane));
+}
+
 }  // namespace plan_dev
 
 using namespace plan_dev;
@@ -433,6 +551,20 @@ hipError_t launch_compact_wide(hipStream_t s, const uint8_t *out, const uint64_t
     const CompactLayout L = compact_layout(n_slices);
     if (hipError_t e = scan<1>(s, LenSrc{out_off, out_len}, LenSink{dense_off}, n_slices, static_cast<uint8_t *>(ws) + L.sums); e != hipSuccess) return e;
     return launch_compact(s, OutputView{out, out_off}, dense_off, n_slices, dense, dense_capacity);
+}
+
+// the lengths behind the patch and the escapes, their prefix sums, the bytes: three steps on `s`, each behind the one before
+hipError_t launch_finish(hipStream_t s, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, const int32_t *status,
+                         uint32_t n_slices, const uint32_t *finish, uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off, void *ws) {
+    const FinishLayout L = finish_layout(n_slices);
+    uint8_t *w = static_cast<uint8_t *>(ws);
+    uint64_t *lens = reinterpret_cast<uint64_t *>(w + L.lens);
+    const FinishIn in{out, out_off, out_len, status, finish};
+    const dim3 grid((n_slices + 3u) / 4u), block(256);
+    if (n_slices) hipLaunchKernelGGL(k_finish_lengths, grid, block, 0, s, in, n_slices, lens);
+    if (hipError_t e = scan<1>(s, ArraySrc<1>{reinterpret_cast<const Vec<1> *>(lens)}, LenSink{dense_off}, n_slices, w + L.sums); e != hipSuccess) return e;
+    if (n_slices) hipLaunchKernelGGL(k_finish_copy, grid, block, 0, s, in, n_slices, dense, dense_capacity, dense_off);
+    return hipGetLastError();
 }
 
 }  // namespace avr

@@ -41,19 +41,29 @@ struct Shape {
     uint32_t last;                                               // that byte
 };
 
-// out_tail: out[L - 1] (unused for L == 0); exp_tail: exp[E - 1] (unused for E < 2)
-AVR_DIV_HD Shape make_shape(uint32_t L, uint32_t E, uint32_t out_tail, uint32_t exp_tail) {
+// The rule from the two facts the container carries, where it carries them (`patch`): the parity of the payload's length and its last
+// byte.  out_tail: out[L - 1] (unused for L == 0).  Nothing is expected here: E and n are 0.  (avr_finish.h copies by this shape.)
+AVR_DIV_HD Shape tail_shape(uint32_t L, uint32_t out_tail, bool patch, uint32_t parity, uint32_t last) {
     Shape s;
     s.L = L;
-    s.E = E;
+    s.E = 0;
     const uint64_t L1 = L > 0 && (out_tail & 0xffu) == 0x80u ? uint64_t(L) - 1 : uint64_t(L);      // finish
     s.R = L1;
     s.at = kNoByte;
-    s.last = exp_tail & 0xffu;
-    if (E >= 2) {                                                // the tail patch
-        if ((L1 & 1) != (uint64_t(E) & 1)) { s.at = L1; s.R = L1 + 1; }
+    s.last = last & 0xffu;
+    if (patch) {                                                 // the tail patch
+        if ((L1 & 1) != (parity & 1)) { s.at = L1; s.R = L1 + 1; }
         else if (L1 > 0) s.at = L1 - 1;
     }
+    s.n = 0;
+    return s;
+}
+
+// ... and from the expected payload, as the compressor derives the two facts: both only for E >= 2.
+// out_tail: out[L - 1] (unused for L == 0); exp_tail: exp[E - 1] (unused for E < 2)
+AVR_DIV_HD Shape make_shape(uint32_t L, uint32_t E, uint32_t out_tail, uint32_t exp_tail) {
+    Shape s = tail_shape(L, out_tail, E >= 2, E & 1u, exp_tail);
+    s.E = E;
     s.n = s.R < s.E ? s.R : s.E;
     return s;
 }

@@ -327,7 +327,37 @@ struct Block {                                          // recode.proto:10-17
     bool has_cabac = false;          std::string cabac;
     bool has_length_parity = false;  bool length_parity = false;
     bool has_last_byte = false;      std::string last_byte;
+    bool has_escaped = false;        bool escaped = false;   // field 7, not in recode.proto: see escape() below
 };
+
+// Emulation prevention (H.264 7.4.1) over a coded payload that has z zero bytes (0, 1 or 2) directly in front of it in the NAL unit:
+// s = z; for every byte b: where s == 2 and b <= 3, 0x03 goes in front of it and s = 0; then s = b == 0 ? s + 1 : 0.  The rule about
+// a zero at the end of a NAL unit is not part of it: a coded payload ends on the byte with the stop bit.
+//
+// An ESCAPED block (field 7 = 1) is a coded block whose payload lies in the file in this form.  Its `size` is the escaped length --
+// the surrogate must fill the payload's place, an MP4's length prefixes being part of the literals -- while length_parity and
+// last_byte are the unescaped payload's: the tail patch works before escaping.  z is never stored: in a conforming stream it is the
+// number of zero bytes directly in front of the payload, capped at 2, which the compressor reads from the file and the decompressor
+// from the bytes it has assembled.  Such a block carries skip_coded = false beside cabac, on purpose: a reader that does not know
+// field 7 (this one before it did, the reference) counts two kinds on the block and ends with "Invalid input block: must have exactly
+// one type", where without it it would restore the unescaped bytes in silence.
+inline std::string escape(const uint8_t *p, size_t n, int z) {
+    std::string out;
+    out.reserve(n + n / 64 + 2);
+    int s = z;
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t b = p[i];
+        if (s == 2 && b <= 3) { out.push_back(char(3)); s = 0; }
+        out.push_back(char(b));
+        s = b == 0 ? s + 1 : 0;
+    }
+    return out;
+}
+inline int zeros_before(const std::string &bytes, size_t at) {          // the zero bytes directly in front of bytes[at], capped at 2
+    int z = 0;
+    while (z < 2 && at > size_t(z) && bytes[at - 1 - size_t(z)] == 0) z++;
+    return z;
+}
 
 // Recoded.metadata (recode.proto: optional Metadata metadata = 1, whose own sub-fields 1-4 nobody writes) carries, when the writer is
 // asked for it, two sub-fields the reference's schema does not define: 5 = original_sha256 (bytes, exactly 32: the SHA-256 of the
@@ -369,6 +399,7 @@ struct Recoded {
             if (b.has_cabac) put_bytes(m, 4, b.cabac);
             if (b.has_length_parity) { put_varint(m, 5 << 3 | 0); put_varint(m, b.length_parity); }
             if (b.has_last_byte) put_bytes(m, 6, b.last_byte);
+            if (b.has_escaped) { put_varint(m, 7 << 3 | 0); put_varint(m, b.escaped); }
             put_bytes(out, 2, m);
         }
         return out;
@@ -399,7 +430,7 @@ struct Recoded {
             if (!get_varint(p, end, &tag)) return false;
             const int field = int(tag >> 3), wire = int(tag & 7);
             const bool bytes_field = field == 2 || field == 4 || field == 6;
-            if (field >= 1 && field <= 6 && wire == (bytes_field ? 2 : 0)) {
+            if (field >= 1 && field <= 7 && wire == (bytes_field ? 2 : 0)) {
                 if (!get_varint(p, end, &v)) return false;
                 if (bytes_field) {
                     if (uint64_t(end - p) < v) return false;
@@ -410,7 +441,8 @@ struct Recoded {
                     else { b->has_last_byte = true; b->last_byte = s; }
                 } else if (field == 1) { b->has_size = true; b->size = int64_t(v); }
                 else if (field == 3) { b->has_skip_coded = true; b->skip_coded = v != 0; }
-                else { b->has_length_parity = true; b->length_parity = v != 0; }
+                else if (field == 5) { b->has_length_parity = true; b->length_parity = v != 0; }
+                else { b->has_escaped = true; b->escaped = v != 0; }
             } else if (!skip_field(p, end, wire)) {
                 return false;
             }
@@ -471,14 +503,18 @@ struct Recoded {
 // the block's sequence number written with SURROGATE_MARKER_BYTES base-255 digits, least significant first,
 // each stored + 1: no zero byte, so no start code or emulation prevention can arise inside it.
 constexpr int SURROGATE_MARKER_BYTES = 8;               // recode.cpp:33
-inline std::string next_surrogate_marker(uint64_t *sequence_number) {
+// The surrogate of an ESCAPED block may follow two zero bytes where the payload began with a byte <= 3 (its first byte then stands in
+// the place of the 0x03): a marker byte of 1 would end the NAL unit there, one of 3 would be taken out as an escape.  Its marker
+// (above_3) is written with base-252 digits stored + 4 instead.  No block of the reference's format gets one.
+inline std::string next_surrogate_marker(uint64_t *sequence_number, bool above_3 = false) {
     uint64_t value = *sequence_number;
     *sequence_number += 1;
+    const uint64_t base = above_3 ? 252 : 255, first = above_3 ? 4 : 1;
     std::string marker;
     marker.reserve(SURROGATE_MARKER_BYTES);
     while (marker.size() < size_t(SURROGATE_MARKER_BYTES)) {
-        marker.push_back(char(value % 255 + 1));
-        value /= 255;
+        marker.push_back(char(value % base + first));
+        value /= base;
     }
     return marker;
 }

@@ -208,7 +208,13 @@ class compressor {                                       // recode.cpp:1109-1316
     // (avr_host.h: Metadata), for decompressor::finish to hold the restored file to.  Off, the container is byte for byte what it is
     // without this call; on, it is those bytes behind the metadata field.
     void set_digest(bool on) { digest_ = on; }
-    struct restore_slice { std::vector<uint8_t> codes; size_t payload_at, payload_size; };   // the payload: original[payload_at .. + payload_size)
+    // Escaped slices: where the payload the parser hands over is not in the file as it is, its escaped forms (avr_host.h: escape)
+    // are looked for, and a hit becomes an ESCAPED coded block (field 7) where the slice is a skip_coded block otherwise.  Before
+    // prepare().  Off, every container is byte for byte what it is without this call.
+    void set_escaped(bool on) { escaped_ = on; }
+    // the payload: original[payload_at .. + payload_size) -- in its escaped form where `unescaped` holds the payload itself, which is
+    // then what the restore check expects (the file's form is held to escape() of it by the search that found it)
+    struct restore_slice { std::vector<uint8_t> codes; size_t payload_at, payload_size; std::string unescaped; };
     std::vector<restore_slice> &restore_slices() { return restore_pending_; }
     const std::string &original() const { return original_; }
     size_t restore_bins() const { size_t bins = 0; for (auto &p : restore_pending_) bins += p.codes.size(); return bins; }
@@ -217,7 +223,10 @@ class compressor {                                       // recode.cpp:1109-1316
         for (auto &p : restore_pending_) {
             const int idx = avr_batch_add_slice_codes(b, p.codes.data(), p.codes.size());
             gpu_check(idx);
-            gpu_check(avr_batch_expect(b, size_t(idx), reinterpret_cast<const uint8_t *>(original_.data()) + p.payload_at, p.payload_size));
+            if (p.unescaped.empty())
+                gpu_check(avr_batch_expect(b, size_t(idx), reinterpret_cast<const uint8_t *>(original_.data()) + p.payload_at, p.payload_size));
+            else
+                gpu_check(avr_batch_expect(b, size_t(idx), reinterpret_cast<const uint8_t *>(p.unescaped.data()), p.unescaped.size()));
             if (first_in_restore_batch_ < 0) first_in_restore_batch_ = idx;
             std::vector<uint8_t>().swap(p.codes);        // the batch has its copy
         }
@@ -300,19 +309,23 @@ class compressor {                                       // recode.cpp:1109-1316
         cabac_decoder(compressor *c, const uint8_t *buf, int size) : c_(c), decoder_(buf, size) {
             block_ = c->find_next_coded_block_and_emit_literal(buf, size);
             if (block_ < 0) return;                      // skipped: hooks off for this slice (:1146-1152)
-            c->out_.block[block_].has_size = true;       // :1154
-            c->out_.block[block_].size = size;
+            Block &blk = c->out_.block[block_];
+            if (!blk.has_size) {                         // :1154 (an escaped block has its size, the escaped length, from the search)
+                blk.has_size = true;
+                blk.size = size;
+            }
             recorder_.reset(new compress_recorder(&c->model_, c->device_estimators_));   // :1161-1163
             if (c->restore_check_) {                     // the payload was just found in the file: it ends where the next search begins
                 restore_ = true;
-                payload_at_ = size_t(c->prev_coded_block_end_) - size_t(size);
-                payload_size_ = size_t(size);
+                payload_size_ = size_t(blk.size);
+                payload_at_ = size_t(c->prev_coded_block_end_) - payload_size_;
+                if (blk.has_escaped) unescaped_.assign(reinterpret_cast<const char *>(buf), size_t(size));
             }
         }
         ~cabac_decoder() {
             if (!recorder_) return;
             c_->pending_.push_back({block_, recorder_->records()});
-            if (restore_) c_->restore_pending_.push_back({std::move(codes_), payload_at_, payload_size_});
+            if (restore_) c_->restore_pending_.push_back({std::move(codes_), payload_at_, payload_size_, std::move(unescaped_)});
         }
         bool hooked() const { return block_ >= 0; }
         int get(uint8_t *state) {                        // :1182-1186
@@ -347,6 +360,7 @@ class compressor {                                       // recode.cpp:1109-1316
         bool restore_ = false;                           // the restore check is on: the resolved codes and the payload's place are kept
         std::vector<uint8_t> codes_;
         size_t payload_at_ = 0, payload_size_ = 0;
+        std::string unescaped_;                          // an escaped slice's payload, kept for the restore check
     };
 
     h264_model *get_model() { return &model_; }          // :1276-1278
@@ -363,9 +377,23 @@ class compressor {                                       // recode.cpp:1109-1316
     int find_next_coded_block_and_emit_literal(const uint8_t *buf, int size) {
         const size_t window_begin = size_t(prev_coded_block_end_), window_end = size_t(read_offset_);
         size_t where = std::string::npos;
+        int in_file = size;                              // the payload's length in the file: more than `size` where it lies there escaped
         if (size >= SURROGATE_MARKER_BYTES && (!decoder_ || decoder_->payload_decodes())) {
             const void *hit = memmem(original_.data() + window_begin, window_end - window_begin, buf, size_t(size));
             if (hit) where = size_t(static_cast<const char *>(hit) - original_.data());
+            // Not there as it is: in one of its escaped forms, then?  The form for z zero bytes in front of the payload is accepted
+            // only where the file has that many in front of the hit (capped at 2), which is what makes z recoverable on the way back.
+            for (int z = 0; escaped_ && where == std::string::npos && z <= 2; z++) {
+                const std::string form = escape(buf, size_t(size), z);
+                if (form.size() == size_t(size) || form.size() > size_t(INT_MAX)) continue;          // no escape in it: the search above was this one
+                for (size_t from = window_begin; from + form.size() <= window_end; ) {
+                    const void *h = memmem(original_.data() + from, window_end - from, form.data(), form.size());
+                    if (!h) break;
+                    const size_t at = size_t(static_cast<const char *>(h) - original_.data());
+                    if (zeros_before(original_, at) == z) { where = at; in_file = int(form.size()); break; }
+                    from = at + 1;
+                }
+            }
         }
         if (where == std::string::npos) {
             Block skipped;
@@ -387,8 +415,16 @@ class compressor {                                       // recode.cpp:1109-1316
             coded.has_last_byte = true;
             coded.last_byte = std::string(1, char(buf[size - 1]));
         }
+        if (in_file != size) {                           // an escaped block: avr_host.h, escape()
+            coded.has_size = true;
+            coded.size = in_file;
+            coded.has_skip_coded = true;
+            coded.skip_coded = false;
+            coded.has_escaped = true;
+            coded.escaped = true;
+        }
         out_.block.push_back(coded);
-        prev_coded_block_end_ = int(where) + size;
+        prev_coded_block_end_ = int(where) + in_file;
         return int(out_.block.size()) - 1;
     }
 
@@ -413,7 +449,7 @@ class compressor {                                       // recode.cpp:1109-1316
 
     struct pending { int block; std::vector<uint16_t> recs; };
     int first_in_batch_ = -1, first_in_restore_batch_ = -1;
-    bool device_estimators_ = false, verify_ = false, restore_check_ = false, digest_ = false;
+    bool device_estimators_ = false, verify_ = false, restore_check_ = false, digest_ = false, escaped_ = false;
     std::vector<restore_slice> restore_pending_;
     std::string original_;
     int device_;
@@ -438,6 +474,8 @@ class decompressor {                                     // recode.cpp:1319-1598
         bool done = false;
         int8_t length_parity = -1;
         uint8_t last_byte = 0;
+        bool escaped = false;                            // an ESCAPED block: finish() escapes its bytes, which must then be `size` long
+        uint64_t size = 0;
     };
 
   public:
@@ -505,6 +543,12 @@ class decompressor {                                     // recode.cpp:1319-1598
                                                 block.length_parity, block.last_byte);
                 block.out_bytes.resize(n);
             }
+            if (block.escaped) {                         // avr_host.h, escape(): z is what the file so far ends on
+                block.out_bytes = escape(reinterpret_cast<const uint8_t *>(block.out_bytes.data()), block.out_bytes.size(), zeros_before(out, out.size()));
+                if (block.out_bytes.size() != block.size)
+                    throw std::runtime_error("Escaped block restores to " + std::to_string(block.out_bytes.size()) + " bytes, its size says " +
+                                             std::to_string(block.size));
+            }
             out += block.out_bytes;
         }
         check_digest(out);
@@ -539,7 +583,12 @@ class decompressor {                                     // recode.cpp:1319-1598
     std::string open_block(int index) {
         const Block &block = in_.block[size_t(index)];
         block_state &state = blocks_[size_t(index)];
-        const int kinds = (block.has_literal ? 1 : 0) + (block.has_cabac ? 1 : 0) + (block.has_skip_coded ? 1 : 0);
+        // An ESCAPED block (field 7) is a coded block that says skip_coded = false beside its cabac, and that pair is accepted only
+        // with it: a reader that does not know the field stops at the line below.  The field on anything else is refused.
+        const bool escaped = block.has_escaped && block.escaped;
+        if (escaped && !(block.has_cabac && block.has_skip_coded && !block.skip_coded && !block.has_literal))
+            throw std::runtime_error("Invalid input block: escaped without cabac and skip_coded = false");
+        const int kinds = (block.has_literal ? 1 : 0) + (block.has_cabac ? 1 : 0) + (block.has_skip_coded && !escaped ? 1 : 0);
         if (kinds != 1) throw std::runtime_error("Invalid input block: must have exactly one type");
         if (block.has_literal) {
             state.out_bytes = block.literal;
@@ -547,7 +596,7 @@ class decompressor {                                     // recode.cpp:1319-1598
             fed_bytes_ = std::min<uint64_t>(uint64_t(INT_MAX), fed_bytes_ + block.literal.size());
             return block.literal;
         }
-        if (block.has_skip_coded) {
+        if (block.has_skip_coded && !escaped) {
             if (!block.skip_coded) throw std::runtime_error("Unknown input block type");
             state.coded = true;
             state.done = true;
@@ -562,7 +611,9 @@ class decompressor {                                     // recode.cpp:1319-1598
         fed_bytes_ += uint64_t(block.size);
         state.coded = true;
         state.done = false;
-        state.surrogate_marker = next_surrogate_marker(&surrogate_marker_sequence_number_);
+        state.escaped = escaped;
+        state.size = uint64_t(block.size);
+        state.surrogate_marker = next_surrogate_marker(&surrogate_marker_sequence_number_, escaped);
         if (block.has_length_parity && block.has_last_byte && !block.last_byte.empty()) {
             state.length_parity = block.length_parity ? 1 : 0;
             state.last_byte = uint8_t(block.last_byte[0]);

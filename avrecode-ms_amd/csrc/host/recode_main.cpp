@@ -42,6 +42,12 @@
 // error: restored file does not match the archive's digest (N bytes restored, M recorded)" (exit status 1, nothing written; in
 // test <dir> only the file that owns the archive is lost) -- and restore an archive without one as ever.  Under AVR_TIMING=1 the lines
 // "compress: digest" and "decompress: digest".
+// AVR_ESCAPED=1 = compress, roundtrip and test <dir> also code the slices whose NAL unit carries an emulation_prevention_three_byte inside
+// the payload: the parser hands over unescaped bytes, so such a payload is not in the file as it is and the slice stays literal otherwise
+// (a skip_coded block).  With the switch its escaped forms are looked for, and a hit becomes an ESCAPED block (Block field 7, avr_host.h):
+// coded like any other, escaped again by decompress.  Off by default: every archive is then byte for byte what it was.  The other
+// direction has no switch: the archive says so.  A reader that does not know field 7 -- the reference, this program before it knew --
+// refuses such an archive ("Invalid input block: must have exactly one type"); it does not restore wrong bytes.
 //
 // And `recode check <archive>`: restore the archive in memory, the way decompress does (K3, the parser, K1 on the device), and write
 // nothing.  "Digest OK: N bytes" and exit status 0 where the archive carries a digest and the restored bytes match it; "No digest in
@@ -84,6 +90,7 @@ bool device_estimators() {
 bool verify() { static const bool on = [] { const char *d = getenv("AVR_VERIFY"); return d && atoi(d) != 0; }(); return on; }
 bool verify_restore() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_RESTORE"); return d && atoi(d) != 0; }(); return on; }
 bool digest() { static const bool on = [] { const char *d = getenv("AVR_DIGEST"); return d && atoi(d) != 0; }(); return on; }
+bool escaped() { static const bool on = [] { const char *d = getenv("AVR_ESCAPED"); return d && atoi(d) != 0; }(); return on; }
 bool verify_k1() { static const bool on = [] { const char *d = getenv("AVR_VERIFY_K1"); return d && atoi(d) != 0; }(); return on; }
 
 std::string slurp(const std::string &path) {
@@ -100,6 +107,7 @@ std::string compress_bytes(const std::string &original) {            // compress
     c.set_verify(verify());
     c.set_restore_check(verify_restore());
     c.set_digest(digest());
+    c.set_escaped(escaped());
     h264::h264_stream_decoder d;
     d.residual_hooks = model_hooks();
     return c.run(&d);
@@ -304,7 +312,7 @@ void perf_test_driver(const std::string &directory_path) {
     const unsigned threads = std::min<unsigned>(hw ? hw : 4, 32);
     shared_batch batch_in, batch_out, batch_restore;
     const bool on_device = device_estimators();                      // read here, once, not in the files' threads
-    const bool verify_on = verify(), verify_k1_on = verify_k1(), restore_on = verify_restore(), digest_on = digest();
+    const bool verify_on = verify(), verify_k1_on = verify_k1(), restore_on = verify_restore(), digest_on = digest(), escaped_on = escaped();
     for (size_t base = 0; base < files.size(); base += window) {
         const size_t n = std::min(window, files.size() - base);
         std::vector<file_job> jobs(n);
@@ -323,6 +331,7 @@ void perf_test_driver(const std::string &directory_path) {
                 j.c->set_device_estimators(on_device);
                 j.c->set_restore_check(restore_on);
                 j.c->set_digest(digest_on);
+                j.c->set_escaped(escaped_on);
                 h264::h264_stream_decoder dec;
                 dec.residual_hooks = model_hooks();
                 dec.dry_run_threads = 1;                             // the cores are taken by the files

@@ -166,6 +166,46 @@ def compact_device(out, out_off, out_len, dense_capacity=None):
     return dense, dense_off
 
 
+def finish_word(last_byte=0, length_parity=0, patch=False, escape=False, zeros_before=0):
+    """AVR_FINISH_WORD: a slice's word for finish_device, from what its container block holds."""
+    return (last_byte & 0xFF) | (length_parity & 1) << 8 | bool(patch) << 9 | bool(escape) << 10 | min(int(zeros_before), 2) << 11
+
+
+def finish_capacity(region_bytes, n_slices):
+    """Room that holds whatever avr_finish_device makes of n_slices slices in regions of region_bytes in all: the header's bound of
+    L + 1 + (L + 1 + z) / 2 for a slice of L bytes with z <= 2 zeros in front, summed (at most 1.5 L + 2.5 each) and rounded up."""
+    return region_bytes + (region_bytes + 1) // 2 + 3 * n_slices
+
+
+def finish_device(out, out_off, out_len, finish, status=None, dense_capacity=None):
+    """avr_finish_device on torch's current stream: (dense uint8[dense_capacity], dense_off int64[n + 1]) -- every slice's bytes as
+    its NAL unit holds them (stop byte dropped, tail patched, escaped, by its word of `finish`: an int32 tensor on the device, see
+    finish_word), one behind the other.  status: the slices' status on the device (int32, one per slice), or None: all sound.
+    dense_capacity: the room in `dense`; None: what the slices can grow to at the most, which is worked out from out_off[-1] and so
+    WAITS for the stream once.  With a capacity given the call enqueues and returns.  dense_off[-1] > dense_capacity says that the
+    slices from the first that did not fit were not written."""
+    import torch
+    dev, n = out_off.device, out_len.numel()
+    for name, t in (("finish", finish), ("status", status)):
+        if t is not None and (t.numel() != n or t.dtype != torch.int32 or t.device != dev):
+            raise AvrError(f"finish_device: {name} must be an int32 tensor of one word per slice on the slices' device")
+    status = None if status is None else status.contiguous()
+    finish = finish.contiguous()
+    with torch.cuda.device(dev):
+        if dense_capacity is None:
+            dense_capacity = finish_capacity(int((out_off[-1] - out_off[0]).item()), n)
+        dense = torch.empty(dense_capacity, dtype=torch.uint8, device=dev)
+        dense_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        ws_bytes = lib().avr_finish_workspace_bytes(n)
+        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
+        _check(lib().avr_finish_device(_device_index(out_off), _stream_ptr(torch), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(),
+                                       None if status is None else status.data_ptr(), n, finish.data_ptr(), dense.data_ptr(), dense_capacity,
+                                       dense_off.data_ptr(), _aligned(ws), ws_bytes))
+        ws.record_stream(torch.cuda.current_stream())
+        finish.record_stream(torch.cuda.current_stream())
+    return dense, dense_off
+
+
 def _aligned(t):
     """t's address rounded up to 256 bytes, as the C ABI wants a workspace (the workspaces here are allocated 256 bytes larger)."""
     return (t.data_ptr() + 255) // 256 * 256
@@ -921,4 +961,16 @@ class DeviceWorkload:
         concatenation of what results() returns.  Synchronises once, to size the view by dense_off[-1]."""
         import torch
         dense, dense_off = compact_device(self.out, self.out_off, self.out_len)
+        return dense[:int(dense_off[-1].item())], dense_off
+
+    def results_finished(self, finish_words):
+        """The slices' bytes as their NAL units hold them (avr_finish_device behind the encode on torch's current stream):
+        finish_words: one word per slice (finish_word), a sequence or an int32 tensor.  (dense uint8 tensor, dense_off int64[n + 1]) on
+        the device, as results_dense() gives the coded bytes; a slice whose status is not SLICE_OK gives none.  Synchronises once, to
+        size the view by dense_off[-1]."""
+        import numpy as np
+        import torch
+        if not torch.is_tensor(finish_words):
+            finish_words = torch.from_numpy(np.asarray(finish_words, dtype=np.uint32).view(np.int32).copy())
+        dense, dense_off = finish_device(self.out, self.out_off, self.out_len, finish_words.to(self.out_off.device), self.status)
         return dense[:int(dense_off[-1].item())], dense_off

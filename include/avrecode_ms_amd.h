@@ -867,7 +867,8 @@ int avr_range_encode_slices_device(int device, void *stream,
  * a workspace below the quote; n_slices >= 2^31.  n_slices == 0 writes the single zero of each n + 1 array and zero totals. */
 /* AVR_NOWAIT marks a call that enqueues on `stream` and returns whatever its arguments: no wait, no allocation, no stream of its own.
  * (It also sets the three calls apart for tests/device_api_refusals.py, whose table is made from the parameter names of the unmarked
- * *_device declarations and cannot describe a struct of arrays with caps; tests/test_plan_bounds.py holds these three to their refusals.) */
+ * *_device declarations and cannot describe a struct of arrays with caps; tests/test_plan_bounds.py holds these three to their refusals,
+ * tests/test_finish_bounds.py avr_finish_device below to its own.) */
 #define AVR_NOWAIT
 #define AVR_PLAN_SERIAL 0   /* out_off (+ rec_off)                                  */
 #define AVR_PLAN_CHUNKS 1   /* + chunk_base, chunk_slice      (K2p, resolver)       */
@@ -894,6 +895,37 @@ int avr_plan_tiles_device(int device, void *stream, const uint32_t *n_bins, size
 int avr_chunk_plan_from(const avr_plan_arrays *arrays, const avr_plan_totals *totals, avr_chunk_plan *plan);     /* host, after a sync */
 int avr_compact_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len, size_t n_slices,
                        uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off /* n + 1 */, void *workspace, size_t workspace_bytes) AVR_NOWAIT;
+
+/* ------------------------------------------------------------------ the way back's epilogue on the device
+ * avr_compact_device ends at coded bytes.  The bytes a NAL unit holds are one step further: the stop byte dropped (avr_drop_stop_byte),
+ * the tail patched (avr_tail_patch) and, for a slice whose container block says so, emulation prevention put back -- which changes
+ * lengths, so that a caller whose output stays in HBM could not know where slice i + 1 starts without it.  avr_finish_device is
+ * avr_compact_device with that step in it (avr_plan_dev.hip, the per-run rules in avrecode-ms_amd/csrc/avr_finish.h): it enqueues on
+ * `stream` and returns, never waits or allocates, and writes nothing outside its workspace, dense_off[0 .. n] and dense[0 .. capacity).
+ *   finish[i]   one word per slice, on the device (AVR_FINISH_WORD):
+ *                 bits 0-7    last_byte            bit 8   length_parity
+ *                 bit 9       the container had both (the tail is patched; without it bits 0-8 are ignored)
+ *                 bit 10      escape               bits 11-12   the zero bytes directly in front of the payload (3 is taken as 2)
+ *   status      n words on the device, or NULL: every slice is AVR_SLICE_OK.  A slice of any other status gives no bytes.
+ *   workspace   avr_finish_workspace_bytes(n_slices) bytes of device memory (a quote of its own), 256-byte aligned, arbitrary on entry
+ * Per slice: L = min(out_len[i], out_off[i + 1] - out_off[i]) bytes are taken, as compaction has it; one trailing 0x80 is dropped; with
+ * bit 9 the last byte is appended where the length's parity differs from bit 8, else written over the last byte (where there is one);
+ * with bit 10 the result p becomes escape(p, z): s = z; for every byte b: if s == 2 and b <= 3, 0x03 is emitted and s = 0; b is
+ * emitted; s = b == 0 ? s + 1 : 0.  A slice grows to L + 1 + (L + 1 + z) / 2 bytes at the most.
+ * dense_off[n + 1] is the exclusive prefix sum of the final lengths with the total appended, complete whatever the capacity; slice i's
+ * bytes go to dense + dense_off[i] whole or not at all, and no byte is written at or past dense_capacity: avr_compact_device's
+ * contract, and its very output where every word of `finish` is 0 and no slice ends on 0x80.  All lengths and offsets are 64 bits wide.
+ * Refused as avr_compact_device refuses (AVR_ERR_INVALID), `finish` being one more array that may not be null with n_slices > 0 and
+ * must be 4-byte aligned, as `status` must where it is given.
+ * avr_batch and avr_multi do not finish: their lengths reach the host anyway.  Nor does the command line, which keeps its host
+ * epilogue (its CPU build links a stand-in for this library that knows no symbol newer than the batch's). */
+#define AVR_FINISH_WORD(last_byte, length_parity, patch, escape, zeros_before) \
+    ((uint32_t)((last_byte) & 0xffu) | (uint32_t)((length_parity) & 1u) << 8 | (uint32_t)((patch) ? 1u : 0u) << 9 | \
+     (uint32_t)((escape) ? 1u : 0u) << 10 | (uint32_t)((zeros_before) > 2u ? 2u : (zeros_before)) << 11)
+size_t avr_finish_workspace_bytes(size_t n_slices);                                                             /* host */
+int avr_finish_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
+                      const int32_t *status /* or NULL: all OK */, size_t n_slices, const uint32_t *finish /* n, device */,
+                      uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off /* n + 1 */, void *workspace, size_t workspace_bytes) AVR_NOWAIT;
 
 /* ------------------------------------------------------------------ dense context ids
  * A context is identified by the offset of its state byte in libavcodec's cabac_state[1024]
