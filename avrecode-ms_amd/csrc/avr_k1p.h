@@ -69,6 +69,83 @@ AVR_HD int clz32(uint32_t x) {
 #endif
 }
 
+// ---- phase A: one chunk's step of a context's state chain (k_k1p_ctxchain, k_k1p_chain_seg, k_k1p_chain_fix)
+//
+// k_k1p_tn's table, tn[tn_section(n) + (st << n | bits)], is the state after the n = 0 .. 8 bins `bits` (first bin in the low bit)
+// from state st.  A run of `left` bins goes through it as  left % 8 bins first, by the section of that n (the identity for n = 0,
+// which is also what a lane without bins reads), then whole bytes by the section of n = 8: the index of a whole byte is
+// st << 8 | byte behind a constant, and which byte of the run it is is known when the code is written, so a whole byte costs one
+// bit-field extract for all NS states and one shift-or per state.  Every look-up after the first is taken only by the lanes that
+// have it, and only while some lane of the wave has it (AVR_ANY: on the CPU a lane is alone).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define AVR_ANY(x) __any(x)
+#define AVR_PIN1(a) asm volatile("" : "+v"(a))
+#else
+#define AVR_ANY(x) (x)
+#define AVR_PIN1(a) ((void)0)
+#endif
+AVR_HD constexpr uint32_t tn_section(uint32_t n) { return (128u << n) - 128u; }
+// Entry i of the table, i < tn_section(9), bin by bin (cabac_code.h:43-47); packed: CabacTables::packed, whose [s][1] is the state
+// after an MPS in state s in its low byte and after an LPS in the next.
+AVR_HD uint8_t tn_entry(uint32_t i, const uint32_t (*packed)[2]) {
+    const uint32_t n = 31u - uint32_t(clz32((i >> 7) + 1)), j = i - tn_section(n);
+    uint32_t st = j >> n;
+    for (uint32_t b = 0; b < n; b++) {
+        const uint32_t nx = packed[st][1], bin = (j >> b) & 1u;
+        st = ((bin ^ st) & 1u) ? (nx >> 8) & 0xffu : nx & 0xffu;
+    }
+    return uint8_t(st);
+}
+// bits 32 (pos / 32) .. + 127 of a chunk's bit string: the window a run from bit `pos` starts in
+AVR_HD U4 chain_window(const uint32_t *bw, uint32_t pos) {
+    const uint32_t wi = (pos >> 5) & (kChunkBitDwords - 1);      // (past the last dword: the next chunk's, never used -- a run ends by bit kChunk)
+    return U4{bw[wi], bw[wi + 1], bw[wi + 2], bw[wi + 3]};
+}
+// bits sh .. sh + 31 of hi:lo, sh < 32
+AVR_HD uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t sh) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, sh);
+#else
+    return sh ? (lo >> sh) | (hi << (32u - sh)) : lo;
+#endif
+}
+// Whole bytes first .. first + COUNT - 1 of the run, out of `avail` (some lane has byte `first`); true: some lane has more.
+template <int NS, int COUNT>
+AVR_HD bool chain_bytes(const uint8_t *tn, uint32_t avail, uint32_t first, uint32_t whole, uint32_t (&st)[NS]) {
+#pragma unroll
+    for (int i = 0; i < COUNT; i++) {
+        if (i && !AVR_ANY(whole > first + i)) return false;
+        if (whole > first + i) {
+            const uint32_t byte = (avail >> (8 * i)) & 0xffu;
+#pragma unroll
+            for (int q = 0; q < NS; q++) st[q] = tn[tn_section(8) + (st[q] << 8 | byte)];
+        }
+    }
+    return AVR_ANY(whole > first + COUNT);
+}
+// The context's `left` bins of the chunk are bits [pos, pos + left) of the chunk's bit string `bw` (pos + left <= kChunk; readable
+// up to dword kChunkBitDwords); w: its four dwords from dword pos / 32 on, which hold the run's first 96 bins at least.  NS states
+// at once, side by side.
+template <int NS>
+AVR_HD void chain_step(const uint8_t *tn, const uint32_t *bw, uint32_t pos, uint32_t left, const U4 &w, uint32_t (&st)[NS]) {
+    const uint32_t sh = pos & 31u, rem = left & 7u, whole = left >> 3;
+    const uint32_t b0 = funnel(w.y, w.x, sh);
+    uint32_t off = tn_section(rem) + (b0 & ((1u << rem) - 1u));  // all of the index that does not wait for the state
+    AVR_PIN1(off);                                               // (kept whole: the compiler would split it up again)
+#pragma unroll
+    for (int q = 0; q < NS; q++) st[q] = tn[(st[q] << rem) + off];
+    if (!AVR_ANY(whole != 0)) return;
+    const uint32_t b1 = funnel(w.z, w.y, sh);                    // the whole bytes start rem bins into the run
+    if (!chain_bytes<NS, 4>(tn, funnel(b1, b0, rem), 0, whole, st)) return;
+    const uint32_t b2 = funnel(w.w, w.z, sh);
+    if (!chain_bytes<NS, 4>(tn, funnel(b2, b1, rem), 4, whole, st)) return;
+    if (!chain_bytes<NS, 3>(tn, b2 >> rem, 8, whole, st)) return;         // 96 - rem bins of the window: eleven whole bytes
+    for (uint32_t first = 11;; first += 4) {                     // a run of more than that: fetched as it goes
+        const uint32_t at = pos + rem + 8 * first, wi = (at >> 5) & (kChunkBitDwords - 1);   // (a lane without the byte: any dword of the string)
+        if (!chain_bytes<NS, 4>(tn, funnel(bw[wi + 1], bw[wi], at & 31u), first, whole, st)) return;
+    }
+}
+
 // ---- resolved codes
 AVR_HD uint32_t code_sym(uint32_t c) { return ((c >> 1) ^ c) & 1u; }
 AVR_HD bool code_is_bypass(uint32_t c) { return (c >> 1) == 126u; }

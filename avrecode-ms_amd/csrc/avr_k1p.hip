@@ -180,13 +180,7 @@ __global__ __launch_bounds__(AVR_MAX_STATES) void k_k1p_densemap(const uint32_t 
 __global__ __launch_bounds__(256) void k_k1p_tn(uint8_t *tn) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= kTnBytes) return;
-    const uint32_t n = 31 - __clz((i >> 7) + 1), j = i - ((128u << n) - 128u);
-    uint32_t st = j >> n;
-    for (uint32_t b = 0; b < n; b++) {
-        const uint32_t nx = d_tables.packed[st][1], bin = (j >> b) & 1u;
-        st = ((bin ^ st) & 1u) ? (nx >> 8) & 0xffu : nx & 0xffu;
-    }
-    tn[i] = uint8_t(st);
+    tn[i] = tn_entry(i, d_tables.packed);
 }
 
 // A lane's walk over the 16-byte record groups [i0, i1) of its chunk (8 records a group; a slice's records are padded with no-ops to
@@ -454,15 +448,56 @@ __global__ __launch_bounds__(512) void k_k1p_local(Plan p, uint32_t total_chunks
 // one kernel apart, so that one half's chains run under the other half's sort and replay.  Those kernels, one lane
 // per chunk at under five waves per SIMD, are short of waves themselves: every kernel of a half got slower by more
 // than the overlap gave back, 2.05 against 1.95 ms per step.  Also without effect: twice the read-ahead (end positions
-// eight chunks ahead, windows four), and whole-byte look-ups without the arithmetic on n between them -- a step is the
-// hottest lane's seven or so dependent LDS round trips, and neither its loads nor its VALU work.  The step as it stands --
-// four look-ups without a branch, four more if any lane needs them, one shift-add between two look-ups -- is 3 % faster
-// than the loops it replaced; taking out, for the measurement, the stores, or the window loads, changes nothing.)
+// eight chunks ahead, windows four); taking out, for the measurement, the stores, or the window loads, changes nothing.)
+// The step (chain_step, avr_k1p.h) is paid for in instructions as well as in round trips: with every wave of a launch resident
+// the SIMDs issue for eight waves at once, and going from 159 to 130 executed instructions a wave and chunk (whole bytes by the
+// table's section for eight bins, no arithmetic on n between them; the read-ahead queue turned by unrolling, not by moves; the
+// segments' bit strings kept only while a lane still needs them) took a fifth off the segmented chains.  Below that the round
+// trips are the time: with the lanes dealt by their contexts' bins per chunk, so that nine waves in ten leave the step after a
+// look-up or two, the count fell to 99 and the kernels took as long as before ("The chains' step, counted").
 constexpr uint32_t kChainLanes = 22, kChainWaves = 8;         // kChainLanes: the fewest lanes a wave takes
-__device__ __forceinline__ uint4 window(const uint32_t *bw, uint32_t pos) {       // bits 32 (pos / 32) .. + 127 of a chunk's string
-    const uint32_t wi = (pos >> 5) & (kChunkBitDwords - 1);      // (past the last dword: the next chunk's, never used -- a run ends by bit kChunk)
-    return make_uint4(bw[wi], bw[wi + 1], bw[wi + 2], bw[wi + 3]);
-}
+// What the chains' loops have in flight for a lane: the end positions of its context four chunks ahead, the window its run starts in two
+// ahead.  take() hands out the current chunk's and puts the requests for the chunks four and two ahead in their place; the loops below
+// call it for slots 0, 1, 2, 3 in turn, unrolled by four, so that the queue turns by which registers a chunk's code names and not by
+// moves (12 v_mov a chunk before).  The loads are unconditional (see k_k1p_ctxchain).
+struct ChainAhead {
+    const uint16_t *le;                                          // end[k] of the chunk being requested
+    const uint32_t *bw_ahead, *bw_cur;                           // bit strings: of the chunk whose window is being requested, of the current one
+    uint32_t nk, k;
+    uint2 e[4];
+    U4 w[2];
+    __device__ __forceinline__ uint2 ends() {                    // (end[k-1], end[k]), then on to the next chunk
+        const uint32_t e1 = le[0], em = le[-1];
+        le += nk;
+        return make_uint2(k ? em : 0u, e1);
+    }
+    __device__ __forceinline__ ChainAhead(const uint32_t *lbits, const uint16_t *lend, uint32_t nk_, uint32_t k_, uint32_t c_first)
+        : le(lend + size_t(c_first) * nk_ + k_), bw_ahead(lbits + size_t(c_first) * kChunkBitDwords), bw_cur(bw_ahead), nk(nk_), k(k_) {
+        for (int j = 0; j < 4; j++) e[j] = ends();
+        for (int j = 0; j < 2; j++) { w[j] = chain_window(bw_ahead, e[j].x); bw_ahead += kChunkBitDwords; }
+    }
+    struct Chunk { uint32_t pos, cnt; U4 w; const uint32_t *bw; };
+    template <int J>
+    __device__ __forceinline__ Chunk take() {
+        const Chunk c{e[J].x, e[J].y > e[J].x ? e[J].y - e[J].x : 0u, w[J & 1], bw_cur};
+        e[J] = ends();
+        w[J & 1] = chain_window(bw_ahead, e[(J + 2) & 3].x);
+        bw_ahead += kChunkBitDwords;
+        bw_cur += kChunkBitDwords;
+        return c;
+    }
+    // f(Chunk) for n_ch chunks in a row
+    template <class F>
+    __device__ __forceinline__ void walk(uint32_t n_ch, F &&f) {
+        uint32_t c = 0;
+        for (; c + 4 <= n_ch; c += 4) { f(take<0>()); f(take<1>()); f(take<2>()); f(take<3>()); }
+        for (; c < n_ch; c++) {                                  // the last three at most: here the queue does turn
+            f(take<0>());
+            const uint2 t = e[0]; e[0] = e[1]; e[1] = e[2]; e[2] = e[3]; e[3] = t;
+            const U4 u = w[0]; w[0] = w[1]; w[1] = u;
+        }
+    }
+};
 __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint32_t n_slices, uint32_t groups, uint32_t chain_lanes, const int32_t *status,
                                                       const uint8_t *tng, const uint32_t *lbits, const uint16_t *lend,
                                                       const uint8_t *init_states, uint8_t *est, uint8_t *final_states) {
@@ -479,72 +514,16 @@ __global__ __launch_bounds__(64 * kChainWaves) void k_k1p_ctxchain(Plan p, uint3
     if ((groups && lane >= chain_lanes) || s >= n_slices || status[s] != AVR_SLICE_OK || k >= nk) return;
     const uint32_t col = p.index ? p.index[k] : k, row4 = ((nk + 3) >> 2) << 2;
     if (col >= p.ns_full) return;                                // a row beyond the batch's contexts (launch sized by a guess)
-    uint32_t st = init_states[size_t(s) * p.ns_full + col] & 127u;
+    uint32_t st[1] = {init_states[size_t(s) * p.ns_full + col] & 127u};
     const uint32_t c0 = p.chunk_base[s], nc = chunks_of(p.n_bins[s]);
-    const uint16_t *le = lend + size_t(c0) * nk + k;             // end[k] of the chunk being requested (four ahead)
-    const uint32_t *bw_ahead = lbits + size_t(c0) * kChunkBitDwords;   // bit string of the chunk whose window is being requested (two ahead)
-    const uint32_t *bw_cur = bw_ahead;                           // bit string of the chunk being walked
     uint8_t *eo = est + size_t(c0) * row4 + k;
-    auto ends = [&]() {                                          // (end[k-1], end[k]), then on to the next chunk
-        const uint32_t e1 = le[0], em = le[-1];
-        le += nk;
-        return make_uint2(k ? em : 0u, e1);
-    };
-    uint2 e0 = ends(), e1 = ends(), e2 = ends(), e3 = ends();
-    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + kChunkBitDwords, e1.x);
-    bw_ahead += 2 * kChunkBitDwords;
-    for (uint32_t c = 0; c < nc; c++) {
-        const uint2 e4 = ends();
-        const uint4 w2 = window(bw_ahead, e2.x);
-        bw_ahead += kChunkBitDwords;
-        *eo = uint8_t(st);
+    ChainAhead ahead(lbits, lend, nk, k, c0);
+    ahead.walk(nc, [&](const ChainAhead::Chunk &c) {
+        *eo = uint8_t(st[0]);
         eo += row4;
-        uint32_t pos = e0.x;
-        const uint32_t end = e0.y;
-        // The step is a chain of dependent look-ups, and every branch on it costs about as much as a look-up: the first 32
-        // bins are four look-ups without one (a look-up of n = 0 bins is the identity: rows 0 .. 127 of the table), the next
-        // 32 four more if any lane of the wave has them; what is left after 64 -- rare -- goes the general way.
-        uint32_t left = (end > pos && st < 126) ? end - pos : 0u;    // pStateIdx 63 never moves
-        const uint32_t sh = pos & 31u;
-        auto four = [&](uint32_t avail) {
-#pragma unroll
-            for (uint32_t i = 0; i < 4; i++) {
-                if (i && !__any(left != 0)) break;
-                const uint32_t n = left < 8u ? left : 8u;
-                uint32_t off = (128u << n) - 128u + (avail & ((1u << n) - 1u));         // all of the index that does not wait for the state
-                asm volatile("" : "+v"(off));                                          // (kept whole: the compiler would split it up again)
-                st = tn[(st << n) + off];                                              // ... and the one shift-add that does
-                avail >>= 8;
-                left -= n;
-            }
-        };
-        four(__builtin_amdgcn_alignbit(w0.y, w0.x, sh));
-        if (__any(left != 0)) {
-            four(__builtin_amdgcn_alignbit(w0.z, w0.y, sh));
-            if (__any(left != 0)) {
-                pos += 64;
-                uint32_t avail = __builtin_amdgcn_alignbit(w0.w, w0.z, sh);      // bins 64 .. 95 are in the window as well
-                uint32_t have = 32;
-                while (left) {
-                    if (have == 0) {                             // a run of more than 96 bins: fetch as it goes
-                        const uint4 win = window(bw_cur, pos);
-                        avail = __builtin_amdgcn_alignbit(win.y, win.x, pos & 31u);
-                        have = 32;
-                    }
-                    const uint32_t n = left < 8u ? left : 8u;
-                    uint32_t off = (128u << n) - 128u + (avail & ((1u << n) - 1u));
-                    asm volatile("" : "+v"(off));
-                    st = tn[(st << n) + off];
-                    avail >>= 8;
-                    left -= n; pos += n; have -= 8;
-                }
-            }
-        }
-        bw_cur += kChunkBitDwords;
-        e0 = e1; e1 = e2; e2 = e3; e3 = e4;
-        w0 = w1; w1 = w2;
-    }
-    if (final_states) final_states[size_t(s) * p.ns_full + col] = uint8_t(st);
+        chain_step<1>(tn, c.bw, c.pos, st[0] < 126u ? c.cnt : 0u, c.w, st);      // pStateIdx 63 never moves
+    });
+    if (final_states) final_states[size_t(s) * p.ns_full + col] = uint8_t(st[0]);
 }
 
 // ------------------------------------------------------------------ the chains in segments
@@ -576,50 +555,6 @@ constexpr uint32_t kSegWaves = 16;                               // 16 waves sha
 constexpr uint32_t kChainWaveSlots = 8192;
 // (kSegBits and SegSummary, what a segment leaves behind: avr_layout.h, which sizes the workspace by it)
 
-// One chunk's step of a context's chain for NS states at once: the context's bins of the chunk are bits [pos, end) of the chunk's
-// bit string (window w: 128 bits from dword pos / 32), taken eight per look-up.  Same structure as k_k1p_ctxchain's step.
-template <int NS>
-__device__ __forceinline__ void chain_step(const uint8_t *tn, const uint32_t *bw_cur, uint32_t pos, uint32_t end, const uint4 &w0, uint32_t (&st)[NS]) {
-    uint32_t left = end > pos ? end - pos : 0u;
-    const uint32_t sh = pos & 31u;
-    auto four = [&](uint32_t avail) {
-#pragma unroll
-        for (uint32_t i = 0; i < 4; i++) {
-            if (i && !__any(left != 0)) break;
-            const uint32_t n = left < 8u ? left : 8u;
-            uint32_t off = (128u << n) - 128u + (avail & ((1u << n) - 1u));
-            asm volatile("" : "+v"(off));
-#pragma unroll
-            for (int q = 0; q < NS; q++) st[q] = tn[(st[q] << n) + off];
-            avail >>= 8;
-            left -= n;
-        }
-    };
-    four(__builtin_amdgcn_alignbit(w0.y, w0.x, sh));
-    if (__any(left != 0)) {
-        four(__builtin_amdgcn_alignbit(w0.z, w0.y, sh));
-        if (__any(left != 0)) {
-            pos += 64;
-            uint32_t avail = __builtin_amdgcn_alignbit(w0.w, w0.z, sh);
-            uint32_t have = 32;
-            while (left) {
-                if (have == 0) {
-                    const uint32_t wi = (pos >> 5) & (kChunkBitDwords - 1);
-                    avail = __builtin_amdgcn_alignbit(bw_cur[wi + 1], bw_cur[wi], pos & 31u);
-                    have = 32;
-                }
-                const uint32_t n = left < 8u ? left : 8u;
-                uint32_t off = (128u << n) - 128u + (avail & ((1u << n) - 1u));
-                asm volatile("" : "+v"(off));
-#pragma unroll
-                for (int q = 0; q < NS; q++) st[q] = tn[(st[q] << n) + off];
-                avail >>= 8;
-                left -= n; pos += n; have -= 8;
-            }
-        }
-    }
-}
-
 // Which (slice, context, segment) a lane of the two kernels below has; false: none.
 struct ChainLane { uint32_t s, k, seg, c_begin, c_end, nc, col; };
 __device__ __forceinline__ bool chain_lane(const Plan &p, uint32_t n_slices, uint32_t n_segs, const int32_t *status, ChainLane *o) {
@@ -644,39 +579,34 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_k1p_chain_seg(Plan p, uint32
     if (!chain_lane(p, n_slices, n_segs, status, &L)) return;
     const uint32_t nk = p.n_states, row4 = ((nk + 3) >> 2) << 2, k = L.k;
     const uint32_t c0 = p.chunk_base[L.s] + L.c_begin, n_ch = L.c_end - L.c_begin;
-    const uint16_t *le = lend + size_t(c0) * nk + k;
-    const uint32_t *bw_ahead = lbits + size_t(c0) * kChunkBitDwords, *bw_cur = bw_ahead;
     uint8_t *eo = est + size_t(c0) * row4 + k;
-    auto ends = [&]() { const uint32_t e1 = le[0], em = le[-1]; le += nk; return make_uint2(k ? em : 0u, e1); };
-    uint2 e0 = ends(), e1 = ends(), e2 = ends(), e3 = ends();
-    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + kChunkBitDwords, e1.x);
-    bw_ahead += 2 * kChunkBitDwords;
     uint32_t st[2] = {124u, 125u};                               // the two ends of the order: (valMPS 0, pStateIdx 62), (valMPS 1, pStateIdx 62)
-    uint32_t met_chunk = n_ch, n_bins = 0;
+    uint32_t met_chunk = n_ch, n_bins = 0, at = 0;
     uint64_t bits0 = 0, bits1 = 0;
-    for (uint32_t c = 0; c < n_ch; c++) {
-        const uint2 e4 = ends();
-        const uint4 w2 = window(bw_ahead, e2.x);
-        bw_ahead += kChunkBitDwords;
+    ChainAhead ahead(lbits, lend, nk, k, c0);
+    ahead.walk(n_ch, [&](const ChainAhead::Chunk &c) {
         if (st[0] == st[1]) {                                    // met: this chunk's entry state is what it is whatever the segment was entered in
             *eo = uint8_t(st[0]);
-            met_chunk = met_chunk < c ? met_chunk : c;
+            met_chunk = met_chunk < at ? met_chunk : at;
+            // nothing reads the bins of a segment reported as met (k_k1p_chain_fix; o.met below): its string is full from here on
+            if (at < 0xffffu) n_bins = kSegBits + 1u;
         }
         eo += row4;
-        const uint32_t pos = e0.x, end = e0.y, cnt = end > pos ? end - pos : 0u;
-        if (n_bins < kSegBits && cnt) {                          // the bins themselves, while they fit: what a segment without a meeting point is carried on by
-            const uint32_t sh = pos & 31u;                       // (up to 64 of a chunk's: with more than that the string is full soon anyway, and then unused)
-            const uint64_t lo = uint64_t(__builtin_amdgcn_alignbit(w0.y, w0.x, sh)) | uint64_t(__builtin_amdgcn_alignbit(w0.z, w0.y, sh)) << 32;
+        at++;
+        const uint32_t cnt = c.cnt;
+        // the bins themselves, while they fit: what a segment without a meeting point is carried on by; only while some lane of the wave
+        // still keeps them -- the hot contexts, whose walks meet within a chunk or two, are quit of it
+        const bool room = n_bins < kSegBits && cnt;
+        if (__any(room) && room) {                               // (up to 64 of a chunk's: with more than that the string is full soon anyway, and then unused)
+            const uint32_t sh = c.pos & 31u;
+            const uint64_t lo = uint64_t(__builtin_amdgcn_alignbit(c.w.y, c.w.x, sh)) | uint64_t(__builtin_amdgcn_alignbit(c.w.z, c.w.y, sh)) << 32;
             const uint64_t got = cnt < 64u ? lo & ((uint64_t(1) << cnt) - 1) : lo;
             if (n_bins < 64u) { bits0 |= got << n_bins; bits1 |= n_bins ? got >> (64u - n_bins) : 0u; }
             else bits1 |= got << (n_bins - 64u);
         }
         n_bins += cnt > 64u ? kSegBits + 1u : cnt;              // a chunk with more than 64 of them: the string is not kept
-        chain_step<2>(tn, bw_cur, pos, end, w0, st);
-        bw_cur += kChunkBitDwords;
-        e0 = e1; e1 = e2; e2 = e3; e3 = e4;
-        w0 = w1; w1 = w2;
-    }
+        chain_step<2>(tn, c.bw, c.pos, cnt, c.w, st);
+    });
     SegSummary o;
     // (met_chunk has 16 bits: a meeting point beyond chunk 65 534 of the segment -- a slice of half a gigabin -- is reported as "did not meet",
     // which k_k1p_chain_fix answers by walking the whole segment again: slower for that pair, never wrong)
@@ -690,24 +620,13 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_k1p_chain_seg(Plan p, uint32
 template <bool NOTE>
 __device__ __forceinline__ uint32_t chain_chunks(const uint8_t *tn, const uint32_t *lbits, const uint16_t *lend, uint8_t *est, uint32_t nk, uint32_t row4,
                                                  uint32_t k, uint32_t c_first, uint32_t n_ch, uint32_t st0) {
-    const uint16_t *le = lend + size_t(c_first) * nk + k;
-    const uint32_t *bw_ahead = lbits + size_t(c_first) * kChunkBitDwords, *bw_cur = bw_ahead;
     uint8_t *eo = est + size_t(c_first) * row4 + k;
-    auto ends = [&]() { const uint32_t e1 = le[0], em = le[-1]; le += nk; return make_uint2(k ? em : 0u, e1); };
-    uint2 e0 = ends(), e1 = ends(), e2 = ends(), e3 = ends();
-    uint4 w0 = window(bw_ahead, e0.x), w1 = window(bw_ahead + kChunkBitDwords, e1.x);
-    bw_ahead += 2 * kChunkBitDwords;
     uint32_t st[1] = {st0};
-    for (uint32_t c = 0; c < n_ch; c++) {
-        const uint2 e4 = ends();
-        const uint4 w2 = window(bw_ahead, e2.x);
-        bw_ahead += kChunkBitDwords;
+    ChainAhead ahead(lbits, lend, nk, k, c_first);
+    ahead.walk(n_ch, [&](const ChainAhead::Chunk &c) {
         if (NOTE) { *eo = uint8_t(st[0]); eo += row4; }
-        if (st[0] < 126u) chain_step<1>(tn, bw_cur, e0.x, e0.y, w0, st);      // pStateIdx 63 never moves
-        bw_cur += kChunkBitDwords;
-        e0 = e1; e1 = e2; e2 = e3; e3 = e4;
-        w0 = w1; w1 = w2;
-    }
+        chain_step<1>(tn, c.bw, c.pos, st[0] < 126u ? c.cnt : 0u, c.w, st);      // pStateIdx 63 never moves
+    });
     return st[0];
 }
 

@@ -28,7 +28,7 @@ constexpr uint32_t kMaxChainSegs = 16;                           // segments a c
 constexpr uint32_t kSegBits = 128;                               // bins a segment's bit string holds
 struct alignas(16) SegSummary {
     uint64_t bits[2];         // the segment's bins of this context, first bin in bit 0 of bits[0] (valid when n_bins <= kSegBits)
-    uint32_t n_bins;
+    uint32_t n_bins;          // (of a segment whose walks did not meet: one that met is left with more than kSegBits whatever it had)
     uint8_t exit_state;       // state after the segment when the walks met
     uint8_t met;              // 1: the walks met (exit_state valid, chunks from met_chunk on are noted)
     uint16_t met_chunk;       // first chunk of the segment (relative to its start) whose entry state is noted; segment length if none
