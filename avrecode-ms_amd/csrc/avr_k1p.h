@@ -416,9 +416,267 @@ AVR_HD void b1_stretch(const uint8_t *res, uint32_t n, uint32_t chunk, const Cod
     for (uint32_t q = 0; q < 4; q++) { o->t_exit[q] = T[q] + Tm; o->r_exit[q] = uint16_t(R[q]); }
 }
 
+// ---- phase B1 as the kernels walk it (k_k1p_replay, k_k1p_b1): B1Walk.  b1_stretch above stays the CPU's statement of the result;
+// tests/b1walk_emul.cpp runs this code on the host, group by group, and holds every field of Stretch to it.
+
+struct alignas(8) U2 { uint32_t x, y; };
+
+// v_perm_b32 as far as it is used here: byte i of the result is byte sel[i] of s0:s1 (0 .. 3: s1's bytes, 4 .. 7: s0's), zero for sel[i] = 12
+AVR_HD uint32_t perm_b32(uint32_t s0, uint32_t s1, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(s0, s1, sel);
+#else
+    const uint64_t both = uint64_t(s0) << 32 | s1;
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < 4; i++) {
+        const uint32_t b = (sel >> (8 * i)) & 0xffu;
+        if (b < 8) r |= uint32_t((both >> (8 * b)) & 0xffu) << (8 * i);
+    }
+    return r;
+#endif
+}
+// The packed 16-bit operations: two values to a register, each half on its own (a shift takes the low four bits of its count).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+AVR_HD uint32_t pk_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)); }
+AVR_HD uint32_t pk_add(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)); }
+AVR_HD uint32_t pk_shl(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) << __builtin_bit_cast(u16x2, b)); }
+AVR_HD uint32_t pk_shr(uint32_t a, uint32_t n) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) >> __builtin_bit_cast(u16x2, n * 0x00010001u)); }
+#else
+AVR_HD uint32_t pk_halves(uint32_t lo, uint32_t hi) { return (lo & 0xffffu) | hi << 16; }
+AVR_HD uint32_t pk_sub(uint32_t a, uint32_t b) { return pk_halves((a & 0xffffu) - (b & 0xffffu), (a >> 16) - (b >> 16)); }
+AVR_HD uint32_t pk_add(uint32_t a, uint32_t b) { return pk_halves((a & 0xffffu) + (b & 0xffffu), (a >> 16) + (b >> 16)); }
+AVR_HD uint32_t pk_shl(uint32_t a, uint32_t b) { return pk_halves((a & 0xffffu) << (b & 15u), (a >> 16) << ((b >> 16) & 15u)); }
+AVR_HD uint32_t pk_shr(uint32_t a, uint32_t n) { return pk_halves((a & 0xffffu) >> n, (a >> 16) >> n); }
+#endif
+
+// A bin as B1Walk takes it, 16 bytes and one LDS read: { x: the LPS ranges of its state's four range quarters, y: next | code << 8 |
+// meta << 16 (next: what k_k1p_replay keeps there, the context's state after the bin), z, w: CodeEntryC's side and adj }.
+AVR_HD U4 b1_entry(const CodeEntry &ce, uint32_t next, uint32_t code) {
+    const CodeEntryC cc = code_entry_c(ce);
+    return U4{ce.row, next | code << 8 | ce.meta << 16, cc.side, cc.adj};
+}
+// per code, for the candidates' LPS side: { x: low byte of post_lps_range per range quarter, y: its shift per quarter }
+AVR_HD U2 codes2_entry(uint32_t row) {
+    U2 r{0, 0};
+    for (uint32_t q = 0; q < 4; q++) {
+        if (!((row >> (8 * q)) & 0xffu)) continue;
+        uint32_t sh;
+        const uint32_t rn = post_lps_range(row, q, &sh);
+        r.x |= (rn & 0xffu) << (8 * q);
+        r.y |= sh << (8 * q);
+    }
+    return r;
+}
+
+// B1's four candidate ranges, two to a register (16 bits each), stepped with the packed 16-bit instructions: a range in [256, 511]
+// shifted down by six is 4 .. 7, which as a byte selector means the bytes of the first operand and, in the half's other byte, 0 = byte 0
+// of the second.  So one byte permute picks each candidate's LPS range out of the state's row by the candidate's own quarter, and
+// the LPS side (the range renormalised, whose bit 8 is the second operand's 1; its shift) comes out of the two rows of codes2 the same
+// way instead of a count of leading zeros per candidate.  Both sides are computed and `side` (all ones: the LPS side) picks by bit,
+// never by a branch: the candidates of a wave's lanes take either side at nearly every bin.
+// One bin on a pair of candidates (step_range, twice): returns the two shifts, packed, without a bypass bin's own.
+AVR_HD uint32_t step_pair(uint32_t &Rp, uint32_t row, uint32_t rown, uint32_t shrow, uint32_t side) {
+    const uint32_t sel = pk_shr(Rp, 6);
+    const uint32_t rl = perm_b32(row, 0u, sel);
+    const uint32_t rm = pk_sub(Rp, rl);                              // MPS side: range - rLPS, in [128, 511]
+    const uint32_t shm = pk_shr(rm, 8) ^ 0x00010001u;                // one shift iff below 256
+    const uint32_t rn = perm_b32(rown, 1u, sel);                     // LPS side, renormalised: in [256, 511]
+    const uint32_t shl = perm_b32(shrow, 0u, sel);
+    Rp = (rn & side) | (pk_shl(rm, shm) & ~side);
+    return (shl & side) | (shm & ~side);
+}
+
+// A chunk's stretch summary from its bins in order, eight at a time.
+// mode: 0 = looking for the LPS that opens the stretch, 1 = four candidate ranges, 2 = they have met, 3 = closed.
+// Inside the chunk (group_inside: all eight bins below i1) nothing can close the stretch and no path has a branch per bin:
+//   merged8   mode 2: step_range_c on the one range left;
+//   cand8     mode 1: step_pair on both pairs, the rows of codes2 read four bins at a time;
+//   open8     mode 0, and mode 1 beside it: the bin that opens the stretch is the first set bit of the group's boundary bits; every
+//             bin is stepped as in cand8 and at the opening bin the candidates are set from its row of codes2 and the shifts so
+//             far dropped, by select.
+// A wave takes each path some lane of it needs.
+// Past the chunk (tail) a merged lane closes at the first boundary bin: tail8 finds it in the boundary bits -- or the bin by which
+// the stretch is too long, or the slice's last -- and steps the bins up to it by select.
+// one(), the bin-by-bin form of all of it, is left with what is rare: the last group of a slice's last chunk when the slice does not end
+// on a multiple of eight (and that chunk's group of padding after it), and in the tail a lane whose candidates have not met.
+struct B1Walk {
+    uint32_t i0, i1, limit, n, max_stretch;
+    const U2 *codes2;
+    // Candidates 0, 1 in Rp0 (low, high half), 2, 3 in Rp1; Tp: their shifts since the last flush; T: before it.  Once they have met
+    // (join) the one range left is all of Rp0 and its shifts go to T[0], T[1 .. 3] being what candidates 1 .. 3 had shifted more than
+    // candidate 0 by then: a merged lane needs no registers of its own for them.
+    uint32_t mode, Rp0, Rp1, Tp0, Tp1, T[4], end;
+    bool merged;
+    Stretch o;
+
+    AVR_HD void init(uint32_t chunk, uint32_t i0_, uint32_t i1_, uint32_t n_, uint32_t max_stretch_, const U2 *codes2_) {
+        i0 = i0_; i1 = i1_; limit = i0_ + kChunk; n = n_; max_stretch = max_stretch_; codes2 = codes2_;
+        mode = 0; Rp0 = Rp1 = 0x01fe01feu; Tp0 = Tp1 = 0; T[0] = T[1] = T[2] = T[3] = 0; end = 0;
+        merged = false;
+        o.first = kNone; o.end = 0; o.exit_q = 0; o.too_long = 0; o.pad[0] = o.pad[1] = 0;
+        for (int q = 0; q < 4; q++) { o.t_exit[q] = 0; o.r_exit[q] = 0; }
+        if (chunk == 0) { o.first = 0; Rp0 = 510; mode = 2; merged = true; }    // opens at bin 0 with the initial range 510 (cabac_code.h:30)
+    }
+    // at least every 8 bins: 8 x 9 shifts fit 16 bits with room.  byp: the bypass bins among them, one shift each, where Tp has them not
+    AVR_HD void flush_t(uint32_t byp = 0) {
+        T[0] += (Tp0 & 0xffffu) + byp; T[1] += (Tp0 >> 16) + byp; T[2] += (Tp1 & 0xffffu) + byp; T[3] += (Tp1 >> 16) + byp;
+        Tp0 = Tp1 = 0;
+    }
+    AVR_HD bool met() const { return Rp0 == Rp1 && (Rp0 >> 16) == (Rp0 & 0xffffu); }
+    // the candidates have met (Tp flushed: the differences are taken on all their shifts so far)
+    AVR_HD void join() { Rp0 &= 0xffffu; T[1] -= T[0]; T[2] -= T[0]; T[3] -= T[0]; mode = 2; merged = true; }
+    AVR_HD void open(uint32_t rown) {                            // post_lps_range for the four quarters
+        Rp0 = perm_b32(rown, 1u, 0x00050004u);
+        Rp1 = perm_b32(rown, 1u, 0x00070006u);
+    }
+    AVR_HD uint32_t step_merged(const U4 &e) {                   // step_range on the one range left
+        uint32_t v;
+        return step_range_c(CodeEntryC{e.x, e.z, 0u, e.w}, &Rp0, &v);
+    }
+    AVR_HD void one(uint32_t idx, const U4 &e) {                 // bin idx (< n), any mode
+        const bool boundary = (e.y >> 16) & 1u;                  // a coded LPS (code_is_boundary)
+        if (mode == 0) {
+            if (idx < i1 && boundary) { o.first = idx; open(codes2[(e.y >> 8) & 0xffu].x); mode = 1; }
+        } else if (mode == 1) {
+            const bool closing = idx >= limit && boundary;
+            if (closing)
+                o.exit_q |= uint8_t(((Rp0 >> 6) & 3u) | ((Rp0 >> 22) & 3u) << 2 | ((Rp1 >> 6) & 3u) << 4 | ((Rp1 >> 22) & 3u) << 6);
+            const U2 e2 = codes2[(e.y >> 8) & 0xffu];
+            const uint32_t extra = (e.y >> 24) * 0x00010001u;    // a bypass bin's one shift
+            Tp0 = pk_add(Tp0, step_pair(Rp0, e.x, e2.x, e2.y, e.z) + extra);
+            Tp1 = pk_add(Tp1, step_pair(Rp1, e.x, e2.x, e2.y, e.z) + extra);
+            if (closing) { end = idx + 1; mode = 3; }
+            else if (met()) { flush_t(); join(); }
+        } else if (mode == 2) {
+            const bool closing = idx >= limit && boundary;
+            if (closing) o.exit_q = uint8_t(((Rp0 >> 6) & 3) * 0x55u);
+            T[0] += step_merged(e);
+            if (closing) { end = idx + 1; mode = 3; }
+            else if (idx >= limit && idx - i0 > max_stretch) { o.too_long = 1; end = idx + 1; mode = 3; }
+        }
+    }
+    AVR_HD void merged8(const U4 e[8]) {
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) T[0] += step_merged(e[j]);
+    }
+    AVR_HD void rows4(const U4 e[4], U2 r[4]) const {            // four rows of codes2, read together and waited for once
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) r[j] = codes2[(e[j].y >> 8) & 0xffu];
+        AVR_PIN2(r[0].x, r[0].y); AVR_PIN2(r[1].x, r[1].y); AVR_PIN2(r[2].x, r[2].y); AVR_PIN2(r[3].x, r[3].y);
+    }
+    AVR_HD void cand8(const U4 e[8]) {
+        uint32_t w = 8 * 23u;                                    // adj is bypass - 23: the sum counts the bypass bins
+#pragma unroll
+        for (uint32_t h = 0; h < 8; h += 4) {
+            U2 r[4];
+            rows4(e + h, r);
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                Tp0 = pk_add(Tp0, step_pair(Rp0, e[h + j].x, r[j].x, r[j].y, e[h + j].z));
+                Tp1 = pk_add(Tp1, step_pair(Rp1, e[h + j].x, r[j].x, r[j].y, e[h + j].z));
+                w += e[h + j].w;
+            }
+        }
+        flush_t(w);
+        // candidates that have met stay together: looking once per group is enough, and the group's shifts are in T[] either way
+        if (met()) join();
+    }
+    AVR_HD void open8(uint32_t base, const U4 e[8]) {
+        uint32_t bm = 0;                                         // bit j: bin j is a coded LPS
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) bm |= e[j].z & (1u << j);
+        // the bin that opens the stretch; 8: none of these; kNone: it is open already
+        const uint32_t at = mode == 0 ? uint32_t(__builtin_ctz(bm | 0x100u)) : kNone;
+        uint32_t w = 0;
+#pragma unroll
+        for (uint32_t h = 0; h < 8; h += 4) {                    // (a lane that is still looking steps the ranges it was set up with: any will do)
+            U2 r[4];
+            rows4(e + h, r);
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                Tp0 = pk_add(Tp0, step_pair(Rp0, e[h + j].x, r[j].x, r[j].y, e[h + j].z));
+                Tp1 = pk_add(Tp1, step_pair(Rp1, e[h + j].x, r[j].x, r[j].y, e[h + j].z));
+                w += e[h + j].w + 23u;
+                const bool here = at == h + j;
+                Rp0 = here ? perm_b32(r[j].x, 1u, 0x00050004u) : Rp0;
+                Rp1 = here ? perm_b32(r[j].x, 1u, 0x00070006u) : Rp1;
+                Tp0 = here ? 0u : Tp0; Tp1 = here ? 0u : Tp1; w = here ? 0u : w;
+            }
+        }
+        if (at < 8) { o.first = base + at; mode = 1; }
+        if (mode == 1) {
+            flush_t(w);
+            if (met()) join();                                   // (in the opening group itself, too)
+        } else {
+            Tp0 = Tp1 = 0;
+        }
+    }
+    // bins base .. base+7, all of them below i1.  any_looking: some lane of those that walk side by side is in mode 0 (a lane alone:
+    // this one).  A wave whose lanes have all merged skips the rest by the branch hipcc puts around a block no lane enters.
+    AVR_HD void group_inside_as(uint32_t base, const U4 e[8], bool any_looking) {
+        if (mode == 2) merged8(e);
+        else if (any_looking) open8(base, e);
+        else cand8(e);
+    }
+    AVR_HD void group_inside(uint32_t base, const U4 e[8]) { group_inside_as(base, e, AVR_ANY(mode == 0)); }
+    AVR_HD void group(uint32_t base, const U4 e[8]) {            // bins base .. base+7 of the chunk, as many of them as the slice has
+        if (base + 8 <= i1) {
+            group_inside(base, e);
+        } else if (mode != 3) {
+            for (uint32_t j = 0; j < 8; j++) if (base + j < n) one(base + j, e[j]);
+            flush_t();
+        }
+    }
+    AVR_HD void chunk_done() { if (mode == 0) mode = 3; }        // no LPS in the chunk: no stretch opens here (first stays kNone)
+    // Past the chunk, mode 2, base < n: every index is at or beyond `limit`, so the stretch ends with the first bin that is a coded LPS
+    // or lies more than max_stretch bins from i0, that bin stepped like the ones before it; failing both it runs on to the slice's end.
+    AVR_HD void tail8(uint32_t base, const U4 e[8]) {
+        uint32_t bm = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) bm |= e[j].z & (1u << j);
+        const uint32_t closes = uint32_t(__builtin_ctz(bm | 0x100u));                     // 8: no bin of these
+        const uint32_t d = base - i0, far = max_stretch >= d ? max_stretch - d + 1 : 0;   // first j with base + j - i0 > max_stretch
+        const uint32_t left = n - base - 1 < 7u ? n - base - 1 : 7u;                     // the group's last bin that the slice has
+        const uint32_t stop = closes < far ? closes : far, last = stop < left ? stop : left;
+        uint32_t before = Rp0;                                   // the range before bin `last`
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) {
+            const bool on = j <= last;
+            uint32_t r = Rp0, v;
+            const uint32_t sh = step_range_c(CodeEntryC{e[j].x, e[j].z, 0u, e[j].w}, &r, &v);
+            before = on ? Rp0 : before;
+            Rp0 = on ? r : Rp0;
+            T[0] += on ? sh : 0u;
+        }
+        if (last == closes) { o.exit_q = uint8_t(((before >> 6) & 3) * 0x55u); end = base + last + 1; mode = 3; }
+        else if (last == far) { o.too_long = 1; end = base + last + 1; mode = 3; }
+    }
+    AVR_HD void tail(uint32_t base, const U4 e[8]) {             // past the chunk, until the stretch closes
+        if (base >= n) return;                                   // (k_k1p_b1 comes with the second half of its sixteen codes whatever n is)
+        if (mode == 2) {
+            tail8(base, e);
+        } else {
+            for (uint32_t j = 0; j < 8; j++) if (base + j < n && mode != 3) one(base + j, e[j]);
+            flush_t();
+        }
+    }
+    AVR_HD const Stretch &finish() {
+        if (o.first != kNone) {
+            o.end = mode != 3 ? n : end;                         // not closed: ran to the end of the slice
+            for (uint32_t q = 0; q < 4; q++) {                   // once merged, the one range carried on for all four candidates
+                const uint32_t rq = ((q & 2u) ? Rp1 : Rp0) >> (16 * (q & 1u)) & 0xffffu;
+                o.t_exit[q] = merged && q ? T[0] + T[q] : T[q];
+                o.r_exit[q] = uint16_t(merged ? Rp0 : rq);
+            }
+        }
+        return o;
+    }
+};
+
 // ------------------------------------------------------------------ phase B2 (one lane per slice)
 
-struct Entry {               // what phase C needs per active stretch
+struct Entry {             // what phase C needs per active stretch
     uint32_t t_start;        // shifts before the stretch = bit position of its first output bit
     uint32_t q;              // entry quarter
 };

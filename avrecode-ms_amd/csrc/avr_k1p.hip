@@ -676,8 +676,6 @@ __global__ __launch_bounds__(64 * kSegWaves) void k_k1p_chain_fix(Plan p, uint32
 }
 
 __device__ __forceinline__ CodeEntry device_code_entry(uint32_t c);
-// per code: { low byte of rLPS << shift per range quarter, the shift per quarter } (see step_pair)
-__device__ __forceinline__ uint2 device_codes2(uint32_t c);
 
 // Replay + phase B1: one lane per chunk, its records in stream order.  est[gc][k] is the state of context k
 // when the chunk is entered, so a lane loads those states (one byte per context, in LDS, laid out (k, lane)
@@ -696,136 +694,18 @@ __device__ __forceinline__ uint2 device_codes2(uint32_t c);
 // state's four range quarters, next state | resolved code << 8 | B1's meta << 16 }.
 constexpr uint32_t kStBypass = 128, kStTerminate = 129, kStPad = 130, kStNone = 131, kReplayStates = 132;
 
-// B1's four candidate ranges, two to a register (16 bits each), stepped with the packed 16-bit instructions: per pair
-// one byte permute picks each candidate's LPS range out of the state's row by the candidate's own range quarter, and the
-// LPS side (range renormalised, its shift) comes out of two more rows of the same shape instead of a count-leading-zeros
-// per candidate (codes2[code] = { rown: low byte of rLPS << shift per quarter, shrow: the shift per quarter }).
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)); }
-__device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)); }
-__device__ __forceinline__ uint32_t pk_shl(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) << __builtin_bit_cast(u16x2, b)); }
-__device__ __forceinline__ uint32_t pk_shr8(uint32_t a) { return (a >> 8) & 0x00ff00ffu; }
-// one bin on a pair of candidates (step_range of avr_k1p.h, twice): returns the two shifts, packed
-__device__ __forceinline__ uint32_t step_pair(uint32_t &Rp, uint32_t row, uint32_t rown, uint32_t shrow, bool sym, uint32_t extra) {
-    const uint32_t sel = ((Rp >> 6) & 0x00030003u) | 0x0c000c00u;   // bytes 0 and 2: the candidate's quarter; 1 and 3: zero
-    const uint32_t rl = __builtin_amdgcn_perm(row, row, sel);
-    const uint32_t rm = pk_sub(Rp, rl);                              // MPS side: range - rLPS, in [128, 511]
-    const uint32_t shm = pk_shr8(rm) ^ 0x00010001u;                  // one shift iff below 256
-    const uint32_t rn = __builtin_amdgcn_perm(rown, rown, sel) | 0x01000100u;   // LPS side, renormalised: in [256, 511]
-    const uint32_t shl = __builtin_amdgcn_perm(shrow, shrow, sel);
-    Rp = sym ? rn : pk_shl(rm, shm);
-    return (sym ? shl : shm) + extra;
-}
-
-// Phase B1 as the kernels walk it (the logic of b1_stretch, avr_k1p.h, which stays the CPU's statement of it): a chunk's
-// stretch summary from its bins in order, eight at a time.  A bin comes as the table entry { x: LPS ranges of its state's
-// four range quarters, y: (code << 8) | (meta << 16), z, w: CodeEntryC's side and adj } (k_k1p_replay has it from its state
-// look-up, k_k1p_b1 from the code).
-// mode: 0 = looking for the LPS that opens the stretch, 1 = four candidate ranges, 2 = they have met, 3 = closed.
-struct B1Walk {
-    uint32_t i0, i1, limit, n, max_stretch;
-    const uint2 *codes2;
-    uint32_t mode, Rp0, Rp1, Tp0, Tp1, T[4], Rm, Tm, end;  // candidates 0, 1 in Rp0 (low, high half), 2, 3 in Rp1; Tp: their shifts since the last flush
-    bool merged;
-    Stretch o;
-
-    __device__ __forceinline__ void init(uint32_t chunk, uint32_t i0_, uint32_t i1_, uint32_t n_, uint32_t max_stretch_, const uint2 *codes2_) {
-        i0 = i0_; i1 = i1_; limit = i0_ + kChunk; n = n_; max_stretch = max_stretch_; codes2 = codes2_;
-        mode = 0; Rp0 = Rp1 = 0x01fe01feu; Tp0 = Tp1 = 0; T[0] = T[1] = T[2] = T[3] = 0; Rm = 510; Tm = 0; end = 0;
-        merged = false;
-        o.first = kNone; o.end = 0; o.exit_q = 0; o.too_long = 0; o.pad[0] = o.pad[1] = 0;
-        for (int q = 0; q < 4; q++) { o.t_exit[q] = 0; o.r_exit[q] = 0; }
-        if (chunk == 0) { o.first = 0; mode = 2; merged = true; }    // opens at bin 0 with the initial range 510 (cabac_code.h:30)
-    }
-    __device__ __forceinline__ void flush_t() {                  // at least every 8 bins: 8 x 9 shifts fit 16 bits with room
-        T[0] += Tp0 & 0xffffu; T[1] += Tp0 >> 16; T[2] += Tp1 & 0xffffu; T[3] += Tp1 >> 16;
-        Tp0 = Tp1 = 0;
-    }
-    __device__ __forceinline__ bool met() const { return Rp0 == Rp1 && (Rp0 >> 16) == (Rp0 & 0xffffu); }
-    __device__ __forceinline__ void one(uint32_t idx, const uint4 &e) {       // bin idx (< n), any mode
-        const CodeEntry ce{e.x, e.y >> 16};
-        const bool boundary = ce.meta & 1u;                      // a coded LPS (code_is_boundary)
-        if (mode == 0) {
-            if (idx < i1 && boundary) {
-                o.first = idx;
-                const uint32_t rown = codes2[(e.y >> 8) & 0xffu].x;              // post_lps_range for the four quarters
-                Rp0 = __builtin_amdgcn_perm(rown, rown, 0x0c010c00u) | 0x01000100u;
-                Rp1 = __builtin_amdgcn_perm(rown, rown, 0x0c030c02u) | 0x01000100u;
-                mode = 1;
-            }
-        } else if (mode == 1) {
-            const bool closing = idx >= limit && boundary;
-            if (closing)
-                o.exit_q |= uint8_t(((Rp0 >> 6) & 3u) | ((Rp0 >> 22) & 3u) << 2 | ((Rp1 >> 6) & 3u) << 4 | ((Rp1 >> 22) & 3u) << 6);
-            const uint2 e2 = codes2[(e.y >> 8) & 0xffu];
-            const uint32_t extra = (ce.meta >> 8) * 0x00010001u;                 // a bypass bin's one shift
-            Tp0 = pk_add(Tp0, step_pair(Rp0, ce.row, e2.x, e2.y, boundary, extra));
-            Tp1 = pk_add(Tp1, step_pair(Rp1, ce.row, e2.x, e2.y, boundary, extra));
-            if (closing) { end = idx + 1; mode = 3; }
-            else if (met()) { Rm = Rp0 & 0xffffu; mode = 2; merged = true; }
-        } else if (mode == 2) {
-            const bool closing = idx >= limit && boundary;
-            if (closing) o.exit_q = uint8_t(((Rm >> 6) & 3) * 0x55u);
-            Tm += step_merged(e);
-            if (closing) { end = idx + 1; mode = 3; }
-            else if (idx >= limit && idx - i0 > max_stretch) { o.too_long = 1; end = idx + 1; mode = 3; }
-        }
-    }
-    __device__ __forceinline__ uint32_t step_merged(const uint4 &e) {         // step_range on the one range left
-        uint32_t v;
-        return step_range_c(CodeEntryC{e.x, e.z, 0u, e.w}, &Rm, &v);
-    }
-    __device__ __forceinline__ void group(uint32_t base, const uint4 e[8]) {  // bins base .. base+7
-        if (mode == 2 && base + 8 <= i1) {                       // merged and inside the chunk: nothing can close the stretch
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) Tm += step_merged(e[j]);
-        } else if (mode == 1 && base + 8 <= i1) {                // four candidates, inside the chunk: the same, and no branch per bin
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint2 e2 = codes2[(e[j].y >> 8) & 0xffu];
-                const bool sym = (e[j].y >> 16) & 1u;
-                const uint32_t extra = (e[j].y >> 24) * 0x00010001u;
-                Tp0 = pk_add(Tp0, step_pair(Rp0, e[j].x, e2.x, e2.y, sym, extra));
-                Tp1 = pk_add(Tp1, step_pair(Rp1, e[j].x, e2.x, e2.y, sym, extra));
-            }
-            flush_t();
-            // candidates that have met stay together: looking once per group is enough, and the group's shifts are in T[] either way
-            if (met()) { Rm = Rp0 & 0xffffu; mode = 2; merged = true; }
-        } else if (mode != 3) {
-            for (uint32_t j = 0; j < 8; j++) if (base + j < n) one(base + j, e[j]);
-            flush_t();
-        }
-    }
-    __device__ __forceinline__ void chunk_done() { if (mode == 0) mode = 3; }  // no LPS in the chunk: no stretch opens here (first stays kNone)
-    __device__ __forceinline__ void tail(uint32_t base, const uint4 e[8]) {      // past the chunk, until the stretch closes
-        for (uint32_t j = 0; j < 8; j++) if (base + j < n && mode != 3) one(base + j, e[j]);
-        flush_t();
-    }
-    __device__ __forceinline__ const Stretch &finish() {
-        if (o.first != kNone) {
-            o.end = mode != 3 ? n : end;                         // not closed: ran to the end of the slice
-            for (uint32_t q = 0; q < 4; q++) {                   // once merged, Rm / Tm carried on for all four candidates
-                const uint32_t rq = ((q & 2u) ? Rp1 : Rp0) >> (16 * (q & 1u)) & 0xffffu;
-                o.t_exit[q] = T[q] + (merged ? Tm : 0u);
-                o.r_exit[q] = uint16_t(merged ? Rm : rq);
-            }
-        }
-        return o;
-    }
-};
-
 // R8: one-byte records (p.recs8; see k_k1p_local): selector = dense id, 126 bypass, 127 terminate, and a byte past the slice's
 // last bin goes to the padding pseudo state by its index -- no code of its own, kCodePad as a two-byte no-op record gets.
 template <bool TILE_CODES, bool R8>
 __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunks, const uint32_t *est, uint8_t *res,
                                                     const int32_t *status, Stretch *stretch, uint32_t max_stretch) {
     extern __shared__ uint32_t replay_lds[];                     // per wave: state dwords [(nk+8)/4][64]
-    __shared__ uint4 info[2 * kReplayStates];
-    __shared__ uint2 codes2[256];
+    __shared__ U4 info[2 * kReplayStates];
+    __shared__ U2 codes2[256];
     constexpr uint32_t kSelOff = R8 ? 128 : 2048;
     __shared__ uint32_t sel_off[kSelOff];
     const uint32_t lane = threadIdx.x & 63, nk = p.n_states;
-    for (uint32_t c = threadIdx.x; c < 256; c += blockDim.x) codes2[c] = device_codes2(c);
+    for (uint32_t c = threadIdx.x; c < 256; c += blockDim.x) codes2[c] = codes2_entry(device_code_entry(c).row);
     uint8_t *stb = reinterpret_cast<uint8_t *>(replay_lds) + (threadIdx.x >> 6) * (((nk + 8) >> 2) << 8) + lane * 4;
     for (uint32_t sel = threadIdx.x; sel < kSelOff; sel += blockDim.x) {
         uint32_t kk;
@@ -850,9 +730,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
             next = st;
             code = st == kStBypass ? kCodeBypass | bin : st == kStTerminate ? code_terminate(bin) : kCodePad;
         }
-        const CodeEntry ce = device_code_entry(code);
-        const CodeEntryC cc = code_entry_c(ce);
-        info[i] = make_uint4(ce.row, next | code << 8 | ce.meta << 16, cc.side, cc.adj);
+        info[i] = b1_entry(device_code_entry(code), next, code);
     }
     __syncthreads();
     const uint32_t gc = blockIdx.x * blockDim.x + threadIdx.x;
@@ -884,7 +762,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
     B1Walk b1;
     b1.init(c, i0, i1, n, max_stretch, codes2);
     // 8 records (16 bytes) -> 8 codes; e[] = their table entries
-    auto eight = [&](const U4 &v, uint32_t &c0, uint32_t &c1, uint4 e[8]) {
+    auto eight = [&](const U4 &v, uint32_t &c0, uint32_t &c1, U4 e[8]) {
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         uint32_t off[8];
 #pragma unroll
@@ -904,7 +782,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
     if (R8) {
         // 8 one-byte records (lo: the first four) -> 8 codes; masked: records at or past `lim` take the padding pseudo state
         const uint32_t pad_off = (((nk + 3) & ~3u) << 6) + ((nk + 3) & 3u);
-        auto eight8 = [&](uint32_t lo, uint32_t hi, uint32_t base, uint32_t lim, auto masked, uint32_t &c0, uint32_t &c1, uint4 e[8]) {
+        auto eight8 = [&](uint32_t lo, uint32_t hi, uint32_t base, uint32_t lim, auto masked, uint32_t &c0, uint32_t &c1, U4 e[8]) {
             uint32_t off[8], bin[8];
 #pragma unroll
             for (uint32_t j = 0; j < 8; j++) {
@@ -926,9 +804,10 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
         // 16 records -> 16 codes, B1 over them, the codes out
         auto sixteen8 = [&](uint32_t base, const U4 &v, auto masked) {
             U4 a;
-            uint4 e[8];
-            eight8(v.x, v.y, base, i1, masked, a.x, a.y, e); b1.group(base, e);
-            eight8(v.z, v.w, base + 8, i1, masked, a.z, a.w, e); b1.group(base + 8, e);
+            U4 e[8];
+            auto group = [&](uint32_t at) { if (decltype(masked)::value) b1.group(at, e); else b1.group_inside(at, e); };   // (unmasked: a whole line below i1)
+            eight8(v.x, v.y, base, i1, masked, a.x, a.y, e); group(base);
+            eight8(v.z, v.w, base + 8, i1, masked, a.z, a.w, e); group(base + 8);
             put16(base, a);
         };
         // from the multiple of 16 at or below rec_off, as k_k1p_local reads it: never an unaligned 16-byte load, whatever the order of the
@@ -941,7 +820,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
             for (uint32_t i = i0 + kChunk; b1.mode != 3 && i < n; i += 8) {
                 const uint2 v = *reinterpret_cast<const uint2 *>(r8 + i);
                 uint32_t c0, c1;
-                uint4 e[8];
+                U4 e[8];
                 eight8(v.x, v.y, i, n, std::true_type{}, c0, c1, e);
                 b1.tail(i, e);
             }
@@ -963,11 +842,11 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
             const U4 *qn = reinterpret_cast<const U4 *>(r + (i + 32 <= last ? i + 32 : last));
             const U4 n0 = qn[0], n1 = qn[1], n2 = qn[2], n3 = qn[3];
             U4 a, b;
-            uint4 e[8];
-            eight(v0, a.x, a.y, e); b1.group(i, e);
-            eight(v1, a.z, a.w, e); b1.group(i + 8, e);
-            eight(v2, b.x, b.y, e); b1.group(i + 16, e);
-            eight(v3, b.z, b.w, e); b1.group(i + 24, e);
+            U4 e[8];
+            eight(v0, a.x, a.y, e); b1.group_inside(i, e);
+            eight(v1, a.z, a.w, e); b1.group_inside(i + 8, e);
+            eight(v2, b.x, b.y, e); b1.group_inside(i + 16, e);
+            eight(v3, b.z, b.w, e); b1.group_inside(i + 24, e);
             put16(i, a);
             put16(i + 16, b);
             v0 = n0; v1 = n1; v2 = n2; v3 = n3;
@@ -977,7 +856,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
             const U4 nop{AVR_NOP_CABAC2, AVR_NOP_CABAC2, AVR_NOP_CABAC2, AVR_NOP_CABAC2};
             const U4 t0 = q[0], t1 = i + 8 < i1 ? q[1] : nop;
             U4 a;
-            uint4 e[8];
+            U4 e[8];
             eight(t0, a.x, a.y, e); b1.group(i, e);
             eight(t1, a.z, a.w, e); b1.group(i + 8, e);
             put16(i, a);
@@ -986,7 +865,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
         // past the chunk: on through the next chunk's bins until the stretch closes (codes not written: not this lane's)
         for (i = i0 + kChunk; b1.mode != 3 && i < n; i += 8) {
             uint32_t c0, c1;
-            uint4 e[8];
+            U4 e[8];
             eight(*reinterpret_cast<const U4 *>(r + i), c0, c1, e);
             b1.tail(i, e);
         }
@@ -1002,28 +881,17 @@ __device__ __forceinline__ CodeEntry device_code_entry(uint32_t c) {
     return CodeEntry{d_tables.packed[2 * (c >> 2)][0], code_sym(c) * 3u};
 }
 
-__device__ __forceinline__ uint2 device_codes2(uint32_t c) {
-    const uint32_t row = device_code_entry(c).row;
-    uint32_t rown = 0, shrow = 0;
-    for (uint32_t q = 0; q < 4; q++) {
-        const uint32_t rl = (row >> (8 * q)) & 0xffu;
-        if (rl) { uint32_t sh; const uint32_t rn = post_lps_range(row, q, &sh); rown |= (rn & 0xffu) << (8 * q); shrow |= sh << (8 * q); }
-    }
-    return make_uint2(rown, shrow);
-}
-
 // Phase B1 from finished codes (the resolved-code entry points; k_k1p_replay does the same walk on the fly): one lane per
 // chunk, a cache line of codes per trip with the next one in flight, eight codes to a group of B1Walk.
 // `tile` != null: the chunk's codes are also written there wave-interleaved (TileCodes), for phase C to read.
 __global__ __launch_bounds__(256) void k_k1p_b1(Plan p, uint32_t total_chunks, const uint8_t *res,
                                                 const int32_t *status, Stretch *st, uint32_t max_stretch, uint8_t *tile) {
-    __shared__ uint4 cinfo[256];                                 // per code: { LPS ranges of its state, (code << 8) | (meta << 16), side, adj }
-    __shared__ uint2 codes2[256];
+    __shared__ U4 cinfo[256];                                    // per code: its b1_entry
+    __shared__ U2 codes2[256];
     {
         const CodeEntry ce = device_code_entry(threadIdx.x);
-        const CodeEntryC cc = code_entry_c(ce);
-        cinfo[threadIdx.x] = make_uint4(ce.row, threadIdx.x << 8 | ce.meta << 16, cc.side, cc.adj);
-        codes2[threadIdx.x] = device_codes2(threadIdx.x);
+        cinfo[threadIdx.x] = b1_entry(ce, 0u, threadIdx.x);
+        codes2[threadIdx.x] = codes2_entry(ce.row);
     }
     __syncthreads();
     const uint32_t gc = blockIdx.x * 256 + threadIdx.x;
@@ -1036,16 +904,17 @@ __global__ __launch_bounds__(256) void k_k1p_b1(Plan p, uint32_t total_chunks, c
     const uint8_t *r = res + p.res_off[slice];
     B1Walk b1;
     b1.init(c, i0, i1, n, max_stretch, codes2);
-    auto eight = [&](uint32_t lo, uint32_t hi, uint4 e[8]) {     // eight codes, first in lo's low byte
+    auto eight = [&](uint32_t lo, uint32_t hi, U4 e[8]) {     // eight codes, first in lo's low byte
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++) e[j] = cinfo[((j < 4 ? lo : hi) >> (8 * (j & 3))) & 0xffu];
     };
     uint8_t *to = tile ? tile + TileCodes::group_at(gc, 0) : nullptr;
-    auto sixteen = [&](uint32_t base, const U4 &v) {
+    auto sixteen = [&](uint32_t base, const U4 &v, auto inside) {    // inside: all sixteen are below i1
         if (to) *reinterpret_cast<U4 *>(to + size_t((base - i0) >> 4) * kTileRowBytes) = v;       // a row a group, as in k_k1p_replay
-        uint4 e[8];
-        eight(v.x, v.y, e); b1.group(base, e);
-        eight(v.z, v.w, e); b1.group(base + 8, e);
+        U4 e[8];
+        auto group = [&](uint32_t at) { if (decltype(inside)::value) b1.group_inside(at, e); else b1.group(at, e); };
+        eight(v.x, v.y, e); group(base);
+        eight(v.z, v.w, e); group(base + 8);
     };
     // a slice's codes are padded to a multiple of 16 (with a group to spare): whole 16-byte loads up to the padded end
     uint32_t i = i0;
@@ -1055,14 +924,14 @@ __global__ __launch_bounds__(256) void k_k1p_b1(Plan p, uint32_t total_chunks, c
         for (; i + 64 <= i1; i += 64) {
             const U4 *qn = reinterpret_cast<const U4 *>(r + (i + 128 <= i1 ? i + 64 : i));     // unconditional: see for_record_groups
             const U4 n0 = qn[0], n1 = qn[1], n2 = qn[2], n3 = qn[3];
-            sixteen(i, v0); sixteen(i + 16, v1); sixteen(i + 32, v2); sixteen(i + 48, v3);
+            sixteen(i, v0, std::true_type{}); sixteen(i + 16, v1, std::true_type{}); sixteen(i + 32, v2, std::true_type{}); sixteen(i + 48, v3, std::true_type{});
             v0 = n0; v1 = n1; v2 = n2; v3 = n3;
         }
-        for (; i < i1; i += 16) sixteen(i, *reinterpret_cast<const U4 *>(r + i));
+        for (; i < i1; i += 16) sixteen(i, *reinterpret_cast<const U4 *>(r + i), std::false_type{});
         b1.chunk_done();
         for (i = i0 + kChunk; b1.mode != 3 && i < n; i += 16) {  // past the chunk, until the stretch closes
             const U4 v = *reinterpret_cast<const U4 *>(r + i);
-            uint4 e[8];
+            U4 e[8];
             eight(v.x, v.y, e); b1.tail(i, e);
             if (b1.mode != 3) { eight(v.z, v.w, e); b1.tail(i + 8, e); }
         }
