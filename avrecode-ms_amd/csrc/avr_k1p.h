@@ -674,6 +674,34 @@ struct B1Walk {
     }
 };
 
+// ---- the replay's state chain (k_k1p_replay's `eight` and `eight8`): replay_step8.  tests/replay_step_emul.cpp runs it on the host
+// against the plain loop per bin (state byte -> table entry -> write-back).
+//
+// Eight bins of one lane: col = the lane's state column (a byte per context), off[j] = where bin j's state byte lives in it (sel_off's
+// value; the pseudo contexts too), bin[j] its bin, info[state << 1 | bin] = b1_entry (next state in byte 0 of .y).  e[j] = bin j's
+// entry, and the column is left as the plain loop leaves it.
+// Read as written the loop is two dependent LDS round trips a bin: bin j+1's state byte may be the one bin j writes.  Here bin j+1's
+// byte is read together with bin j's entry, BEFORE bin j's write-back, and taken only where the two bins' offsets differ; where they
+// are equal the next state of bin j is handed on in a register.  LDS operations of a wave complete in issue order, so that read sees
+// every write up to bin j-1's: one round trip a bin.
+//
+// The states of a column: a context's 7-bit state (pStateIdx << 1 | valMPS), and the pseudo states of what is no context of the
+// batch -- bypass, terminate, padding, none -- which never move.
+constexpr uint32_t kStBypass = 128, kStTerminate = 129, kStPad = 130, kStNone = 131, kReplayStates = 132;
+
+AVR_HD void replay_step8(uint8_t *col, const uint32_t off[8], const uint32_t bin[8], const U4 *info, U4 e[8]) {
+    uint32_t st = col[off[0]];
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) {
+        e[j] = info[(st << 1) | bin[j]];
+        uint32_t ahead = 0;
+        if (j < 7) ahead = col[off[j + 1]];
+        const uint32_t next = e[j].y & 0xffu;
+        col[off[j]] = uint8_t(next);
+        if (j < 7) st = off[j + 1] == off[j] ? next : ahead;
+    }
+}
+
 // ------------------------------------------------------------------ phase B2 (one lane per slice)
 
 struct Entry {             // what phase C needs per active stretch

@@ -691,8 +691,8 @@ __device__ __forceinline__ CodeEntry device_code_entry(uint32_t c);
 // The step is branch-free up to B1's modes.  Two look-ups per bin: sel_off[selector] = where the bin's state
 // byte lives in the lane's column (bypass, terminate, padding and anything that is no context of the batch go
 // to pseudo contexts whose pseudo states 128.. never move), and info[state << 1 | bin] = { LPS ranges of the
-// state's four range quarters, next state | resolved code << 8 | B1's meta << 16 }.
-constexpr uint32_t kStBypass = 128, kStTerminate = 129, kStPad = 130, kStNone = 131, kReplayStates = 132;
+// state's four range quarters, next state | resolved code << 8 | B1's meta << 16 }.  The chain from one bin to the
+// next -- state byte, entry, write-back -- is replay_step8 of avr_k1p.h: one LDS round trip a bin.
 
 // R8: one-byte records (p.recs8; see k_k1p_local): selector = dense id, 126 bypass, 127 terminate, and a byte past the slice's
 // last bin goes to the padding pseudo state by its index -- no code of its own, kCodePad as a two-byte no-op record gets.
@@ -764,17 +764,13 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
     // 8 records (16 bytes) -> 8 codes; e[] = their table entries
     auto eight = [&](const U4 &v, uint32_t &c0, uint32_t &c1, U4 e[8]) {
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        uint32_t off[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8; j++) off[j] = sel_off[((w[j >> 1] >> ((j & 1) * 16)) >> 1) & 0x7ffu];
+        uint32_t off[8], bin[8];
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++) {
-            const uint32_t bin = (w[j >> 1] >> ((j & 1) * 16)) & 1u;
-            uint8_t *sp = stb + off[j];
-            const uint32_t st = *sp;
-            e[j] = info[(st << 1) | bin];
-            *sp = uint8_t(e[j].y);
+            off[j] = sel_off[((w[j >> 1] >> ((j & 1) * 16)) >> 1) & 0x7ffu];
+            bin[j] = (w[j >> 1] >> ((j & 1) * 16)) & 1u;
         }
+        replay_step8(stb, off, bin, info, e);
         // the eight codes (byte 1 of .y) side by side: two byte permutes and an OR per four
         c0 = __builtin_amdgcn_perm(e[1].y, e[0].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[3].y, e[2].y, 0x05010c0cu);
         c1 = __builtin_amdgcn_perm(e[5].y, e[4].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[7].y, e[6].y, 0x05010c0cu);
@@ -791,13 +787,7 @@ __global__ __launch_bounds__(256) void k_k1p_replay(Plan p, uint32_t total_chunk
                 if (decltype(masked)::value) off[j] = base + j < lim ? off[j] : pad_off;
                 bin[j] = b & 1u;
             }
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                uint8_t *sp = stb + off[j];
-                const uint32_t st = *sp;
-                e[j] = info[(st << 1) | bin[j]];
-                *sp = uint8_t(e[j].y);
-            }
+            replay_step8(stb, off, bin, info, e);
             c0 = __builtin_amdgcn_perm(e[1].y, e[0].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[3].y, e[2].y, 0x05010c0cu);
             c1 = __builtin_amdgcn_perm(e[5].y, e[4].y, 0x0c0c0501u) | __builtin_amdgcn_perm(e[7].y, e[6].y, 0x05010c0cu);
         };
