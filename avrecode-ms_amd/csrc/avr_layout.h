@@ -93,7 +93,10 @@ inline K2pLayout k2p_layout(size_t n_slices, uint32_t total_chunks, uint64_t out
     L.ck_pos = c.take(uint64_t(total_chunks) * 4);
     L.fin_range = c.take(uint64_t(n_slices) * 8);
     L.fin_pos = c.take(uint64_t(n_slices) * 4);
-    L.long_chunks = c.take_unrounded(4096);                      // threshold, count and at most 1 022 long slices: a multiple of 256 as it is
+    // threshold, count and the long slices, 1 024 words: at most 1 007 slices where launch_k2p takes the hybrid by the batch's shape
+    // (1 025 .. 61 440 slices); under the test hook k2p_wave = 3 at most 1 022 from 65 slices on, and no more than there are slices
+    // below (tests/test_k2p_ragged.py).  A multiple of 256 as it is
+    L.long_chunks = c.take_unrounded(4096);
     L.sums = c.take(out_total * 4 + 64);                         // + 64: slack behind the last slice's sums; the quote has always had it
     L.total = c.at;
     return L;
