@@ -32,6 +32,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avrecode_ms_amd.h
 
 KIND_CABAC, KIND_RANGE, KIND_CABAC_CODES, KIND_CABAC8 = 0, 1, 2, 3
 KIND_RANGE_KEYS, EST_KEYS = 4, 1026                           # key records: the estimators are resolved on the device
+KIND_RANGE_KEYS8, EST_KEYS8 = 5, 128                          # ... in one byte: bin | dense key id << 1, ids 0..125, SEL8_BYPASS, SEL8_TERMINATE
 SEL_BYPASS, SEL_TERMINATE = 1024, 1025
 SEL8_BYPASS, SEL8_TERMINATE, MAX_STATES8 = 126, 127, 126      # one-byte records (KIND_CABAC8)
 SLICE_OK, SLICE_ZERO_PROB, SLICE_OVERFLOW, SLICE_BAD_RECORD = 0, 1, 2, 3
@@ -167,6 +168,14 @@ SIGNATURES = {
     "avr_batch_begin_group": (c_int, [c_void_p, c_void_p]),
     "avr_batch_add_slice_range_keys": (c_int, [c_void_p, c_void_p, c_size_t]),
     "avr_batch_get_estimators": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]),
+    "avr_batch_begin_group8": (c_int, [c_void_p, c_void_p]),
+    "avr_batch_add_slice_range_keys8": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "avr_range_resolve8_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
+    "avr_range_resolve8_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "avr_range_keys8_verify_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
+    "avr_range_keys8_verify_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "avr_range_resolve_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_void_p]),
     "avr_range_resolve_device": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
@@ -473,8 +482,26 @@ class Batch:
         r = np.ascontiguousarray(recs, dtype=np.uint16)
         return _check(self._L.avr_batch_add_slice_range_keys(self._h, r.ctypes.data, r.size))
 
+    def begin_group8(self, est=None) -> int:
+        """begin_group() for one-byte key records (KIND_RANGE_KEYS8): `est` is EST_KEYS8 x 2 uint8 {pos, neg} in the dense numbering.
+        It fixes the batch's kind; begin_group() on such a batch, and this on any other, raise."""
+        import numpy as np
+        if est is None:
+            return _check(self._L.avr_batch_begin_group8(self._h, None))
+        e = np.ascontiguousarray(est, dtype=np.uint8)
+        if e.size != EST_KEYS8 * 2:
+            raise AvrError(f"a start table of one-byte key records has {EST_KEYS8} x 2 entries, not {e.size}")
+        return _check(self._L.avr_batch_begin_group8(self._h, e.ctypes.data))
+
+    def add_slice_range_keys8(self, recs8) -> int:
+        """K2 from one-byte key records (bin | dense key id << 1; ids 0..125, SEL8_BYPASS, SEL8_TERMINATE): half the bytes over PCIe."""
+        import numpy as np
+        r = np.ascontiguousarray(recs8, dtype=np.uint8)
+        return _check(self._L.avr_batch_add_slice_range_keys8(self._h, r.ctypes.data, r.size))
+
     def get_estimators(self, group: int):
-        """The group's table after the run: EST_KEYS x 2 uint8 {pos, neg}, in the layout begin_group() takes."""
+        """The group's table after the run: EST_KEYS (one-byte key records: EST_KEYS8) x 2 uint8 {pos, neg}, in the layout
+        begin_group() / begin_group8() takes."""
         import numpy as np
         p, n = c_void_p(), c_size_t()
         _check(self._L.avr_batch_get_estimators(self._h, group, ctypes.byref(p), ctypes.byref(n)))
@@ -500,7 +527,7 @@ class Batch:
         p = c_void_p()
         idx = _check(self._L.avr_batch_reserve_slice(self._h, kind, n, None if st is None else st.ctypes.data,
                                                      0 if st is None else st.size, ctypes.byref(p)))
-        ctype = ctypes.c_uint8 if kind in (KIND_CABAC_CODES, KIND_CABAC8) else ctypes.c_uint16
+        ctype = ctypes.c_uint8 if kind in (KIND_CABAC_CODES, KIND_CABAC8, KIND_RANGE_KEYS8) else ctypes.c_uint16
         view = np.ctypeslib.as_array(ctypes.cast(p.value, POINTER(ctype)), shape=(n,)) if n else np.zeros(0, ctype)
         return idx, view
 
@@ -745,7 +772,7 @@ class MultiBatch:
 from .device import (DeviceWorkload, chunk_plan_arrays_device, compact_device, device_plan, encode_tiles, finish_device, finish_word,  # noqa: E402
                      plan_tiles, plan_tiles_device, synth_config)  # noqa: E402  (torch-backed helpers)
 
-__all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS",
+__all__ = ["AvrError", "Batch", "MultiBatch", "build_recode", "RECODE_PATH", "DeviceWorkload", "KIND_CABAC", "KIND_CABAC8", "KIND_RANGE", "KIND_RANGE_KEYS", "EST_KEYS", "KIND_RANGE_KEYS8", "EST_KEYS8",
            "SEL_BYPASS", "SEL_TERMINATE", "SLICE_VERIFY_FAILED", "VERIFY_NONE", "EXPECT_NONE",
            "build_native", "cabac_tables", "device_count", "drop_stop_byte", "encode_tiles", "lib",
            "make_cabac_records", "make_range_records", "plan_tiles", "plan_tiles_device", "chunk_plan_arrays_device", "compact_device",

@@ -162,6 +162,7 @@ struct avr_batch {
     int kind = -1;
     bool recs8 = false;                     // the slices came as one-byte records (AVR_KIND_CABAC8); kind is AVR_KIND_CABAC
     bool keys = false;                      // the slices came as key records (AVR_KIND_RANGE_KEYS); kind is AVR_KIND_RANGE
+    bool keys8 = false;                     // ... as one-byte key records (AVR_KIND_RANGE_KEYS8: keys is set too), or avr_batch_begin_group8 said they will
     size_t n_states = 0;
     bool ran = false;
     Stream stream;
@@ -244,7 +245,10 @@ struct avr_batch {
     avr::States states;
     avr::Output output;
     // the key records of a run that has them, as the resolver and the estimator checker read them
-    avr::Slices key_records() const { return {d_keys.p, d_rec_off.p, d_n_bins.p, nullptr, uint32_t(n_bins.size())}; }
+    avr::Slices key_records() const { return {d_keys.p, d_rec_off.p, d_n_bins.p, nullptr, uint32_t(n_bins.size()), false, {}, keys8 ? 1u : 2u}; }
+    size_t est_keys() const { return keys8 ? AVR_EST_KEYS8 : AVR_EST_KEYS; }      // estimators to a table of this batch ...
+    size_t est_table() const { return est_keys() * 2; }                           // ... and its bytes
+    uint32_t est_pad() const { return keys8 ? avr::est::kKeysPad8 : avr::est::kKeysPad; }
 };
 
 // The refusals the entry points open with.  check_idle: for what changes a batch between runs; check_open: for what adds to a batch
@@ -383,7 +387,7 @@ void avr_batch_destroy(avr_batch *b) { delete b; }
 
 int avr_batch_reset(avr_batch *b) {
     if (int rc = check_idle(b)) return rc;
-    b->kind = -1; b->recs8 = false; b->keys = false; b->n_states = 0; b->ran = false; b->total_bins = 0;
+    b->kind = -1; b->recs8 = false; b->keys = false; b->keys8 = false; b->n_states = 0; b->ran = false; b->total_bins = 0;
     b->group_first.clear(); b->est_in.clear(); b->any_est_in = false; b->est_out_fetched = false;
     b->rec_off.assign(1, 0);
     b->n_bins.clear();
@@ -392,34 +396,42 @@ int avr_batch_reset(avr_batch *b) {
     return AVR_OK;
 }
 
-constexpr size_t kEstTable = size_t(AVR_EST_KEYS) * 2;           // bytes of one table of estimators
-
-int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in) {
+// avr_batch_begin_group (keys8 false) and avr_batch_begin_group8 (true): the first group of a batch without slices fixes which of
+// the two forms of key records the batch holds
+static int begin_group(avr_batch *b, const uint8_t *est_in, bool keys8) {
     if (int rc = check_open(b)) return rc;
     if (b->kind >= 0 && !b->keys) return fail(AVR_ERR_INVALID, "a batch holds slices of one kind only: groups belong to key records");
+    if ((b->kind >= 0 || !b->group_first.empty()) && b->keys8 != keys8)
+        return fail(AVR_ERR_INVALID, keys8 ? "avr_batch_begin_group8 on a batch of two-byte key records: a batch holds slices of one kind only"
+                                           : "avr_batch_begin_group on a batch of one-byte key records (avr_batch_begin_group8): a batch holds slices of one kind only");
     if (b->group_first.size() >= b->max_slices) return fail(AVR_ERR_CAPACITY, "batch holds max_slices=%zu groups", b->max_slices);
-    for (size_t k = 0; est_in && k < AVR_EST_KEYS; k++) {
+    const size_t n_keys = keys8 ? AVR_EST_KEYS8 : AVR_EST_KEYS, table_bytes = 2 * n_keys;
+    for (size_t k = 0; est_in && k < n_keys; k++) {
         const unsigned pos = est_in[2 * k], neg = est_in[2 * k + 1];
         if (pos < 1 || neg < 1 || pos + neg > 0x60)
             return fail(AVR_ERR_INVALID, "start table entry %zu = {%u, %u}: need pos >= 1, neg >= 1, pos + neg <= 0x60", k, pos, neg);
     }
     const size_t g = b->group_first.size();
-    b->est_in.resize((g + 1) * kEstTable);
-    uint8_t *dst = b->est_in.data() + g * kEstTable;
-    if (est_in) memcpy(dst, est_in, kEstTable); else memset(dst, 1, kEstTable);    // fresh: {1, 1}
+    b->keys8 = keys8;
+    b->est_in.resize((g + 1) * table_bytes);
+    uint8_t *dst = b->est_in.data() + g * table_bytes;
+    if (est_in) memcpy(dst, est_in, table_bytes); else memset(dst, 1, table_bytes);    // fresh: {1, 1}
     b->any_est_in |= est_in != nullptr;
     b->group_first.push_back(uint32_t(b->n_bins.size()));
     return int(g);
 }
+int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in) { return begin_group(b, est_in, false); }
+int avr_batch_begin_group8(avr_batch *b, const uint8_t *est_in) { return begin_group(b, est_in, true); }
 
 // Room for one more slice in the pinned staging buffer (padding written); *where = its first element.
 static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_states, size_t n_states, void **where) {
     if (int rc = check_open(b)) return rc;
     if (kind != AVR_KIND_CABAC && kind != AVR_KIND_RANGE && kind != AVR_KIND_CABAC_CODES && kind != AVR_KIND_CABAC8 &&
-        kind != AVR_KIND_RANGE_KEYS)
+        kind != AVR_KIND_RANGE_KEYS && kind != AVR_KIND_RANGE_KEYS8)
         return fail(AVR_ERR_INVALID, "unknown kind %d", kind);
     // key records are K2 records before their estimators are resolved: the batch is an AVR_KIND_RANGE batch whose records the device makes
-    const bool keys = kind == AVR_KIND_RANGE_KEYS;
+    const bool keys8 = kind == AVR_KIND_RANGE_KEYS8;
+    const bool keys = kind == AVR_KIND_RANGE_KEYS || keys8;
     if (keys) kind = AVR_KIND_RANGE;
     // one-byte records are K1 records in another width: the batch is an AVR_KIND_CABAC batch whose staging buffer holds bytes
     const bool recs8 = kind == AVR_KIND_CABAC8;
@@ -427,14 +439,15 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
         if (int rc = check_states8(n_states)) return rc;
         kind = AVR_KIND_CABAC;
     }
-    if ((b->kind >= 0 && (b->kind != kind || b->recs8 != recs8 || b->keys != keys)) || (!keys && !b->group_first.empty()))
+    if ((b->kind >= 0 && (b->kind != kind || b->recs8 != recs8 || b->keys != keys)) || (!keys && !b->group_first.empty()) ||
+        ((b->kind >= 0 || !b->group_first.empty()) && b->keys8 != keys8))    // (a group begun says which form of key records)
         return fail(AVR_ERR_INVALID, "a batch holds slices of one kind only");
     if (n > 0xfffffff0u) return fail(AVR_ERR_INVALID, "slice too long");
     if (b->n_bins.size() >= b->max_slices) return fail(AVR_ERR_CAPACITY, "batch holds max_slices=%zu slices", b->max_slices);
     if (b->total_bins + n > b->max_bins) return fail(AVR_ERR_CAPACITY, "batch holds max_bins=%zu records", b->max_bins);
     const size_t idx = b->n_bins.size();
     if (keys && b->group_first.empty()) {                        // no group begun: a fresh one
-        if (int rc = avr_batch_begin_group(b, nullptr); rc < 0) return rc;
+        if (int rc = begin_group(b, nullptr, keys8); rc < 0) return rc;
     }
     if (kind == AVR_KIND_CABAC) {
         if (n_states > AVR_MAX_STATES) return fail(AVR_ERR_INVALID, "n_states %zu > %d", n_states, AVR_MAX_STATES);
@@ -457,7 +470,7 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
         memset(dst + n, AVR_CODE_BYPASS(0), padded - n);         // the padding value of a resolved stream (bypass 0, never coded)
         b->rec_off.push_back(off + padded);
         *where = dst;
-    } else if (recs8) {
+    } else if (recs8 || keys8) {
         // one byte per record in the same pinned buffer, slice i at BYTE rec_off[i], a multiple of 16 (the one-byte kernels read
         // 16-byte groups); what lies between a slice's last record and the next multiple of 16 is told apart by its index there
         const uint64_t padded = (uint64_t(n) + 15) & ~uint64_t(15);
@@ -476,6 +489,7 @@ static int reserve_slice(avr_batch *b, int kind, size_t n, const uint8_t *init_s
     b->kind = kind;
     b->recs8 = recs8;
     b->keys = keys;
+    b->keys8 = keys8;
     return int(idx);
 }
 
@@ -498,6 +512,7 @@ int avr_batch_add_slice_cabac(avr_batch *b, const uint16_t *recs, size_t n, cons
 }
 int avr_batch_add_slice_range(avr_batch *b, const uint16_t *recs, size_t n) { return add_slice(b, AVR_KIND_RANGE, recs, n, 2, nullptr, 0); }
 int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n) { return add_slice(b, AVR_KIND_RANGE_KEYS, recs, n, 2, nullptr, 0); }
+int avr_batch_add_slice_range_keys8(avr_batch *b, const uint8_t *recs8, size_t n) { return add_slice(b, AVR_KIND_RANGE_KEYS8, recs8, n, 1, nullptr, 0); }
 int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n, const uint8_t *init_states, size_t n_states) {
     return add_slice(b, AVR_KIND_CABAC8, recs8, n, 1, init_states, n_states);
 }
@@ -635,19 +650,19 @@ static int submit_codes(avr_batch *b, uint32_t n32) {
 // A batch of key records: the estimators of every group resolved on the device, d_keys -> d_recs (K2 range records with their
 // padding), the groups' tables after the run left in d_est_out.  Enqueues and returns.
 static int resolve_keys(avr_batch *b, uint32_t n32) {
-    const size_t n = n32, n_groups = b->group_first.size();
+    const size_t n = n32, n_groups = b->group_first.size(), table_bytes = b->est_table();
     std::vector<uint32_t> group_first(b->group_first);
     group_first.push_back(n32);
     int rc;
-    if ((rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(avr::est_layout(n, n_groups, b->plan.total_chunks).total + 256)) ||
-        (rc = b->d_est_out.reserve(n_groups * kEstTable)) || (b->any_est_in && (rc = b->d_est_in.reserve(n_groups * kEstTable))))
+    if ((rc = b->d_group_first.reserve(n_groups + 1)) || (rc = b->d_est_ws.reserve(avr::est_layout(n, n_groups, b->plan.total_chunks, b->est_pad()).total + 256)) ||
+        (rc = b->d_est_out.reserve(n_groups * table_bytes)) || (b->any_est_in && (rc = b->d_est_in.reserve(n_groups * table_bytes))))
         return rc;
     hipStream_t s = b->stream;
     AVR_STAGE(b->d_group_first.p, group_first.data(), n_groups + 1);
     if (b->any_est_in) {                                         // through pinned memory: the copy must not read pageable memory after the call
-        if ((rc = b->h_est_in.reserve(n_groups * kEstTable))) return rc;
-        memcpy(b->h_est_in.p, b->est_in.data(), n_groups * kEstTable);
-        AVR_HIP(hipMemcpyAsync(b->d_est_in.p, b->h_est_in.p, n_groups * kEstTable, hipMemcpyHostToDevice, s));
+        if ((rc = b->h_est_in.reserve(n_groups * table_bytes))) return rc;
+        memcpy(b->h_est_in.p, b->est_in.data(), n_groups * table_bytes);
+        AVR_HIP(hipMemcpyAsync(b->d_est_in.p, b->h_est_in.p, n_groups * table_bytes, hipMemcpyHostToDevice, s));
     }
     b->est_out_fetched = false;
     AVR_HIP(avr::launch_est_resolve(s, b->key_records(), b->d_group_first.p, uint32_t(n_groups), b->any_est_in ? b->d_est_in.p : nullptr,
@@ -681,7 +696,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     int rc;
     if ((b->recs8 ? (rc = b->d_recs8.reserve(total_recs + 16)) : (rc = b->d_recs.reserve(total_recs))) ||
         (!chunked && ((rc = b->d_tiles.reserve(total_chunks)) || (rc = b->d_tile_off.reserve(n_tiles + 1)))) ||
-        (rc = b->d_rec_off.reserve(n + 1)) || (rc = b->h_ndense.reserve(16)) || (b->keys && (rc = b->d_keys.reserve(total_recs))))
+        (rc = b->d_rec_off.reserve(n + 1)) || (rc = b->h_ndense.reserve(16)) || (b->keys && (rc = b->d_keys.reserve(b->keys8 ? total_recs / 2 + 16 : total_recs))))      // (elements of two bytes)
         return rc;
     if (cabac && ((rc = b->d_states.reserve(n * std::max<size_t>(ns, 1))) || (rc = b->d_final.reserve(n * std::max<size_t>(ns, 1))) ||
                   (rc = b->h_final.reserve(n * std::max<size_t>(ns, 1)))))
@@ -700,6 +715,7 @@ static int submit_impl(avr_batch *b, bool use_hint) {
     }
     AVR_HIP(hipEventRecord(b->ev[0], s));
     if (b->recs8) AVR_HIP(hipMemcpyAsync(b->d_recs8.p, b->h_recs.p, total_recs, hipMemcpyHostToDevice, s));        // one byte a record
+    else if (b->keys8) AVR_HIP(hipMemcpyAsync(b->d_keys.p, b->h_recs.p, total_recs, hipMemcpyHostToDevice, s));    // one byte a key record
     else AVR_HIP(hipMemcpyAsync(b->keys ? b->d_keys.p : b->d_recs.p, b->h_recs.p, total_recs * sizeof(uint16_t), hipMemcpyHostToDevice, s));
     AVR_STAGE(b->d_rec_off.p, b->rec_off.data(), n + 1);
     AVR_STAGE(b->d_out_off.p, b->hp.out_off.data(), n + 1);
@@ -877,14 +893,14 @@ int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg
     if (group >= b->group_first.size()) return fail(AVR_ERR_INVALID, "group %zu out of range", group);
     if (!b->est_out_fetched) {                                   // on first use: most callers want the table of a file's last batch only
         if (int rc = select_device(b->device)) return rc;
-        const size_t bytes = b->group_first.size() * kEstTable;
+        const size_t bytes = b->group_first.size() * b->est_table();
         if (int rc = b->h_est_out.reserve(bytes)) return rc;
         AVR_HIP(hipMemcpyAsync(b->h_est_out.p, b->d_est_out.p, bytes, hipMemcpyDeviceToHost, b->stream));
         AVR_HIP(hipStreamSynchronize(b->stream));
         b->est_out_fetched = true;
     }
-    if (pos_neg) *pos_neg = b->h_est_out.p + group * kEstTable;
-    if (n_keys) *n_keys = AVR_EST_KEYS;
+    if (pos_neg) *pos_neg = b->h_est_out.p + group * b->est_table();
+    if (n_keys) *n_keys = b->est_keys();
     return AVR_OK;
 }
 
@@ -1320,9 +1336,10 @@ static int check_est(const Slices &keys, size_t n_slices, const void *other, con
     if (n_slices && !workspace) return fail(AVR_ERR_INVALID, "null workspace");
     if (workspace_bytes < quote(n_slices, n_groups, plan))
         return fail(AVR_ERR_INVALID, "workspace of %zu bytes is smaller than %s()", workspace_bytes, quote_name);
-    if (n_slices && other == keys.recs) return fail(AVR_ERR_INVALID, "%s must not alias keys", name);
+    const char *keys_name = keys.rec_bytes == 1 ? "keys8" : "keys";
+    if (n_slices && other == keys.recs) return fail(AVR_ERR_INVALID, "%s must not alias %s", name, keys_name);
     if ((reinterpret_cast<uintptr_t>(keys.recs) | reinterpret_cast<uintptr_t>(other)) & 15)
-        return fail(AVR_ERR_INVALID, "keys / %s not 16-byte aligned", name);
+        return fail(AVR_ERR_INVALID, "%s / %s not 16-byte aligned", keys_name, name);
     if ((reinterpret_cast<uintptr_t>(est_in) | reinterpret_cast<uintptr_t>(est_out)) & 1)
         return fail(AVR_ERR_INVALID, "est_in / est_out not 2-byte aligned");
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AVR_ERR_INVALID, "workspace not 256-byte aligned");
@@ -1348,6 +1365,42 @@ int avr_range_keys_verify_device(int device, void *stream, const uint16_t *keys,
     const Slices in{keys, rec_off, n_bins, nullptr, uint32_t(n_slices)};
     if (int rc = check_est(in, n_slices, recs, "recs", group_first, n_groups, est_in, est_out, plan, workspace, workspace_bytes, status && first_bad,
                            avr_range_keys_verify_workspace_bytes, "avr_range_keys_verify_workspace_bytes"))
+        return rc;
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_est_verify(hip(stream), in, recs, group_first, uint32_t(n_groups), est_in, est_out, plan, workspace, status, first_bad));
+    return AVR_OK;
+}
+
+// the same two calls for one-byte key records (AVR_KIND_RANGE_KEYS8): Slices::rec_bytes = 1 picks the kernels' other width
+size_t avr_range_resolve8_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan) {
+    if (!plan) return 0;
+    return avr::est_layout(n_slices, n_groups, plan->total_chunks, avr::est::kKeysPad8).total;
+}
+size_t avr_range_keys8_verify_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan) {
+    (void)n_groups;
+    if (!plan) return 0;
+    return avr::est_verify_layout(n_slices, plan->total_chunks, avr::estv::kTabStride8).total;
+}
+
+int avr_range_resolve8_device(int device, void *stream, const uint8_t *keys8, const uint64_t *rec_off, const uint32_t *n_bins,
+                              size_t n_slices, const uint32_t *group_first, size_t n_groups, const uint8_t *est_in, uint8_t *est_out,
+                              const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes, uint16_t *recs_out, int32_t *status) {
+    const Slices in{keys8, rec_off, n_bins, nullptr, uint32_t(n_slices), false, {}, 1};
+    if (int rc = check_est(in, n_slices, recs_out, "recs_out", group_first, n_groups, est_in, est_out, plan, workspace, workspace_bytes, status != nullptr,
+                           avr_range_resolve8_workspace_bytes, "avr_range_resolve8_workspace_bytes"))
+        return rc;
+    if (int rc = select_device(device)) return rc;
+    AVR_HIP(avr::launch_est_resolve(hip(stream), in, group_first, uint32_t(n_groups), est_in, est_out, plan, workspace, recs_out, status));
+    return AVR_OK;
+}
+
+int avr_range_keys8_verify_device(int device, void *stream, const uint8_t *keys8, const uint16_t *recs, const uint64_t *rec_off,
+                                  const uint32_t *n_bins, size_t n_slices, const uint32_t *group_first, size_t n_groups,
+                                  const uint8_t *est_in, const uint8_t *est_out, const avr_chunk_plan *plan, void *workspace,
+                                  size_t workspace_bytes, int32_t *status, uint32_t *first_bad) {
+    const Slices in{keys8, rec_off, n_bins, nullptr, uint32_t(n_slices), false, {}, 1};
+    if (int rc = check_est(in, n_slices, recs, "recs", group_first, n_groups, est_in, est_out, plan, workspace, workspace_bytes, status && first_bad,
+                           avr_range_keys8_verify_workspace_bytes, "avr_range_keys8_verify_workspace_bytes"))
         return rc;
     if (int rc = select_device(device)) return rc;
     AVR_HIP(avr::launch_est_verify(hip(stream), in, recs, group_first, uint32_t(n_groups), est_in, est_out, plan, workspace, status, first_bad));

@@ -27,6 +27,9 @@
 //     because pos < 128 makes (pos + a) >> s a step function of pos with one threshold (fn_normalise).  Scan and chain run over
 //     blocks of kRowBlock rows (RowSeq below), so the longest serial walk over a group is its blocks plus one block's rows, a
 //     step each -- not one per bin, per halving or per row.
+// One-byte key records (AVR_KIND_RANGE_KEYS8: bin | dense id << 1, 128 ids, every one a key) go through the same kernels in a second
+// instantiation (avr_est.hip: Keys8 -- 7 ballots to a key match, tables of 128 entries, 16 records to a 16-byte load); nothing below
+// depends on the width.
 // Everything here also compiles for the CPU: tests/est_emul.cpp runs these functions against a plain restatement.
 #pragma once
 #include <stdint.h>

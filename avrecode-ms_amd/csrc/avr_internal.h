@@ -131,6 +131,7 @@ struct Slices {
     uint32_t n_slices = 0;
     bool tiled = false;                      // in tiles (one lane per slice), not slice-major
     cabac_verify::Form form{};               // K1: which of the verifier's forms that is (K2 records are two bytes wide: tiled says it all)
+    uint32_t rec_bytes = 2;                  // key records (launch_est_resolve, launch_est_verify): 2, or 1 for AVR_KIND_RANGE_KEYS8
     template <class T> const T *as() const { return static_cast<const T *>(recs); }
 };
 // The context states of a K1 run, before and after; what only reads them (the verifier) takes the view.
@@ -197,7 +198,9 @@ hipError_t launch_k1p_code(hipStream_t s, const Slices &in, const avr_chunk_plan
 hipError_t launch_cabac_encode_codes(hipStream_t s, const Slices &in, const Output &o, int32_t want_status = AVR_SLICE_OK);
 // K2 for few, long slices (avr_k2p.hip): range recurrence per slice, coding per chunk into byte sums, carries + finish
 hipError_t launch_k2p(hipStream_t s, const Slices &in, const avr_chunk_plan *pl, uint64_t out_total, void *workspace, const Output &o);
-// the compress direction's estimators (avr_est.hip): key records -> K2 range records, per group of slices; never waits
+// the compress direction's estimators (avr_est.hip): key records -> K2 range records, per group of slices; never waits.  keys.rec_bytes
+// 1: one-byte key records, keys.off in bytes (recs_out at the same offsets in records), tables of AVR_EST_KEYS8 entries, and the
+// workspace est_layout(.., est::kKeysPad8); for launch_est_verify est_verify_layout(.., estv::kTabStride8)
 hipError_t launch_est_resolve(hipStream_t s, const Slices &keys, const uint32_t *group_first, uint32_t n_groups, const uint8_t *est_in,
                               uint8_t *est_out, const avr_chunk_plan *pl, void *workspace, uint16_t *recs_out, int32_t *status);
 // the estimator checker (avr_est_verify.hip): resolved records held to their key records and to each other (avr_est_verify.h);

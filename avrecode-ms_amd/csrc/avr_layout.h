@@ -106,21 +106,23 @@ inline K2pLayout k2p_layout(size_t n_slices, uint32_t total_chunks, uint64_t out
 
 namespace est {
 constexpr uint32_t kKeysPad = 1028;                    // a table's stride in the workspace
+constexpr uint32_t kKeysPad8 = 128;                    // ... of one-byte key records (AVR_KIND_RANGE_KEYS8): the 128 dense ids, nothing to pad
 constexpr uint32_t kWindow = 16;                       // chunks per window
 inline uint64_t n_rows(uint64_t total_chunks, uint32_t W) { return 2 * ((total_chunks + W - 1) / W); }
 }  // namespace est
 
 // slice -> group, first bad slice per group, per row a 32-bit table (counts, then functions) and a 16-bit one (totals, then
-// {pos, neg} at the row's start); rows exist whether a group spans windows or not
+// {pos, neg} at the row's start); rows exist whether a group spans windows or not.  keys_pad: the tables' stride, kKeysPad for two-byte
+// key records, kKeysPad8 for one-byte ones (768 bytes a row)
 struct EstLayout { uint64_t slice_group, group_bad, row32, row16, total; };
-inline EstLayout est_layout(uint64_t n_slices, uint64_t n_groups, uint64_t total_chunks) {
+inline EstLayout est_layout(uint64_t n_slices, uint64_t n_groups, uint64_t total_chunks, uint32_t keys_pad = est::kKeysPad) {
     EstLayout L;
     Cursor c;
     const uint64_t rows = est::n_rows(total_chunks, est::kWindow);
     L.slice_group = c.take(4 * n_slices);
     L.group_bad = c.take(4 * n_groups);
-    L.row32 = c.take_unrounded(rows * est::kKeysPad * 4);
-    L.row16 = c.take_unrounded(rows * est::kKeysPad * 2);        // directly behind row32, unrounded: the header documents 6 168 bytes a row
+    L.row32 = c.take_unrounded(rows * keys_pad * 4);
+    L.row16 = c.take_unrounded(rows * keys_pad * 2);             // directly behind row32, unrounded: the header documents 6 168 bytes a row
     L.total = c.at;
     return L;
 }
@@ -129,21 +131,23 @@ inline EstLayout est_layout(uint64_t n_slices, uint64_t n_groups, uint64_t total
 
 namespace estv {
 constexpr uint32_t kTabStride = 1028;                  // a 16-bit table's stride in the workspace
+constexpr uint32_t kTabStride8 = 128;                  // ... of one-byte key records
 constexpr uint32_t kSpan = 16;                         // chunks per span (the checker's own: nothing ties it to the resolver's window)
 inline uint64_t n_slots(uint64_t total_chunks, uint32_t S) { return 2 * ((total_chunks + S - 1) / S); }
 }  // namespace estv
 
 // slice -> group, then per piece slot a 16-bit table (what the key's next bin must carry after the piece, then the table at the
 // piece's start) and a second one for the aggregate of the block of pieces that ends there; no larger than EstLayout for the same
-// batch, so the resolver's workspace can be handed on as it stands
+// batch, so the resolver's workspace can be handed on as it stands.  stride: kTabStride, or kTabStride8 for one-byte key records (512
+// bytes a slot)
 struct EstVerifyLayout { uint64_t slice_group, tab, agg, total; };
-inline EstVerifyLayout est_verify_layout(uint64_t n_slices, uint64_t total_chunks) {
+inline EstVerifyLayout est_verify_layout(uint64_t n_slices, uint64_t total_chunks, uint32_t stride = estv::kTabStride) {
     EstVerifyLayout L;
     Cursor c;
     const uint64_t slots = estv::n_slots(total_chunks, estv::kSpan);
     L.slice_group = c.take(4 * n_slices);
-    L.tab = c.take_unrounded(slots * estv::kTabStride * 2);
-    L.agg = c.take_unrounded(slots * estv::kTabStride * 2);
+    L.tab = c.take_unrounded(slots * stride * 2);
+    L.agg = c.take_unrounded(slots * stride * 2);
     L.total = c.at;
     return L;
 }

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 
-from . import EST_KEYS, KIND_CABAC, KIND_CABAC8, KIND_RANGE, KIND_RANGE_KEYS, MAX_STATES8, NOP_CABAC, NOP_RANGE, AvrError, SynthConfig, _check, lib
+from . import EST_KEYS, EST_KEYS8, KIND_CABAC, KIND_CABAC8, KIND_RANGE, KIND_RANGE_KEYS, KIND_RANGE_KEYS8, MAX_STATES8, NOP_CABAC, NOP_RANGE, AvrError, SynthConfig, _check, lib
 
 
 def synth_config(workload: int, scale_permille: int = 1000, first_slice: int = 0) -> SynthConfig:
@@ -359,33 +359,74 @@ class DeviceWorkload:
     @classmethod
     def from_device_keys(cls, key_flat, rec_off, n_bins, group_first, est_in=None, device_index=0, plan="torch"):
         """The same from slice-major key records already on the device (a synthetic K1 record is a key record)."""
+        return cls._from_device_keys(KIND_RANGE_KEYS, key_flat, rec_off, n_bins, group_first, est_in, device_index, plan)
+
+    @classmethod
+    def _from_device_keys(cls, kind, key_flat, rec_off, n_bins, group_first, est_in, device_index, plan):
+        """A workload of key records of either width: est_out sized by the kind's table, rec_flat two-byte records at the keys' rec_off."""
         import numpy as np
         import torch
         dev = n_bins.device
         order, tile_off = plan_tiles_device(n_bins) if plan == "device" else plan_tiles(n_bins)
         tiles = torch.empty(max(int(tile_off[-1].item()), 1) * 16, dtype=torch.uint8, device=dev)
-        w = cls(KIND_RANGE_KEYS, device_index, n_bins, order, tile_off, tiles, None, 0, plan)
+        w = cls(kind, device_index, n_bins, order, tile_off, tiles, None, 0, plan)
         w.key_flat, w.rec_off = key_flat, rec_off
         w.group_first = torch.from_numpy(np.asarray(group_first, dtype=np.int32)).to(dev)
         w.n_groups = w.group_first.numel() - 1
         w.est_in = est_in
-        w.est_out = torch.empty(max(w.n_groups, 1) * EST_KEYS * 2, dtype=torch.uint8, device=dev)
-        w.rec_flat = torch.empty_like(key_flat)
+        w.est_out = torch.empty(max(w.n_groups, 1) * (EST_KEYS8 if kind == KIND_RANGE_KEYS8 else EST_KEYS) * 2, dtype=torch.uint8, device=dev)
+        w.rec_flat = torch.empty(key_flat.numel(), dtype=torch.int16, device=dev)
         return w
 
-    def resolve_keys(self):
-        """avr_range_resolve_device alone: the K2 records (slice-major, self.rec_off) of this key workload, the groups' tables
-        in self.est_out; enqueues and returns."""
+    @classmethod
+    def from_host_keys8(cls, recs8_list, group_first, tables=None, device_index=0, gap=0, plan="torch", pad_bytes=None):
+        """ONE-BYTE key records (bin | dense key id << 1, KIND_RANGE_KEYS8) from the host with their groups, as from_host_keys:
+        slice i at byte rec_off[i], a multiple of 16; tables[g]: EST_KEYS8 x 2 uint8.  `gap`: groups of sixteen bytes left unused
+        between slices (plan="torch" only).  The padding and the gaps hold pad_bytes (a uint8 array repeated over the whole buffer;
+        default 0xee): every byte value is a key, so the kernels must tell padding by its index.  plan="device": the offsets from avr_plan_chunks_device with rec_round = 16."""
+        import numpy as np
         import torch
-        if self.kind != KIND_RANGE_KEYS:
+        dev = torch.device("cuda", device_index)
+        nb = np.array([len(r) for r in recs8_list], dtype=np.int32)
+        with torch.cuda.device(dev):
+            n_bins = torch.from_numpy(nb).to(dev)
+            if plan == "device":
+                if gap:
+                    raise AvrError("from_host_keys8: the device planner leaves no gaps")
+                d_off = device_plan(n_bins, 0, 16)[0]["rec_off"]
+                rec_off = d_off.cpu().numpy()
+            else:
+                rec_off = np.zeros(len(recs8_list) + 1, dtype=np.int64)
+                rec_off[1:] = np.cumsum((nb.astype(np.int64) + 15) // 16 * 16 + 16 * gap)
+                d_off = torch.from_numpy(rec_off).to(dev)
+            size = int(rec_off[-1]) + 16
+            flat = np.full(size, 0xEE, np.uint8) if pad_bytes is None else np.resize(np.asarray(pad_bytes, dtype=np.uint8), size)
+            for i, r in enumerate(recs8_list):
+                flat[rec_off[i]:rec_off[i] + len(r)] = np.asarray(r, dtype=np.uint8)
+            est_in = None if tables is None else torch.from_numpy(np.ascontiguousarray(np.stack(tables), np.uint8)).to(dev)
+            return cls.from_device_keys8(torch.from_numpy(flat).to(dev), d_off, n_bins, group_first, est_in, device_index, plan)
+
+    @classmethod
+    def from_device_keys8(cls, key8_flat, rec_off, n_bins, group_first, est_in=None, device_index=0, plan="torch"):
+        """The same from slice-major one-byte key records already on the device (uint8 tensor, readable to rec_off[-1] rounded up to 16).
+        The resolved two-byte records go to self.rec_flat at the same rec_off, counted in records."""
+        return cls._from_device_keys(KIND_RANGE_KEYS8, key8_flat, rec_off, n_bins, group_first, est_in, device_index, plan)
+
+    def resolve_keys(self):
+        """avr_range_resolve_device (one-byte key records: avr_range_resolve8_device) alone: the K2 records (slice-major, self.rec_off)
+        of this key workload, the groups' tables in self.est_out; enqueues and returns."""
+        import torch
+        if self.kind not in (KIND_RANGE_KEYS, KIND_RANGE_KEYS8):
             raise AvrError("not a workload of key records")
         p = self._chunk_plan()
         L = lib()
+        quote, call = ((L.avr_range_resolve8_workspace_bytes, L.avr_range_resolve8_device) if self.kind == KIND_RANGE_KEYS8 else
+                       (L.avr_range_resolve_workspace_bytes, L.avr_range_resolve_device))
         if "ws_est" not in p:
-            n = L.avr_range_resolve_workspace_bytes(self.n_slices, self.n_groups, ctypes.byref(p["plan"]))
+            n = quote(self.n_slices, self.n_groups, ctypes.byref(p["plan"]))
             p["ws_est"] = torch.empty(n + 256, dtype=torch.uint8, device=self.n_bins.device)
             p["ws_est_bytes"] = n
-        _check(L.avr_range_resolve_device(
+        _check(call(
             self.device_index, _stream_ptr(torch), self.key_flat.data_ptr(), self.rec_off.data_ptr(), self.n_bins.data_ptr(),
             self.n_slices, self.group_first.data_ptr(), self.n_groups, self.est_in.data_ptr() if self.est_in is not None else None,
             self.est_out.data_ptr(), ctypes.byref(p["plan"]), _aligned(p["ws_est"]), p["ws_est_bytes"],
@@ -398,16 +439,18 @@ class DeviceWorkload:
         nothing with the resolver.  Returns (self.status, first_bad): first_bad an int32 tensor (VERIFY_NONE reads as -1; n_bins: the
         slice's padding or its group's table), SLICE_VERIFY_FAILED in the status of a slice with a finding.  Enqueues and returns."""
         import torch
-        if self.kind != KIND_RANGE_KEYS:
+        if self.kind not in (KIND_RANGE_KEYS, KIND_RANGE_KEYS8):
             raise AvrError("verify_keys: not a workload of key records")
         p = self._chunk_plan()
         L = lib()
+        quote, call = ((L.avr_range_keys8_verify_workspace_bytes, L.avr_range_keys8_verify_device) if self.kind == KIND_RANGE_KEYS8 else
+                       (L.avr_range_keys_verify_workspace_bytes, L.avr_range_keys_verify_device))
         if "ws_estv" not in p:
-            n = L.avr_range_keys_verify_workspace_bytes(self.n_slices, self.n_groups, ctypes.byref(p["plan"]))
+            n = quote(self.n_slices, self.n_groups, ctypes.byref(p["plan"]))
             p["ws_estv"] = torch.empty(n + 256, dtype=torch.uint8, device=self.n_bins.device)
             p["ws_estv_bytes"] = n
         first_bad = torch.empty(self.n_slices, dtype=torch.int32, device=self.n_bins.device)
-        _check(L.avr_range_keys_verify_device(
+        _check(call(
             self.device_index, _stream_ptr(torch), self.key_flat.data_ptr(), self.rec_flat.data_ptr(), self.rec_off.data_ptr(),
             self.n_bins.data_ptr(), self.n_slices, self.group_first.data_ptr(), self.n_groups,
             self.est_in.data_ptr() if self.est_in is not None else None, self.est_out.data_ptr(), ctypes.byref(p["plan"]),

@@ -38,6 +38,14 @@
  *       bits 1..11 model key: 0..1023 a context id, AVR_SEL_BYPASS, AVR_SEL_TERMINATE -- the 1026 keys h264_model keeps in flat_[]
  *                  (residual hooks off); bits 12..15 zero.  The device looks up and updates the key's {pos, neg} estimator
  *                  (recode.cpp:823-827, 1037-1052) and makes the range record: the same two bytes feed both directions.
+ *   one-byte key record (AVR_KIND_RANGE_KEYS8), uint8_t: a key is only an index into its group's table of estimators, and a real
+ *   file meets at most 126 contexts, so a dense id does what the 11-bit key does in half the bytes over PCIe
+ *       bit 0      bin value
+ *       bits 1..7  dense key id: 0..125 the caller's model keys in a numbering the caller keeps fixed over a whole GROUP,
+ *                  AVR_SEL8_BYPASS (126), AVR_SEL8_TERMINATE (127).  All 128 ids are keys: no record value is malformed.
+ *   The layout is AVR_KIND_CABAC8's: slice-major, slice i at BYTE rec_off[i], a multiple of 16, readable up to the next multiple of 16;
+ *   the bytes past n_bins are padding of any value, told apart by index: never counted, never matched, never validated.  A group with
+ *   more than 126 keys keeps the two-byte form.
  *
  * Environment.  The library reads three variables, once per process; NONE of them can change a coded byte -- they pick
  * between mappings that produce the same bytes (tests/ run all of them against the oracle):
@@ -82,6 +90,9 @@ extern "C" {
  *   key records    a bit of 12..15 set, or a key above AVR_SEL_TERMINATE.  The later slices of the record's GROUP have no defined
  *                  estimators, so that slice AND EVERY LATER SLICE OF ITS GROUP come back AVR_SLICE_BAD_RECORD with length 0; earlier
  *                  slices and other groups are coded.  (No rule about put_terminate(1): K2 has none.)
+ *   key records,   no record value is malformed; a rec_off that is not a multiple of 16 makes its slice a bad one by the group rule
+ *   one-byte       above (that slice and every later slice of its group: AVR_SLICE_BAD_RECORD, length 0).  Such a slice is read from
+ *                  the multiple of 16 below its rec_off, and none of its resolved records is written.
  * Enforced by the packers (avr_pack_tiles_device, avr_pack_tiles8_device, avr_pack_tiles8_narrow_device) with the tile coders behind them, by the K1p calls
  * (avr_cabac_encode_chunked_device and its hinted, second-pass and parts forms, avr_cabac8_encode_chunked_device,
  * avr_cabac_resolve_device), by K2p (avr_range_encode_chunked_device), by avr_range_resolve_device and so by the batch API on either path: a slice's status
@@ -122,6 +133,8 @@ extern "C" {
 #define AVR_KIND_CABAC8 3        /* K1 from ONE-BYTE records (bin, dense selector), see avr_batch_add_slice_cabac8 */
 #define AVR_KIND_RANGE_KEYS 4    /* K2 from KEY records (bin, model key): the estimators are resolved on the device, see avr_batch_begin_group */
 #define AVR_EST_KEYS 1026        /* estimators to a table: keys 0 .. AVR_SEL_TERMINATE */
+#define AVR_KIND_RANGE_KEYS8 5   /* K2 from ONE-BYTE key records (bin, dense key id), see avr_batch_begin_group8 */
+#define AVR_EST_KEYS8 128        /* estimators to a table of one-byte key records: ids 0 .. 125, AVR_SEL8_BYPASS, AVR_SEL8_TERMINATE */
 
 /* One-byte K1 records (AVR_KIND_CABAC8): bit 0 = the bin, bits 1..7 = a dense selector -- 0 .. 125 the slice's contexts in the
  * order the recorder met them (its ids are dense by first appearance already: INTEGRATION.md), AVR_SEL8_BYPASS, AVR_SEL8_TERMINATE.
@@ -195,8 +208,23 @@ int avr_batch_add_slice_cabac8(avr_batch *b, const uint8_t *recs8, size_t n,
 int avr_batch_begin_group(avr_batch *b, const uint8_t *est_in);
 int avr_batch_add_slice_range_keys(avr_batch *b, const uint16_t *recs, size_t n);
 int avr_batch_get_estimators(avr_batch *b, size_t group, const uint8_t **pos_neg, size_t *n_keys);
+/* K2 from ONE-BYTE key records (AVR_KIND_RANGE_KEYS8, above): the same slices in half the bytes over PCIe, for groups that meet at most
+ * 126 keys.  A table (est_in, avr_batch_get_estimators: n_keys = AVR_EST_KEYS8) holds AVR_EST_KEYS8 = 128 {pos, neg} byte pairs in the
+ * dense numbering.  avr_batch_begin_group8 is avr_batch_begin_group for this kind -- 128 pairs or NULL, the same validity rule, the
+ * group's index returned -- and a call of its own because a group may be begun before the batch's first slice says which kind it
+ * holds: it fixes the batch's kind.  avr_batch_begin_group on a batch of this kind is AVR_ERR_INVALID, and so is avr_batch_begin_group8
+ * on a batch of any other kind.  Without a group begun, the first slice opens a fresh one.  avr_batch_submit stages one byte a record
+ * (avr_batch_timings()[0] shows it), runs avr_range_resolve8_device into the batch's two-byte record buffer and then the K2 path an
+ * AVR_KIND_RANGE_KEYS batch of the same slices takes; avr_batch_set_verify runs the K2 verifier over the resolver's output and then
+ * avr_range_keys8_verify_device.  Bytes, lengths, statuses, first_bad and tables are those of an AVR_KIND_RANGE_KEYS batch given the
+ * widened records (id << 1 | bin, the ids being valid two-byte keys), table entries 0..127.
+ * NOT WIRED, deliberately: avr_multi and the `recode` command line take the two-byte form only.  Both are also linked against the CPU
+ * stand-in of the batch calls that the tests keep (tests/cpu_batch.cpp), which knows no symbol newer than itself; INTEGRATION.md shows
+ * the adapter side (numbering keys densely by first appearance over a file, choosing the form per file). */
+int avr_batch_begin_group8(avr_batch *b, const uint8_t *est_in);
+int avr_batch_add_slice_range_keys8(avr_batch *b, const uint8_t *recs8, size_t n);
 /* Zero-copy form of the calls above: room for a slice of n elements (uint16_t records for AVR_KIND_CABAC /
- * AVR_KIND_RANGE / AVR_KIND_RANGE_KEYS, uint8_t codes for AVR_KIND_CABAC_CODES, uint8_t records for AVR_KIND_CABAC8) in the batch's pinned staging buffer, which the H2D copy
+ * AVR_KIND_RANGE / AVR_KIND_RANGE_KEYS, uint8_t codes for AVR_KIND_CABAC_CODES, uint8_t records for AVR_KIND_CABAC8 / AVR_KIND_RANGE_KEYS8) in the batch's pinned staging buffer, which the H2D copy
  * reads directly; the caller writes exactly n elements to *buffer before avr_batch_submit / avr_batch_run (the padding
  * after them is already in place).  init_states / n_states as for avr_batch_add_slice_cabac (copied now), ignored
  * for the other kinds.  A recorder that appends here saves one pass over its records.  Returns the slice index. */
@@ -232,7 +260,7 @@ int avr_batch_run_info(avr_batch *b, uint32_t info[4]);
  * all 0 for a run of a batch without slices, as are avr_batch_verify_ms, avr_batch_verify_est_ms and avr_batch_restore_ms */
 int avr_batch_timings(avr_batch *b, float ms[4]);
 
-/* Verification of a K2 batch (AVR_KIND_RANGE, AVR_KIND_RANGE_KEYS) on the device: off by default, and then nothing of a run differs.
+/* Verification of a K2 batch (AVR_KIND_RANGE, AVR_KIND_RANGE_KEYS, AVR_KIND_RANGE_KEYS8) on the device: off by default, and then nothing of a run differs.
  * avr_batch_set_verify(b, 1): from the next avr_batch_submit on, the verifier (avr_range_verify_tiles_device on the one-lane-per-slice
  * path, avr_range_verify_slices_device over the slice-major records on the K2p path -- for key records, the resolver's output) is
  * enqueued behind the encode kernels on the batch's stream; avr_batch_submit still does not wait.  The setting stays until it is set
@@ -926,6 +954,32 @@ size_t avr_finish_workspace_bytes(size_t n_slices);                             
 int avr_finish_device(int device, void *stream, const uint8_t *out, const uint64_t *out_off, const uint32_t *out_len,
                       const int32_t *status /* or NULL: all OK */, size_t n_slices, const uint32_t *finish /* n, device */,
                       uint8_t *dense, uint64_t dense_capacity, uint64_t *dense_off /* n + 1 */, void *workspace, size_t workspace_bytes) AVR_NOWAIT;
+
+/* ------------------------------------------------------------------ the estimators from ONE-BYTE key records (AVR_KIND_RANGE_KEYS8)
+ * avr_range_resolve_device and avr_range_keys_verify_device for one-byte key records (format above): the same kernels in another
+ * width, and the contracts of the two-byte calls word for word -- enqueue on `stream` and return, no wait, no allocation, nothing
+ * written outside the documented extents, the same refusals -- with these differences:
+ *   keys8         one byte a record; slice i at BYTE rec_off[i], a multiple of 16 (else: the group rule above, AVR_SLICE_BAD_RECORD),
+ *                 readable to the next multiple of 16; what lies past n_bins there may hold anything.  16-byte aligned.
+ *   recs_out/recs two-byte K2 range records at the SAME rec_off counted in RECORDS: bin | pos << 1 | neg << 8 for [0, n_bins),
+ *                 AVR_NOP_RANGE from n_bins to the slice's next multiple of 8 -- not 16: the K2 packers, K2p and the K2 verifier read what
+ *                 they read behind the two-byte resolver -- and nothing beyond.  recs_out may not alias keys8.  The checker's rule (1)
+ *                 reads bit 0 of the byte, its rule (4) keeps the extent of 8.
+ *   est_in/est_out  tables of AVR_EST_KEYS8 = 128 byte pairs in the dense numbering
+ *   workspace     resolver: align256(4 n_slices) + align256(4 n_groups) + 2 ceil(total_chunks / 16) * 768
+ *                 checker:  align256(4 n_slices) + 2 ceil(total_chunks / 16) * 512, never above the resolver's
+ * The checker gives a slice whose rec_off is not a multiple of 16, if it takes part, a finding at bin 0 and reads nothing of it. */
+size_t avr_range_resolve8_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan);
+int avr_range_resolve8_device(int device, void *stream, const uint8_t *keys8, const uint64_t *rec_off, const uint32_t *n_bins, size_t n_slices,
+                              const uint32_t *group_first, size_t n_groups, const uint8_t *est_in, uint8_t *est_out,
+                              const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
+                              uint16_t *recs_out, int32_t *status) AVR_NOWAIT;
+size_t avr_range_keys8_verify_workspace_bytes(size_t n_slices, size_t n_groups, const avr_chunk_plan *plan);
+int avr_range_keys8_verify_device(int device, void *stream, const uint8_t *keys8, const uint16_t *recs, const uint64_t *rec_off,
+                                  const uint32_t *n_bins, size_t n_slices, const uint32_t *group_first, size_t n_groups,
+                                  const uint8_t *est_in /* may be NULL */, const uint8_t *est_out /* may be NULL */,
+                                  const avr_chunk_plan *plan, void *workspace, size_t workspace_bytes,
+                                  int32_t *status, uint32_t *first_bad) AVR_NOWAIT;
 
 /* ------------------------------------------------------------------ dense context ids
  * A context is identified by the offset of its state byte in libavcodec's cabac_state[1024]
